@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Benchmark of the PRAM per-query hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 A "step" is one pass of the hot path over one batch of synthetic query frames (16 per GPU by default =
 BASELINE configs[1]; ``--batch-total Q`` shards Q queries over the N ranks instead = configs[2] / [4]):
@@ -12,9 +12,12 @@ with the single all-gather of the fixed-size result records.
 With ``--gpus N`` (N > 1) and no launcher in the environment the script starts its own N ranks
 (``torch.distributed.run``, one process per GPU over RCCL) and refuses to run when fewer than N GPUs are visible.
 
-Rank 0 prints ONE JSON line (contract in the task statement): metric / value (whole-job queries/s) / roofline
-(attention kernel) / parity (one untimed query checked against the oracle, stage by stage) / cpu_baseline (the
-oracle on the host cores, per stage, N = 1 only).
+Rank 0 prints ONE JSON line (contract in the task statement): metric / value (whole-job queries/s) / ms_per_step (one
+timed step).  A plain run does only what that headline needs: set up, warm up, time the K steps, print the line.
+``--full`` adds, after the timed steps: roofline (attention kernel, one extra instrumented step) / power / parity
+(timed queries checked against the oracle, stage by stage) / alt (other configurations of the path) / cpu_baseline
+(the oracle on the host cores, per stage, N = 1 only).  ``--dump-outputs DIR`` writes what the last timed step
+computed as DIR/<name>.npy (inputs are seeded: the same arguments give the same inputs in every run and build).
 """
 from __future__ import annotations
 
@@ -456,6 +459,34 @@ def pmc_traffic(precision):
         return None
 
 
+DUMP_BUDGET_BYTES = 64 * 10 ** 6      # --dump-outputs: all files together, .npy headers included
+
+
+def dump_outputs(path, arrays, budget=DUMP_BUDGET_BYTES):
+    """--dump-outputs: write every tensor of `arrays` as path/<name>.npy, float32 (float64 stays float64; integer and boolean
+    outputs are exact in float32 at these sizes).  The smallest arrays are written first, each whole while it fits its share of
+    what is left of `budget`; an array larger than its share is written as a fixed sample of its flattened elements (positions
+    drawn by a generator seeded with 0, in ascending order: the same positions for the same shape in every run and every build).
+    -> {name: {"shape": [...], "written": elements written}}"""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    items = sorted(((k, v) for k, v in arrays.items() if torch.is_tensor(v)), key=lambda kv: kv[1].numel())
+    left, report = budget, {}
+    for i, (name, t) in enumerate(items):
+        a = t.detach().cpu()
+        a = a.double() if a.dtype == torch.float64 else a.float()
+        share = left // (len(items) - i)
+        n_max = max(1, (share - 128) // a.element_size())      # (128: the .npy header)
+        if a.numel() > n_max:
+            pos = torch.randperm(a.numel(), generator=torch.Generator().manual_seed(0))[:n_max].sort().values
+            a = a.reshape(-1)[pos]
+        f = os.path.join(path, f"{name}.npy")
+        np.save(f, a.contiguous().numpy())
+        left -= os.path.getsize(f)
+        report[name] = {"shape": list(t.shape), "written": int(a.numel())}
+    return report
+
+
 _MASKED = []      # (keeps the HIP handles of masked streams alive for the process)
 
 
@@ -565,6 +596,8 @@ class Job:
                            for i in range(max(1, inflight))]
         self.issued = 0
         self.gather_events = None      # world > 1: main() arms it for the timed steps (HIP events around every all-gather)
+        self.keep_out = False          # --dump-outputs: main() sets it; step() then keeps the pipeline's outputs of the last step
+        self.last_out = None
 
     def _build_segk(self, q0, kpts):
         """The matcher's real call pattern (localization/multimap3d.py:112-139 -> singlemap3d.py:143-154): per query, for each of
@@ -629,18 +662,22 @@ class Job:
         sizes = self.shard_sizes if self.uneven else None
         i = self.issued
         self.issued += 1
+        out = None
         if self.lanes is None:
             if self.h2d:
                 self._upload()
             if self.graphs is not None:
-                self.graphs[0].replay()
+                out = self.graphs[0].replay()
                 rec = self.graphs[0].record
             elif self.segk:
                 rec = self._segk_step()
             else:
                 im, rf = self.rot[i % len(self.rot)]
-                rec = QueryPipeline.pack_record(self.pipe.run(im, rf, stages=self.stages))
+                out = self.pipe.run(im, rf, stages=self.stages)
+                rec = QueryPipeline.pack_record(out)
             self.last_local = rec
+            if self.keep_out:
+                self.last_out = out
             return gather_records(rec, sizes)
         lane = self.lanes[i % len(self.lanes)]
         with torch.cuda.stream(lane):
@@ -648,14 +685,17 @@ class Job:
                 self._upload()
             if self.graphs is not None:
                 g = self.graphs[i % len(self.graphs)]
-                g.replay()
+                out = g.replay()
                 rec = g.record
             elif self.segk:
                 rec = self._segk_step()
             else:
                 im, rf = self.rot[i % len(self.rot)]
-                rec = QueryPipeline.pack_record(self.pipe.run(im, rf, stages=self.stages))
+                out = self.pipe.run(im, rf, stages=self.stages)
+                rec = QueryPipeline.pack_record(out)
         self.last_local = rec          # this rank's own records of the step just issued (main(): checked against its slice of the gather)
+        if self.keep_out:
+            self.last_out = out
         if self.world == 1:
             return rec
         # the (tiny) all-gather stays on the one main stream, in step order on every rank: RCCL never sees
@@ -743,10 +783,17 @@ def main():
     ap.add_argument("--latency", action="store_true",
                     help="the reference's online loop (localization/loc_by_rec_online.py:109-133): ONE query per step, one step at "
                          "a time, graph replay; ms_per_step is the per-query latency")
-    ap.add_argument("--cpu-queries", type=int, default=4, help="CPU-baseline sample size (0 = skip)")
-    ap.add_argument("--no-parity", action="store_true", help="skip the oracle parity gate (kernel profiling runs)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline does not need, after the timed steps: the oracle parity gate, the "
+                         "attention roofline (one extra instrumented step), socket power, the 'alt' configurations and the CPU baseline. "
+                         "Without it the run sets up, warms up, times the steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (its result record and the pipeline's "
+                         "output tensors) as DIR/<name>.npy, float32, at most 64 MB in all (larger outputs: a fixed seeded sample)")
+    ap.add_argument("--cpu-queries", type=int, default=4, help="--full: CPU-baseline sample size (0 = skip)")
+    ap.add_argument("--no-parity", action="store_true", help="--full: skip the oracle parity gate (kernel profiling runs)")
     ap.add_argument("--alt", default="auto", choices=["auto", "on", "off"],
-                    help="also time, in the same run (6 steps each), AdaGML, the exact-fp32 path, the secondary 512 x 1024 matcher "
+                    help="--full: also time, in the same run (6 steps each), AdaGML, the exact-fp32 path, the secondary 512 x 1024 matcher "
                          "shape and the one-query latency, and report them as 'alt' (auto: on for the default 1-GPU configuration)")
     ap.add_argument("--attn-chunk-keys", type=int, default=None,
                     help="keys per chunk of the split-fp16 attention (pram_attention_x3_set_chunk_keys; default: the library's 4096 = one chunk for every shipped shape, "
@@ -762,6 +809,11 @@ def main():
     steps = args.steps if args.steps is not None else (100 if args.latency else 20)
     warmup = args.warmup if args.warmup is not None else (30 if args.latency else 6)
     inflight = args.inflight if args.inflight is not None else (1 if args.latency else 3)
+    full = args.full
+    if steps < 1:
+        raise SystemExit(f"bench.py: --steps {steps}: at least one timed step")
+    if args.alt == "on" and not full:
+        raise SystemExit("bench.py: --alt on measures beside the headline: it needs --full")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         sys.exit(spawn_ranks(args.gpus))
@@ -830,11 +882,12 @@ def main():
     job = Job(dev, rank, world, q0, B, args.matcher, args.kpts, args.n_class, args.stages, inflight, use_graph,
               ref_kpts=args.ref_kpts, match_kpts=args.match_kpts, shard_sizes=shard_sizes)
     pipe, sds, images, ref, gt, counts, do_match = job.pipe, job.sds, job.images, job.ref, job.gt, job.counts, job.do_match
+    job.keep_out = rank == 0 and args.dump_outputs is not None
 
     for _ in range(warmup):
         job.step()
     sync_all()
-    sampler = PowerSampler(dev.index if dev.index is not None else 0) if rank == 0 else None
+    sampler = PowerSampler(dev.index if dev.index is not None else 0) if rank == 0 and full else None
     if sampler is not None:
         sampler.start()
     if world > 1 and job.lanes is not None:
@@ -861,6 +914,11 @@ def main():
         rank_gather_ms = [float(x[2].item()) * 1e3 for x in allt]
         dt = max(float(x[0].item()) for x in allt)
     assert rec.shape[0] == total_per_step, (rec.shape, total_per_step)
+    if job.keep_out:
+        # what the last timed step computed: the (gathered) result record and this rank's pipeline outputs, before anything
+        # else runs on the device
+        dumped = dump_outputs(args.dump_outputs, {"record": rec, **(job.last_out or {})})
+        print(f"[bench] outputs of the last timed step -> {args.dump_outputs}: {json.dumps(dumped)}", file=sys.stderr, flush=True)
     local_rec = rec[q0 - spans[0][0]:q1 - spans[0][0]] if world > 1 else rec
     # the gather keeps query order: on EVERY rank, rows [q0, q1) of the gathered record are the records this rank computed in the
     # last step (uneven shards included); one flag per rank, gathered
@@ -886,23 +944,25 @@ def main():
     x3_ran = ops.x3_launched(dev)
     range_hit = ops.x3_range_exceeded(dev) if x3_ran else False
 
-    # ---- roofline of the dominant kernel (attention), one extra instrumented EAGER step, HIP events on the launch stream
-    lanes_saved, graphs_saved = job.lanes, job.graphs
-    job.lanes = job.graphs = None                      # the instrumented step runs alone on the current stream
-    torch.cuda.synchronize()
-    ops.attention_probe = []
-    job.step()
-    torch.cuda.synchronize()
-    probe, ops.attention_probe = ops.attention_probe, None
-    job.lanes, job.graphs = lanes_saved, graphs_saved
-    roofline = attention_roofline(probe, precision, dev, dt / steps * 1e3)
     default_shape = (args.kpts, B, args.matcher, args.stages, args.n_class, args.ref_kpts, args.match_kpts) == (2048, 16, "gml", "erm", 113, 0, 0)
-    roofline["traffic"] = pmc_traffic(precision) if default_shape else None
-    roofline["traffic_source"] = ("profiles/pmc_attention.json (rocprofv3 --pmc passes of this kernel source: 2 x FETCH_SIZE + WRITE_SIZE)"
-                                  if roofline["traffic"] is not None else None)
+    roofline = None
+    if full:
+        # ---- roofline of the dominant kernel (attention), one extra instrumented EAGER step, HIP events on the launch stream
+        lanes_saved, graphs_saved = job.lanes, job.graphs
+        job.lanes = job.graphs = None                      # the instrumented step runs alone on the current stream
+        torch.cuda.synchronize()
+        ops.attention_probe = []
+        job.step()
+        torch.cuda.synchronize()
+        probe, ops.attention_probe = ops.attention_probe, None
+        job.lanes, job.graphs = lanes_saved, graphs_saved
+        roofline = attention_roofline(probe, precision, dev, dt / steps * 1e3)
+        roofline["traffic"] = pmc_traffic(precision) if default_shape else None
+        roofline["traffic_source"] = ("profiles/pmc_attention.json (rocprofv3 --pmc passes of this kernel source: 2 x FETCH_SIZE + WRITE_SIZE)"
+                                      if roofline["traffic"] is not None else None)
 
     parity = None
-    if rank == 0 and not args.no_parity and "e" in args.stages and "r" in args.stages:
+    if full and rank == 0 and not args.no_parity and "e" in args.stages and "r" in args.stages:
         # the gate reads the TIMED batch's own outputs: one more run of all B queries through the path that was timed; its record
         # must equal the last timed step's record bit for bit (the kernels are deterministic), which ties the two together
         with torch.no_grad():
@@ -920,7 +980,7 @@ def main():
 
     # ---- other configurations of the same path, measured in this run (rank 0, N = 1): what the driver otherwise never sees
     alt = None
-    want_alt = args.alt == "on" or (args.alt == "auto" and default_shape and world == 1 and precision == "x3" and not args.latency)
+    want_alt = full and (args.alt == "on" or (args.alt == "auto" and default_shape and world == 1 and precision == "x3" and not args.latency))
     if rank == 0 and world == 1 and want_alt:
         alt = {}
         alt_parity_failed = []
@@ -1039,7 +1099,6 @@ def main():
                        "frame": f"{W_IMG}x{H}", "keypoints": args.kpts,
                        "keypoints_found": counts[:4], "parallelism": f"query-sharded x{world}, one all-gather of result records",
                        "matches_last_step": n_matches, "matches_correct_last_step": n_correct},
-            "roofline": roofline,
             "range_guard": {"x3_range_exceeded": bool(range_hit), "split_fp16_kernels_in_step": bool(x3_ran),
                             "policy": "deferred: the status word is read once after the timed region (steps in flight); set = the line is void"},
         }
@@ -1050,6 +1109,8 @@ def main():
             line["per_rank_host_issue_ms_per_step"] = [round(x, 3) for x in rank_issue_ms]
             line["per_rank_gather_ms"] = [round(x, 4) for x in rank_gather_ms]
             line["config"]["host_core_of_rank0"] = core
+        if roofline is not None:
+            line["roofline"] = roofline
         if power is not None:
             line["power"] = power
         if parity is not None:
@@ -1057,7 +1118,7 @@ def main():
         if alt is not None:
             line["alt"] = alt
             line["alt_parity_failed"] = alt_parity_failed
-        if world == 1 and args.cpu_queries > 0:
+        if full and world == 1 and args.cpu_queries > 0:
             ref_cpu_sets = None if ref is None else {k: v.cpu() for k, v in ref.items()}
             line["cpu_baseline"] = cpu_baseline(sds, args.matcher, args.cpu_queries, args.kpts, ref_cpu_sets)
         print(json.dumps(line), flush=True)

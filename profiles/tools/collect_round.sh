@@ -8,7 +8,7 @@ ROOT=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/../.." && pwd)}
 OUT=$ROOT/gpurun_out/$TAG
 mkdir -p "$OUT"
 cd "$ROOT"
-b() { name=$1; shift; python bench.py "$@" > "$OUT/bench_$name.json" 2> "$OUT/bench_$name.err"; echo "bench_$name rc=$? $(cut -c1-160 "$OUT/bench_$name.json")"; }
+b() { name=$1; shift; python bench.py --full "$@" > "$OUT/bench_$name.json" 2> "$OUT/bench_$name.err"; echo "bench_$name rc=$? $(cut -c1-160 "$OUT/bench_$name.json")"; }
 # PMC passes first (one counter set per run, never combined with other tracing) and their summary on THIS box: bench.py prints
 # roofline.traffic only while profiles/pmc_attention.json carries the hash of the attention source it runs
 bash profiles/tools/pmc_collect.sh "$OUT/pmc" --alt off > "$OUT/pmc.log" 2>&1; tail -4 "$OUT/pmc.log"

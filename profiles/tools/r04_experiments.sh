@@ -4,7 +4,7 @@
 #   bash profiles/tools/r04_experiments.sh [batch|latency|c5act|attnsweep|resblock]
 set -u
 what=${1:-all}
-bench() { python bench.py --cpu-queries 0 --no-parity --alt off "$@" 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read()); print(d['ms_per_step'], d['value'], d.get('power',{}).get('socket_w_mean'), d.get('power',{}).get('sclk_mhz_mean'))"; }
+bench() { python bench.py --full --cpu-queries 0 --no-parity --alt off "$@" 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read()); print(d['ms_per_step'], d['value'], d.get('power',{}).get('socket_w_mean'), d.get('power',{}).get('sclk_mhz_mean'))"; }
 if [ $what = batch ] || [ $what = all ]; then      # profiles/r04_batch_sweep.txt: batch size x steps in flight
   echo "b16 inflight3: $(bench)"; echo "b8 inflight3: $(bench --batch-per-gpu 8 --steps 40)"; echo "b8 inflight6: $(bench --batch-per-gpu 8 --inflight 6 --steps 40)"
   echo "b32 inflight2: $(bench --batch-per-gpu 32 --inflight 2 --steps 10)"; echo "b16 inflight2: $(bench --inflight 2)"

@@ -10,5 +10,5 @@ echo "## kernel timing (profiles/tools/x3_attn_probe.py)"
 bash profiles/tools/ab.sh $kreps "python profiles/tools/x3_attn_probe.py | awk '{printf \"%s %s us | \", \$4 \$5, \$6} END {print \"\"}'" $tags
 if [ $breps -gt 0 ]; then
   echo "## bench (16 queries per step, 20 steps, no parity gate / cpu baseline)"
-  bash profiles/tools/ab.sh $breps "python bench.py --cpu-queries 0 --no-parity --alt off | python -c \"import sys,json; d=json.loads(sys.stdin.read()); print(d['ms_per_step'], d['value'], d['roofline']['achieved'], d.get('power',{}).get('socket_w_mean'), d.get('power',{}).get('sclk_mhz_mean'))\"" ${4:-$tags}
+  bash profiles/tools/ab.sh $breps "python bench.py --full --cpu-queries 0 --no-parity --alt off | python -c \"import sys,json; d=json.loads(sys.stdin.read()); print(d['ms_per_step'], d['value'], d['roofline']['achieved'], d.get('power',{}).get('socket_w_mean'), d.get('power',{}).get('sclk_mhz_mean'))\"" ${4:-$tags}
 fi

@@ -29,6 +29,42 @@ def test_bench_cli_contract_and_cores():
         assert key in src, key
 
 
+def test_dump_outputs_budget_dtypes_and_fixed_sample(tmp_path):
+    """--dump-outputs: every tensor as <name>.npy in float32 (float64 kept); under the byte budget the small arrays are whole and
+    the large one is a seeded sample of its elements — the same positions in every run."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, str(ROOT))
+    import bench
+    g = torch.Generator().manual_seed(3)
+    arrays = {"counts": torch.tensor([5, 7], dtype=torch.int32), "matches0": torch.randint(-1, 50, (2, 64), generator=g),
+              "mask": torch.rand(2, 64, generator=g) > 0.5, "exact": torch.rand(4, dtype=torch.float64, generator=g),
+              "big": torch.rand(2, 64, 1000, generator=g)}
+    budget = 200_000
+    rep = [bench.dump_outputs(tmp_path / d, arrays, budget=budget) for d in ("a", "b")]
+    assert rep[0] == rep[1]
+    for d in ("a", "b"):
+        files = {p.stem: np.load(p) for p in (tmp_path / d).glob("*.npy")}
+        assert set(files) == set(arrays)
+        assert sum(p.stat().st_size for p in (tmp_path / d).glob("*.npy")) <= budget
+        assert files["exact"].dtype == np.float64 and all(files[k].dtype == np.float32 for k in ("counts", "matches0", "mask", "big"))
+        for k in ("counts", "matches0", "mask", "exact"):
+            assert np.array_equal(files[k], arrays[k].double().numpy()) and rep[0][k]["written"] == arrays[k].numel()
+        assert 0 < rep[0]["big"]["written"] == files["big"].size < arrays["big"].numel() and rep[0]["big"]["shape"] == [2, 64, 1000]
+        assert np.isin(files["big"], arrays["big"].numpy()).all()
+    assert np.array_equal(np.load(tmp_path / "a" / "big.npy"), np.load(tmp_path / "b" / "big.npy"))
+
+
+def test_bench_plain_run_gates_the_extras_behind_full():
+    """The parity gate, roofline, power, alt and CPU baseline run only with --full; --alt on without it is refused."""
+    src = (ROOT / "bench.py").read_text()
+    for flag in ("--full", "--dump-outputs"):
+        assert flag in src
+    r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--alt", "on", "--steps", "1", "--warmup", "0"],
+                       capture_output=True, text=True, timeout=300)
+    assert r.returncode != 0 and "--full" in r.stderr
+
+
 def test_committed_bench_line_is_well_formed():
     line = json.loads((ROOT / "profiles" / "r01_bench_final.json").read_text())
     assert line["unit"] == "queries/s" and line["n_gpus"] == 1 and line["dtype"] == "f32" and line["vs_baseline"] is None

@@ -20,8 +20,8 @@ def _last_json(stdout: str) -> dict:
 
 
 def test_bench_one_gpu_line(hip_lib):
-    r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--steps", "3", "--warmup", "1", "--batch-per-gpu", "2", "--cpu-queries", "0"],
-                       capture_output=True, text=True, timeout=900, cwd=ROOT)
+    r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--steps", "3", "--warmup", "1", "--batch-per-gpu", "2", "--cpu-queries", "0",
+                        "--full"], capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     d = _last_json(r.stdout)
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
@@ -37,13 +37,34 @@ def test_bench_one_gpu_line(hip_lib):
     assert rf["bound"] == "mfma" and abs(rf["frac"] - rf["achieved"] / rf["peak"]) < 1e-3 and rf["launches_per_step"] == 33
 
 
+def test_bench_plain_run_is_lean_and_dumps_its_last_step(hip_lib, tmp_path):
+    """Without --full the line holds the headline only (no parity gate, roofline, alt or CPU baseline ran); --steps sets the timed
+    steps; --dump-outputs writes the last timed step's record and pipeline outputs as float32 .npy files."""
+    import numpy as np
+    r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--batch-per-gpu", "2",
+                        "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=900, cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-2000:]
+    d = _last_json(r.stdout)
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in d, k
+    assert d["steps"] == 3 and d["warmup"] == 1 and abs(d["value"] - 2 * 1e3 / d["ms_per_step"]) < 0.01 * d["value"]
+    assert not {"parity", "roofline", "alt", "cpu_baseline", "power"} & set(d), sorted(d)
+    files = {p.stem: np.load(p) for p in tmp_path.glob("*.npy")}
+    assert {"record", "keypoints", "scores", "counts", "descriptors", "prediction", "matches0", "matching_scores0"} <= set(files)
+    assert all(a.dtype in (np.float32, np.float64) for a in files.values())
+    assert sum(p.stat().st_size for p in tmp_path.glob("*.npy")) <= 64 * 10 ** 6
+    rec, n = files["record"], files["counts"].astype(int)
+    assert rec.shape == (2, 2048, 6) and (n > 0).all()
+    assert np.array_equal(rec[:, :, 4], files["matches0"]) and int((files["matches0"] >= 0).sum()) == d["config"]["matches_last_step"]
+
+
 def test_bench_alt_matcher_pattern_and_upload_in_step(hip_lib):
     """Two of the `alt` configurations on a small batch: the matcher's real call pattern (seg_k ragged pairs per query in one grouped
     call: every reported match is the planted twin) and the frame upload inside the step (uint8 frames from pinned host memory +
     pram_stage_frames_u8)."""
     env = dict(os.environ, PRAM_BENCH_ALTS="matcher_segk5,h2d_in_step")
     r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--steps", "2", "--warmup", "1", "--batch-per-gpu", "2", "--cpu-queries", "0",
-                        "--no-parity", "--alt", "on"], capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
+                        "--no-parity", "--alt", "on", "--full"], capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     assert r.returncode == 0, r.stderr[-2000:]
     alt = _last_json(r.stdout)["alt"]
     assert set(alt) == {"matcher_segk5", "h2d_in_step"} and not any("error" in v for v in alt.values()), alt
@@ -59,7 +80,7 @@ def test_bench_alt_sustained_and_activation_scale(hip_lib):
     checkpoint — with the fp32 parity gate green on it)."""
     env = dict(os.environ, PRAM_BENCH_ALTS="sustained,act_scale_1")
     r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--steps", "4", "--warmup", "2", "--batch-per-gpu", "2", "--cpu-queries", "0",
-                        "--alt", "on"], capture_output=True, text=True, timeout=1500, cwd=ROOT, env=env)
+                        "--alt", "on", "--full"], capture_output=True, text=True, timeout=1500, cwd=ROOT, env=env)
     assert r.returncode == 0, r.stderr[-2000:]
     d = _last_json(r.stdout)
     alt = d["alt"]
@@ -75,7 +96,7 @@ def test_bench_alt_sustained_and_activation_scale(hip_lib):
 def test_bench_latency_mode_line(hip_lib):
     """`--latency`: one query per step, nothing in flight, the step replayed from captured graphs on two streams, 512-key attention
     chunks (split launches); the parity gate runs on the same arithmetic."""
-    r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--latency", "--steps", "8", "--warmup", "3", "--cpu-queries", "0"],
+    r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--latency", "--steps", "8", "--warmup", "3", "--cpu-queries", "0", "--full"],
                        capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     d = _last_json(r.stdout)
