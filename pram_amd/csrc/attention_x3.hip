@@ -70,7 +70,6 @@ struct ArgsX {
     int chunk_tiles;                 // 64-key tiles per key chunk (g_chunk_tiles: even, the same for every launch of the process)
     float* part_o;                   // [nsplit][batch * m_max][heads * D]   normalised chunk outputs
     float* part_l;                   // [nsplit][batch][heads][m_max]        their log2-sum-exp
-    _Float16* out16; int ldo16;      // single-product mode: the context as fp16 [batch * m_max][ldo16] instead of `out` (the next GEMM's operand)
 };
 
 // Key chunks (as attention.hip).  From 1024 keys on, the keys of a sequence are processed in chunks of chunk_tiles tiles: every
@@ -187,11 +186,7 @@ __global__ __launch_bounds__(NWV * 64, (NWV == NW && MODE != 1) ? 2 : 1) void at
     const bool q_ok = qrow < qlen;
     if (klen <= 0) {   // empty key set: context defined as 0 (see attention.hip); the split mode's first chunk reports it
         if (MODE == 2 && blockIdx.y != 0) return;
-        if (q_ok && HI && p.out16) {
-            _Float16* o16 = p.out16 + ((size_t)b * p.m_max + qrow) * p.ldo16 + head * D;
-#pragma unroll
-            for (int c = 0; c < 32; ++c) o16[c * 2 + h] = (_Float16)0.f;
-        } else if (q_ok) {
+        if (q_ok) {
             float* op = p.out + ((size_t)b * p.m_max + qrow) * p.ldo + head * D;
 #pragma unroll
             for (int c = 0; c < 8; ++c) *reinterpret_cast<float4*>(op + c * 8 + h * 4) = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -961,28 +956,14 @@ __global__ __launch_bounds__(NWV * 64, (NWV == NW && MODE != 1) ? 2 : 1) void at
     if (q_ok) {
         const size_t row = (size_t)b * p.m_max + qrow;
         const int clast = (nkt - 1) / CT;          // split mode: the workgroup's last chunk is parked like the others
-        if (HI && MODE == 0 && p.out16) {          // fp16 context (what the consuming GEMM would round it to while staging)
-            typedef _Float16 half4v __attribute__((ext_vector_type(4)));
-            _Float16* o16 = p.out16 + row * p.ldo16 + head * D;
+        float* op = MODE == 2 ? p.part_o + ((size_t)clast * p.batch * p.m_max + row) * (p.heads * D) + head * D
+                              : p.out + row * p.ldo + head * D;
 #pragma unroll
-            for (int dn = 0; dn < 2; ++dn)
+        for (int dn = 0; dn < 2; ++dn)
 #pragma unroll
-                for (int g = 0; g < 4; ++g) {
-                    half4v hv;
-                    hv[0] = (_Float16)oacc[dn][4 * g + 0]; hv[1] = (_Float16)oacc[dn][4 * g + 1];
-                    hv[2] = (_Float16)oacc[dn][4 * g + 2]; hv[3] = (_Float16)oacc[dn][4 * g + 3];
-                    *reinterpret_cast<half4v*>(o16 + dn * 32 + 8 * g + 4 * h) = hv;
-                }
-        } else {
-            float* op = MODE == 2 ? p.part_o + ((size_t)clast * p.batch * p.m_max + row) * (p.heads * D) + head * D
-                                  : p.out + row * p.ldo + head * D;
-#pragma unroll
-            for (int dn = 0; dn < 2; ++dn)
-#pragma unroll
-                for (int g = 0; g < 4; ++g)
-                    *reinterpret_cast<float4*>(op + dn * 32 + 8 * g + 4 * h) =
-                        make_float4(oacc[dn][4 * g + 0], oacc[dn][4 * g + 1], oacc[dn][4 * g + 2], oacc[dn][4 * g + 3]);
-        }
+            for (int g = 0; g < 4; ++g)
+                *reinterpret_cast<float4*>(op + dn * 32 + 8 * g + 4 * h) =
+                    make_float4(oacc[dn][4 * g + 0], oacc[dn][4 * g + 1], oacc[dn][4 * g + 2], oacc[dn][4 * g + 3]);
         if (h == 0) {
             const size_t li = ((size_t)b * p.heads + head) * p.m_max + qrow;
             if (MODE == 2) p.part_l[(size_t)((nkt - 1) / CT) * p.batch * p.heads * p.m_max + li] = l_tot2;
@@ -1237,26 +1218,18 @@ extern "C" int pram_attention_x3_vt(const void* v_hi, const void* v_lo, int ldv,
 
 // fused or split launch (see "Key chunks" above).  The mode never changes the result.  Both park chunk results in the workspace
 // ([chunks][rows][heads * 64] + [chunks][batch][heads][rows] floats) when a sequence has more than one chunk.
-static int g_chunk_tiles = 0;
-static int chunk_tiles() {
-    if (g_chunk_tiles == 0) {
-        const char* e = getenv("PRAM_ATTN_CHUNK_KEYS");
-        int t = e ? atoi(e) / BKV : DEFAULT_CHUNK_TILES;
-        g_chunk_tiles = (t >= 2 && t % 2 == 0) ? t : DEFAULT_CHUNK_TILES;
-    }
-    return g_chunk_tiles;
-}
+static int g_chunk_tiles = DEFAULT_CHUNK_TILES;
 static size_t x3_ws_bytes(int batch, int heads, int m_max, int n_max) {
-    const int nchunks = cdiv(n_max, chunk_tiles() * BKV);
+    const int nchunks = cdiv(n_max, g_chunk_tiles * BKV);
     if (n_max < 1024 || nchunks < 2) return 0;
     return (size_t)nchunks * batch * m_max * (heads * D + heads) * sizeof(float);
 }
 
-/* Keys per chunk of pram_attention_x3_f32 (a multiple of 128; default 4096, or PRAM_ATTN_CHUNK_KEYS): process-wide, to be set
+/* Keys per chunk of pram_attention_x3_f32 (a multiple of 128; default 4096): process-wide, to be set
    before the first launch — it fixes where every launch folds its partial soft-maxes.  0 keeps the current value; returns it. */
 extern "C" int pram_attention_x3_set_chunk_keys(int keys) {
     if (keys >= 128 && keys % 128 == 0) g_chunk_tiles = keys / BKV;
-    return chunk_tiles() * BKV;
+    return g_chunk_tiles * BKV;
 }
 
 static int g_split_target = SPLIT_TARGET;
@@ -1265,7 +1238,7 @@ static int g_split_target = SPLIT_TARGET;
 static int x3_split_groups(int batch, int heads, int m_max, int n_max) {
     if (n_max < 1024) return 1;
     const long units = (long)batch * heads * cdiv(m_max, BQ);
-    const int nchunks = cdiv(n_max, chunk_tiles() * BKV);
+    const int nchunks = cdiv(n_max, g_chunk_tiles * BKV);
     const long g = units > 0 ? g_split_target / units : 1;
     return (int)(g < 2 ? 1 : (g > nchunks ? nchunks : g));
 }
@@ -1289,22 +1262,15 @@ extern "C" int pram_attention_x3_is_split(int batch, int heads, int m_max, int n
 /* MFMA instructions (v_mfma_f32_32x32x16_f16) the kernel pram_attention_x3_f32 launches for n_max keys issues per 64-key tile and
    32-query wave; a single-product fp16 attention needs 16 (8 for K Q^T, 8 for P V).  40 = three products for the scores, two
    for P V (probabilities as one fp16); 48 = three and three (below 1024 keys).  bench.py prices its roofline with this. */
-static int g_p_split = -1;
-static bool p_split_always() {
-    if (g_p_split < 0) {
-        const char* e = getenv("PRAM_ATTN_P");      // "split" / "fp16": see pram_attention_x3_set_p_split
-        g_p_split = (e && e[0] == 'f') ? 0 : 1;
-    }
-    return g_p_split != 0;
-}
+static bool g_p_split = true;
 
 /* How the probabilities enter P V from 1024 keys on (below, always split): 1 = as two fp16 parts like every other operand (three
    MFMAs per product, 48 per tile: the default), 0 = as ONE fp16 (two MFMAs, 40 per tile: ~15 % less attention time, but the
    2^-12 rounding of every probability shows: SegNetViT logits 7e-4..1.3e-3 from the fp32 oracle instead of 4e-5 (not inside the 1e-3 parity bar everywhere: an opt-in, not parity-gated) on the synthetic token
    sets of tests/, 0.15 % of the landmark arg-maxes flipped).  Process-wide; negative = query.  Returns the value in force. */
 extern "C" int pram_attention_x3_set_p_split(int split) {
-    if (split >= 0) g_p_split = split ? 1 : 0;
-    return p_split_always() ? 1 : 0;
+    if (split >= 0) g_p_split = split != 0;
+    return g_p_split ? 1 : 0;
 }
 
 #ifdef PRAM_PROFILING
@@ -1324,7 +1290,7 @@ extern "C" int pram_debug_attention_phases(unsigned long long* out32, int reset)
 }
 #endif
 
-extern "C" int pram_attention_x3_mfma_per_tile(int n_max) { return (n_max < 1024 || p_split_always()) ? 48 : 40; }
+extern "C" int pram_attention_x3_mfma_per_tile(int n_max) { return (n_max < 1024 || g_p_split) ? 48 : 40; }
 
 /* Split-fp16 flash attention.  q / k: row-major planes written by pram_linear_x3_f32 (value * 16 = hi + lo; ld* in halves,
    16-byte aligned rows and head offsets); vt: the V^T planes of pram_attention_x3_vt for the KEY side ([batch][heads][64][tv],
@@ -1344,7 +1310,7 @@ extern "C" int pram_attention_x3_f32(const void* q_hi, const void* q_lo, int ldq
     PRAM_REQUIRE((long long)n_max * ldk * 2 < (1ll << 32) && 64ll * (cdiv(n_max, 64) * 64) * 2 < (1ll << 32), "pram_attention_x3_f32: a sequence's K rows / V^T planes must span < 4 GiB");
     ArgsX p{(const _Float16*)q_hi, (const _Float16*)q_lo, (const _Float16*)k_hi, (const _Float16*)k_lo, (const _Float16*)vt_hi,
             (const _Float16*)vt_lo, out, lse2, q_lens, k_lens, ldq, ldk, cdiv(n_max, 64) * 64, ldo, batch, heads, m_max, n_max,
-            scale * LOG2E / (pram_act_scale() * pram_act_scale()), cdiv(m_max, BQ), kv_shift, pram_act_scale(), 1, 0, chunk_tiles(), nullptr, nullptr};
+            scale * LOG2E / (pram_act_scale() * pram_act_scale()), cdiv(m_max, BQ), kv_shift, pram_act_scale(), 1, 0, g_chunk_tiles, nullptr, nullptr};
     const dim3 grid(batch * heads * p.q_tiles), blk(256);
     hipStream_t st = (hipStream_t)stream;
     {
@@ -1361,7 +1327,7 @@ extern "C" int pram_attention_x3_f32(const void* q_hi, const void* q_lo, int ldq
             }
             return pram_launch_status("pram_attention_x3_f32");
         }
-        const bool psplit = p_split_always();      // probabilities as two fp16 parts (three MFMAs per P V product) also from 1024 keys on
+        const bool psplit = g_p_split;      // probabilities as two fp16 parts (three MFMAs per P V product) also from 1024 keys on
         // the key-chunk kernels (128-row workgroups) run the phases form when the grid puts two workgroups on a CU — two waves on
         // a SIMD — and a workgroup walks at least 2048 keys; the interleaved form otherwise (one frame split four ways: one wave
         // per SIMD, nothing to overlap with; 512-key groups: the longer prologue of the phases form is not won back)
@@ -1381,7 +1347,7 @@ extern "C" int pram_attention_x3_f32(const void* q_hi, const void* q_lo, int ldq
         const size_t need = x3_ws_bytes(batch, heads, m_max, n_max);
         static const char* force = prof_env("PRAM_ATTN_MODE");      // profiling only: 0 = the unchunked kernel (different last bits), 1 = fused, 2 = split
         const int fm = force ? atoi(force) : -1;
-        const int nchunks = cdiv(n_max, chunk_tiles() * BKV);
+        const int nchunks = cdiv(n_max, g_chunk_tiles * BKV);
         if (fm == 0 || (nchunks < 2 && fm != 1)) {      // one chunk per sequence: the walk is the unchunked kernel's (a fold from (0, -inf) is exact)
             // a grid that fills the chip with 256-row workgroups runs eight waves per workgroup (NWV): every K / V tile is staged once
             // per 256 query rows.  PRAM_ATTN_WAVES=4 keeps the 128-row workgroups (profiling); the choice never changes a bit.
@@ -1447,23 +1413,4 @@ extern "C" int pram_attention_h16t_f32(const void* q16, int ldq, const void* k16
             ldq, ldk, cdiv(n_max, 64) * 64, ldo, batch, heads, m_max, n_max, scale * LOG2E, cdiv(m_max, BQ), kv_shift, 1.0f, 1, 0, 0, nullptr, nullptr};
     launch_h16t(p, (hipStream_t)stream);
     return pram_launch_status("pram_attention_h16t_f32");
-}
-
-/* pram_attention_h16t_f32 with the context written as fp16 [batch * m_max][ldo16] (ldo16 % 4 == 0): the operand format of the
-   fp16 path's next GEMM (pram_linear_f16_ssq_h16) — the same values that GEMM would round the fp32 context to while staging it. */
-extern "C" int pram_attention_h16t_h16(const void* q16, int ldq, const void* k16, int ldk, const void* vt16, void* out16, int ldo16,
-                                       float* lse2, const int* q_lens, const int* k_lens, int batch, int heads, int m_max,
-                                       int n_max, float scale, int kv_shift, void* stream) {
-    PRAM_REQUIRE(q16 && k16 && vt16 && out16, "pram_attention_h16t_h16: null pointer");
-    PRAM_REQUIRE(ldq % 8 == 0 && ldk % 8 == 0 && ldo16 % 4 == 0, "pram_attention_h16t_h16: ld of the fp16 operands must be a multiple of 8 (output: 4)");
-    PRAM_REQUIRE(batch >= 0 && heads > 0 && m_max >= 0 && n_max >= 0 && kv_shift >= 0, "pram_attention_h16t_h16: bad sizes");
-    if (batch == 0 || m_max == 0) return PRAM_OK;
-    PRAM_REQUIRE(n_max > 0, "pram_attention_h16t_h16: empty key set");
-    // K / V tiles are addressed by 32-bit byte offsets from a per-sequence base
-    PRAM_REQUIRE((long long)n_max * ldk * 2 < (1ll << 32) && 64ll * (cdiv(n_max, 64) * 64) * 2 < (1ll << 32), "pram_attention_h16t_h16: a sequence's K rows / V^T planes must span < 4 GiB");
-    ArgsX p{(const _Float16*)q16, nullptr, (const _Float16*)k16, nullptr, (const _Float16*)vt16, nullptr, nullptr, lse2, q_lens, k_lens,
-            ldq, ldk, cdiv(n_max, 64) * 64, 0, batch, heads, m_max, n_max, scale * LOG2E, cdiv(m_max, BQ), kv_shift, 1.0f, 1, 0, 0, nullptr, nullptr,
-            (_Float16*)out16, ldo16};
-    launch_h16t(p, (hipStream_t)stream);
-    return pram_launch_status("pram_attention_h16t_h16");
 }

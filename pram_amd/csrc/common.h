@@ -29,7 +29,8 @@ static inline int pram_launch_status(const char* what) {
 static inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 
 // Behaviour-changing environment switches (tile / kernel-form overrides) exist in profiling builds only (-DPRAM_PROFILING, e.g.
-// profiles/tools/build_variants.py TAG:file.hip:-DPRAM_PROFILING): the production library reads none of them.
+// profiles/tools/build_variants.py TAG:file.hip:-DPRAM_PROFILING).  The production library reads one: PRAM_CONV_HALO
+// (conv.hip), "0" forces the per-tap 3x3 kernel — tests/test_gpu_guard_chunks_mlp.py compares it against the halo kernel.
 #include <stdlib.h>
 static inline const char* prof_env(const char* name) {
 #ifdef PRAM_PROFILING

@@ -119,7 +119,7 @@ class SegNetViT(blk.PackedCache, nn.Module):
         kw = dict(lens=lens, t_pad=N)      # ragged like the layers: rows beyond a frame's keypoint count are never read or written
         # the logits of rows beyond a frame's keypoint count read zero (they are the tensor the caller sees), not leftovers
         o0 = None if lens is None else ops._filled((B * N, P["seg3_w"].shape[0]), x.device)
-        if ops.gemm_prec() == "x3" and blk.FUSED_MLP and P["seg3_w"].shape[0] > 64:
+        if ops.gemm_prec() == "x3" and P["seg3_w"].shape[0] > 64:
             out = ops.mlp_tail(x, P["seg0_w"], P["seg0_b"], P["seg1_w"], P["seg1_b"], P["seg3_w"], P["seg3_b"], out=o0, **kw)
         else:
             h = ops.linear(x, P["seg0_w"], P["seg0_b"], **kw)

@@ -15,10 +15,6 @@ import torch.nn as nn
 from .. import ops
 from . import _blocks as blk
 
-import os as _os
-# conv1a -> conv1b as one kernel on the split-fp16 path (pram_sfd2_conv1_x3_f32); 0: two kernels (conv1a on the exact-fp32 MFMA kernel)
-FUSED_CONV1 = _os.environ.get("PRAM_FUSED_CONV1", "1") != "0"
-
 RGB_mean = [0.485, 0.456, 0.406]
 RGB_std = [0.229, 0.224, 0.225]
 
@@ -108,7 +104,7 @@ class ResNet4x(blk.PackedCache, nn.Module):
     def _backbone(self, image: torch.Tensor):
         blk.require_cuda(image, "ResNet4x")
         P = self._packed_get(self._build_packed)
-        fused1 = FUSED_CONV1 and ops.gemm_prec() in ("x3", "f16")
+        fused1 = ops.gemm_prec() in ("x3", "f16")
         x = image.float().contiguous() if fused1 and image.shape[-1] != 4 else ops.image_to_nhwc4(image.float())
 
         def cbr(x, n, stride=1):

@@ -116,7 +116,7 @@ def test_c4_sfd2_extraction_k4096_vs_oracle(dev):
 
 def test_c5_fp16_path_nc513_4096(dev):
     """C5: 'fp16 MFMA path', 4096 keypoints, 513 classes.  Own documented tolerance (single fp16 product per MAC), set at 1.5 x the
-    measurement (3.3-4.05e-2 from the fp32 oracle, arg-max agreement 0.9961-0.9971 by the PRAM_F16_ACT setting): logits
+    measurement (3.3-4.05e-2 from the fp32 oracle, arg-max agreement 0.9961-0.9971): logits
     within 6.1e-2, arg-max agreement >= 99.42 % (= bench.F16_BARS, what alt.c5_f16.parity gates on); NOT the fp32 parity configuration."""
     desc, kp = _tokens(4096, idx=2)
     ref = R.segnetvit_forward(H.segnet_sd(513), desc, kp, (1, 3, 480, 640))

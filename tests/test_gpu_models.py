@@ -142,7 +142,7 @@ def test_segnetvit_ragged_batch(dev):
 def test_c5_fp16_attention_path_tolerance(dev):
     """BASELINE config C5 ('fp16 MFMA path', 4096 keypoints): fp16-operand attention inside the otherwise-fp32 models.
     Own, looser, documented tolerance — the bars are 2 x what the path measures (printed below; round 3: attention only 1.55e-2 /
-    0.9983 / 1.0, attention + GEMMs 3.1-3.4e-2 / 0.9973-0.9978 / 1.0, the higher figures with PRAM_F16_ACT=1): indices are NOT
+    0.9983 / 1.0, attention + GEMMs 3.1-3.4e-2 / 0.9973-0.9978 / 1.0): indices are NOT
     promised bit-exact on this path."""
     from pram_amd import ops
     desc, kp = _tokens(1, 4096)
