@@ -273,7 +273,7 @@ __device__ __forceinline__ void linear_epilogue(const LinArgs& p, f32x16 (&acc)[
             // (a masked key must meet a finite value).
             typedef _Float16 half8v __attribute__((ext_vector_type(8)));
             const int r0 = rbase + mi * 32;
-            if (r0 < p.m) {
+            if (r0 < p.m && cbase < p.n) {      // a tile wider than the output (n = 192 under 128-column tiles) has no head beyond n
                 const int sq = r0 / p.vt_t, t0 = r0 - sq * p.vt_t;
                 const int len = p.lens ? p.lens[sq] : p.vt_t;
                 const int head = (cbase - p.vt_col0) >> 6;

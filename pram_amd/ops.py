@@ -490,7 +490,7 @@ class guard_scope:
 # is found by the range guard itself: a tripped guard first lowers the scale of the models that ran (sticky: the cliff is met
 # once) and re-runs on the split kernels; only a value no scale can carry goes to the exact-fp32 kernels.
 ACT_SCALE_DEFAULT = 16.0
-ACT_SCALE_MIN = 2.0 ** -8
+ACT_SCALE_MIN = 2.0 ** -8      # the guard lowers EVERY model that ran: all of them keep their bars down to here (tests/test_gpu_act_scale.py)
 guard_events = {"rescaled": 0, "f32_fallback": 0}      # what the range guard did so far in this process (tests / bench read it)
 
 

@@ -381,11 +381,17 @@ def test_product_path_rejects_cpu(dev):
         _segnet(dev)({"seg_descriptors": desc, "keypoints": kp, "image": torch.empty(1, 3, 480, 640)})
 
 
-@pytest.mark.parametrize("scale", [1.0, 1.0 / 16.0])
+def _guard_ladder():
+    from pram_amd import ops
+    return [ops.ACT_SCALE_DEFAULT * 16.0 ** -i for i in range(8) if ops.ACT_SCALE_DEFAULT * 16.0 ** -i >= ops.ACT_SCALE_MIN]
+
+
+@pytest.mark.parametrize("scale", _guard_ladder())
 def test_models_keep_parity_at_lower_activation_scales(dev, golden, scale):
-    """The three model families with their activation planes at scale 1 / 2^-4 instead of 16 (where the range guard leaves a
-    checkpoint with hot activations): the same golden vectors, the same bars — fp32 outputs 1e-3, match indices exact, SFD2's
-    dense maps 1e-4 — on in-range data whose small values now sit far below the planes' scale."""
+    """The three model families with their activation planes at every scale of the range guard's ladder (16, 1, 2^-4, ... down
+    to ops.ACT_SCALE_MIN: where the guard leaves a checkpoint with hot activations): the same golden vectors, the same bars —
+    fp32 outputs 1e-3, match indices exact, SFD2's dense maps 1e-4 — on in-range data whose small values now sit far below the
+    planes' scale."""
     # SegNetViT
     g = golden("segnetvit_b2_n512_c113")
     desc, kp = _tokens(2, 512)

@@ -163,11 +163,14 @@ def test_guard_lowers_scales_before_it_leaves_the_split_path(monkeypatch):
     assert [r[:2] for r in runs] == [(16.0, 16.0), (1.0, 1.0), (1.0 / 16, 1.0 / 16)] and a.act_scale == 1.0 / 16
     assert ops.guard_events["rescaled"] == ev["rescaled"] + 2 and ops.guard_events["f32_fallback"] == ev["f32_fallback"]
     runs.clear()
+    # nothing fits: 1/16 -> ... -> ACT_SCALE_MIN -> the exact-fp32 kernels
+    below = [1.0 / 16 * 16.0 ** -i for i in range(1, 8) if 1.0 / 16 * 16.0 ** -i >= ops.ACT_SCALE_MIN]
+    assert ops.ACT_SCALE_MIN <= 1.0 / 16 and below and below[-1] == ops.ACT_SCALE_MIN
     with ops.guard_scope("fallback"):
-        trips["left"] = 5                                                   # nothing fits: 1/16 -> 1/256 -> the exact-fp32 kernels
+        trips["left"] = len(below) + 4
         ops.guarded_call(call, "dev")
-    assert [r[0] for r in runs] == [1.0 / 16, 1.0 / 256, 1.0 / 256] and runs[-1][2] == "f32" and runs[0][2] != "f32"
-    assert ops.guard_events["f32_fallback"] == ev["f32_fallback"] + 1 and a.act_scale == 1.0 / 256
+    assert [r[0] for r in runs] == [1.0 / 16] + below + [ops.ACT_SCALE_MIN] and runs[-1][2] == "f32" and runs[0][2] != "f32"
+    assert ops.guard_events["f32_fallback"] == ev["f32_fallback"] + 1 and a.act_scale == ops.ACT_SCALE_MIN
     trips["left"] = 1
     with ops.guard_scope("raise"):
         try:
