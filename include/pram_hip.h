@@ -578,6 +578,63 @@ int pram_stage_frames_u8(const void* frames_hwc3, const float* lut, float* out_n
 /* dst[0 .. count) <- value, 32-bit words, on the stream (torch.zeros / torch.full of the host-side glue without a framework kernel). */
 int pram_fill_u32(void* dst, unsigned int value, size_t count, void* stream);
 
+/* ---------------------------------------------------------------- candidate-landmark matching: vote -> pairs -> 2D-3D matches
+ * The loop of MultiMap3D.run (localization/multimap3d.py:110-145) around SingleMap3D.localize_with_ref_frame
+ * (singlemap3d.py:127-162) for a whole batch of queries, without the host: for each of the seg_k best-voted landmarks of a query
+ * (pram_seg_vote) decide the two keypoint sets (pram_cand_plan), fill the grouped matcher's inputs (pram_cand_gather), and turn
+ * its matches0 into correspondences (pram_cand_correspond).  pairs = batch * seg_k, pair p = query p / seg_k, candidate p % seg_k.
+ *
+ * Reference store (one map; pram_amd/localization/candidates.py::ReferenceStore builds it): the reference frames' rows
+ * concatenated in their original order, frame f = rows frame_off[f] .. frame_off[f + 1]: r_desc [rows][128], r_kpts [rows][2],
+ * r_scores [rows], r_xyz [rows][3] float64, r_point3d_ids [rows] int64, r_segs [rows] int32 (in-map landmark of the row's 3D point);
+ * frame_norm [frames][3] = (cx, cy, scale) of normalize_keypoints for the frame's camera; per in-map landmark l: lm_frame[l] (its
+ * reference frame, -1 = none) and the rows of that frame with r_segs == l, in their original order, as sel_rows[lm_sel_off[l] ..
+ * + lm_sel_len[l]] (RefFrame.get_keypoints_by_sid, refframe.py:34-43); per frame the label histogram hist_label / hist_cnt
+ * [hist_off[f] .. hist_off[f + 1]] (distinct r_segs values of the frame and how many rows carry each).
+ *
+ * Plan table: int32 [PRAM_CAND_PLAN_COLS][pairs] (one contiguous column per field, so lens0 / lens1 go to the matcher as they are) = query, global landmark id (vote id - 1; -1 = no candidate), reference frame
+ * (-1 = none: an empty pair), semantic flag, lens0, lens1, offset of the pair's token list in `tokens` (-1 = all keypoints of the
+ * query in order), first row of the frame, offset of the pair's row list in sel_rows (-1 = the whole frame in order), vote order. */
+#define PRAM_CAND_PLAN_COLS 10
+
+/* sorted_ids [batch][n][c] (pram_row_sort_desc_f32 over a batch of padded queries): the ids of the rows t >= counts[b] become 0
+ * at every rank — such a token names only the background, which is never a candidate, so pram_seg_vote(n) over the padded query
+ * equals the vote over its first counts[b] tokens and its token lists keep the common stride n. */
+int pram_cand_mask_ranks(long long* sorted_ids, const int* counts, int batch, int n, int c, void* stream);
+
+/* One workgroup per (query, candidate).  win_sid / win_count [batch][seg_k], n_win [batch]: pram_seg_vote's outputs (topk = seg_k)
+ * per query; seg_ids [batch][n] = pram_seg_epilogue_f32's (argmax - 1), counts [batch] keypoints per query.  multimap3d.py:114-139:
+ * landmark = vote id - 1, in-map id = landmark - start_sid, its reference frame; semantic = semantic_matching && tokens >=
+ * min_kpts && check_semantic_consistency (singlemap3d.py:513-532: labels present on both sides, min of the two sides' shares
+ * >= overlap_ratio, float64); query side = the voted tokens when semantic, else all keypoints; reference side = the frame's rows of
+ * that landmark when semantic and in-map id > 0 (singlemap3d.py:130), else the whole frame.  Candidates beyond n_win[b] and
+ * landmarks without a reference frame give lens0 = lens1 = 0. */
+int pram_cand_plan(const int* win_sid, const int* win_count, const int* n_win, const int* seg_ids, const int* counts,
+                   int batch, int n, int n_class, int seg_k, const int* lm_frame, const int* lm_sel_off,
+                   const int* lm_sel_len, int n_landmarks, int start_sid, const int* frame_off, const int* hist_off,
+                   const int* hist_label, const int* hist_cnt, int n_frames, int min_kpts, double overlap_ratio,
+                   int semantic_matching, int* plan, void* stream);
+
+/* The grouped matcher's inputs from the plan, one wave per row: desc0 / desc1 [pairs][t_pad][128], scores0 / scores1
+ * [pairs][t_pad], nkpts0 / nkpts1 [pairs][t_pad][2] = keypoints already normalised per pair, (k - (cx, cy)) / scale in fp32 (the
+ * operation order of pram_fourier_encoding_f32): the query side with (q_cx, q_cy, q_scale), the reference side with its frame's
+ * frame_norm.  Rows at and beyond a pair's lens are written as zeros.  Query side from the extractor's batched outputs q_desc
+ * [batch][n][128], q_kpts [batch][n][2], q_scores [batch][n]; tokens = pram_seg_vote's [batch][seg_k][n].  The descriptor buffers
+ * must be 16-byte aligned; t_pad >= every lens0 / lens1 of the plan (rows beyond t_pad are not written). */
+int pram_cand_gather(const int* plan, const int* tokens, const int* sel_rows, const float* q_desc, const float* q_kpts,
+                     const float* q_scores, int n, const float* r_desc, const float* r_kpts, const float* r_scores,
+                     const float* frame_norm, int ref_rows, float q_cx, float q_cy, float q_scale, float* desc0, float* nkpts0,
+                     float* scores0, float* desc1, float* nkpts1, float* scores1, int pairs, int t_pad, void* stream);
+
+/* matches0 [pairs][ldm] (the matcher's, -1 = none; the first min(lens0, t0) entries of a row are read) -> per pair the matched
+ * rows in ascending query position (indices0 >= 0, singlemap3d.py:156-162), out buffers [pairs][cap]...: m_kpt_ids int64 (index
+ * into the query's full keypoint list), m_kpts [..][2] (q_kpts rows, pixels), m_ref_kpts [..][2], m_point3d_ids int64, m_xyz
+ * [..][3] float64 (copied bit for bit), m_sids int32 (r_segs), m_count [pairs].  A match index outside [0, lens1) is dropped. */
+int pram_cand_correspond(const long long* matches0, int ldm, const int* plan, const int* tokens, const int* sel_rows,
+                         const float* q_kpts, int n, const float* r_kpts, const double* r_xyz, const long long* r_point3d_ids,
+                         const int* r_segs, int ref_rows, int pairs, int t0, int cap, long long* m_kpt_ids, float* m_kpts,
+                         float* m_ref_kpts, long long* m_point3d_ids, double* m_xyz, int* m_sids, int* m_count, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

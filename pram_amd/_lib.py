@@ -97,6 +97,10 @@ _SIGS = {
     "pram_fill_u32": (I, [P, C.c_uint, SZ, P]),
     "pram_stage_frames_u8": (I, [P, P, P, I, I, I, P]),
     "pram_score_lookup_f32": (I, [P, LL, I, I, P, P, I, I, P, P]),
+    "pram_cand_mask_ranks": (I, [P, P, I, I, I, P]),
+    "pram_cand_plan": (I, [P, P, P, P, P, I, I, I, I, P, P, P, I, I, P, P, P, P, I, I, C.c_double, I, P, P]),
+    "pram_cand_gather": (I, [P, P, P, P, P, P, I, P, P, P, P, I, F, F, F, P, P, P, P, P, P, I, I, P]),
+    "pram_cand_correspond": (I, [P, I, P, P, P, P, I, P, P, P, P, I, I, I, I, P, P, P, P, P, P, P, P]),
 }
 
 

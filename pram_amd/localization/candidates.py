@@ -1,0 +1,259 @@
+"""Candidate-landmark matching on the device: from the recogniser's vote to 2D-3D matches.
+
+Reference: the loop of MultiMap3D.run (localization/multimap3d.py:110-145) around SingleMap3D.localize_with_ref_frame
+(localization/singlemap3d.py:127-162) with check_semantic_consistency (singlemap3d.py:513-532) and RefFrame.get_keypoints /
+get_keypoints_by_sid (localization/refframe.py:34-75): per query, for each of the seg_k best-voted landmarks, the query keypoints
+voted to it are matched against that landmark's reference frame and matches0 becomes (keypoint, xyz) lists for a pose solver.
+The reference does this in a host loop with a host <-> device round trip per candidate; here the reference frames are resident
+(ReferenceStore), the pairs of ALL queries are planned and gathered by HIP kernels (csrc/candidates.hip), matched in ONE grouped
+produce_matches call, and the correspondences are compacted on the device.  The pose solver itself is not part of this."""
+from __future__ import annotations
+
+from typing import Dict, List, Optional, Sequence
+
+import numpy as np
+import torch
+
+from pram_amd import ops
+from pram_amd.nets.utils import keypoint_norm_constants
+
+_FRAME_KEYS = ("keypoints", "descriptors", "xyzs", "point3D_ids", "keypoint_segs", "width", "height")
+
+
+class ReferenceStore:
+    """The reference frames of ONE map, built once from plain numpy and uploaded once.
+
+    frames: a sequence of dicts with ``keypoints`` [n, 3] (x, y, score), ``descriptors`` [n, 128], ``xyzs`` [n, 3] float64,
+    ``point3D_ids`` [n] int64, ``keypoint_segs`` [n] (in-map landmark id of each keypoint's 3D point), ``width``, ``height`` and
+    optionally ``id`` (default: the position in the sequence).  seg_ref_frame_ids: in-map landmark id -> frame ids (a dict or a
+    sequence; like the reference, entry [0] is the landmark's reference frame).  start_sid: the map's first global landmark id
+    (multimap3d.py:119-123).
+
+    Layout: all rows concatenated in frame order and, inside a frame, in their original order; frame f owns rows
+    frame_off[f] .. frame_off[f + 1] (RefFrame.get_keypoints = that range).  ``sel_rows`` holds, per frame, the frame's rows
+    stably sorted by keypoint_segs, so get_keypoints_by_sid(sid) = one slice of it (rows with keypoint_segs == sid in their
+    original order); the slice of every landmark in its own reference frame is tabulated for the device (lm_sel_off / lm_sel_len).
+    Per frame the label histogram that check_semantic_consistency needs (hist_label / hist_cnt)."""
+
+    def __init__(self, frames: Sequence[dict], seg_ref_frame_ids, start_sid: int = 0, device=None):
+        frames = list(frames)
+        for i, f in enumerate(frames):
+            missing = [k for k in _FRAME_KEYS if k not in f]
+            if missing:
+                raise ValueError(f"reference frame {i}: missing {missing}")
+        self.frame_ids = [f.get("id", i) for i, f in enumerate(frames)]
+        index_of = {fid: i for i, fid in enumerate(self.frame_ids)}
+        if len(index_of) != len(frames):
+            raise ValueError("reference frame ids are not unique")
+        self.start_sid = int(start_sid)
+        lens = [int(np.asarray(f["keypoints"]).shape[0]) for f in frames]
+        self.frame_off = np.zeros(len(frames) + 1, dtype=np.int32)
+        self.frame_off[1:] = np.cumsum(lens)
+        cat = lambda key, dt, shape: (np.concatenate([np.asarray(f[key], dtype=dt).reshape(shape) for f in frames]) if frames
+                                      else np.zeros(shape, dtype=dt).reshape((0,) + tuple(shape[1:])))
+        kp = cat("keypoints", np.float32, (-1, 3))
+        self.keypoints = np.ascontiguousarray(kp[:, :2])
+        self.scores = np.ascontiguousarray(kp[:, 2])
+        self.descriptors = cat("descriptors", np.float32, (-1, 128))
+        self.xyzs = cat("xyzs", np.float64, (-1, 3))
+        self.point3D_ids = cat("point3D_ids", np.int64, (-1,))
+        self.keypoint_segs = cat("keypoint_segs", np.int32, (-1,))
+        n_rows = int(self.frame_off[-1])
+        for name in ("descriptors", "xyzs", "point3D_ids", "keypoint_segs"):
+            if getattr(self, name).shape[0] != n_rows:
+                raise ValueError(f"{name}: row count differs from keypoints")
+        self.frame_size = np.array([[int(f["width"]), int(f["height"])] for f in frames], dtype=np.int32).reshape(-1, 2)
+        # the matcher call sites hand over (1, 3, width, height) and normalize_keypoints unpacks height, width (singlemap3d.py:152)
+        self.frame_norm = np.array([keypoint_norm_constants((1, 3, int(w), int(h))) for w, h in self.frame_size], dtype=np.float32).reshape(-1, 3)
+        sel, hoff, hlab, hcnt, self._slices = [], [0], [], [], []
+        for f in range(len(frames)):
+            a, b = int(self.frame_off[f]), int(self.frame_off[f + 1])
+            segs = self.keypoint_segs[a:b]
+            order = np.argsort(segs, kind="stable")
+            labels, first, cnt = np.unique(segs[order], return_index=True, return_counts=True)
+            self._slices.append({int(l): (a + int(s), int(c)) for l, s, c in zip(labels, first, cnt)})
+            sel.append(order.astype(np.int32) + a)
+            hlab.append(labels.astype(np.int32))
+            hcnt.append(cnt.astype(np.int32))
+            hoff.append(hoff[-1] + len(labels))
+        i32 = lambda parts: np.concatenate(parts).astype(np.int32) if parts else np.zeros(0, dtype=np.int32)
+        self.sel_rows, self.hist_label, self.hist_cnt = i32(sel), i32(hlab), i32(hcnt)
+        self.hist_off = np.array(hoff, dtype=np.int32)
+        items = seg_ref_frame_ids.items() if isinstance(seg_ref_frame_ids, dict) else enumerate(seg_ref_frame_ids)
+        items = [(int(k), v) for k, v in items]
+        n_lm = max([k for k, _ in items], default=-1) + 1
+        self.lm_frame = np.full(n_lm, -1, dtype=np.int32)
+        self.lm_sel_off = np.zeros(n_lm, dtype=np.int32)
+        self.lm_sel_len = np.zeros(n_lm, dtype=np.int32)
+        for k, v in items:
+            if k < 0:
+                raise ValueError(f"landmark id {k} < 0")
+            v = np.atleast_1d(np.asarray(v))
+            if v.size == 0:
+                continue
+            fid = v[0].item()
+            if fid not in index_of:
+                raise ValueError(f"landmark {k}: reference frame {fid!r} is not in the store")
+            f = index_of[fid]
+            self.lm_frame[k] = f
+            self.lm_sel_off[k], self.lm_sel_len[k] = self._slices[f].get(k, (0, 0))
+        self._dev: Dict[str, dict] = {}
+        if device is not None:
+            self.tables(device)
+
+    # ---- host views (what the two RefFrame accessors select; used by the tests and by anyone who wants to look)
+    @property
+    def n_frames(self) -> int:
+        return len(self.frame_ids)
+
+    @property
+    def n_rows(self) -> int:
+        return int(self.frame_off[-1])
+
+    @property
+    def max_frame_rows(self) -> int:
+        return int(np.diff(self.frame_off).max()) if self.n_frames else 0
+
+    def rows(self, frame: int) -> np.ndarray:
+        """RefFrame.get_keypoints: the frame's rows (indices into the concatenated arrays), original order."""
+        return np.arange(self.frame_off[frame], self.frame_off[frame + 1], dtype=np.int64)
+
+    def rows_by_sid(self, frame: int, sid: int) -> np.ndarray:
+        """RefFrame.get_keypoints_by_sid(sid): the frame's rows with keypoint_segs == sid, original order."""
+        off, n = self._slices[frame].get(int(sid), (0, 0))
+        return self.sel_rows[off:off + n].astype(np.int64)
+
+    def tables(self, device) -> dict:
+        """The device-side tables (uploaded on first use, then resident)."""
+        device = torch.device(device)
+        if device.type != "cuda":
+            from pram_amd._lib import PramHipError
+            raise PramHipError("ReferenceStore.tables: expected a CUDA device (pram_amd has no CPU path)")
+        key = str(device)
+        if key not in self._dev:
+            up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(device)
+            pad = lambda a: np.concatenate([a, np.zeros(1, dtype=a.dtype)])      # never an empty allocation behind a pointer
+            t = {name: up(getattr(self, name)) if getattr(self, name).size else up(np.zeros((1,) + getattr(self, name).shape[1:], dtype=getattr(self, name).dtype))
+                 for name in ("descriptors", "keypoints", "scores", "xyzs", "point3D_ids", "keypoint_segs", "frame_norm")}
+            for name in ("sel_rows", "hist_label", "hist_cnt", "lm_frame", "lm_sel_off", "lm_sel_len", "frame_off", "hist_off"):
+                t[name] = up(pad(getattr(self, name)))
+            t.update(n_rows=self.n_rows, n_frames=self.n_frames, n_landmarks=len(self.lm_frame), start_sid=self.start_sid)
+            self._dev[key] = t
+        return self._dev[key]
+
+
+def _query_norm(features: dict):
+    if "image_size" in features:
+        w, h = features["image_size"]
+    elif "image" in features:
+        h, w = features["image"].shape[-2:]
+    else:
+        raise ValueError("features: needs 'image_size' = (width, height) of the query camera, or the 'image' batch")
+    return keypoint_norm_constants((1, 3, int(w), int(h)))      # the reference's (1, 3, width, height), singlemap3d.py:147
+
+
+@torch.no_grad()
+def vote_candidates(features: dict, recognition, seg_k: int) -> dict:
+    """Sort + landmark vote for the whole batch (ops.row_sort_desc, ops.seg_vote: the kernels process_segmentations uses).
+    recognition: the [B, N, C] segmentations of the batch (a tensor, or a dict with 'segmentations' / 'prediction' and optionally
+    'seg_ids' = Frame.seg_ids, e.g. QueryPipeline's 'landmark'), or an already computed vote (a dict with win_sid, win_count, n_win,
+    tokens, seg_ids, n_class).  -> dict(win_sid, win_count [B, seg_k], n_win [B], tokens [B, seg_k, N], seg_ids [B, N], n_class)."""
+    counts = features["counts"]
+    if isinstance(recognition, dict) and "win_sid" in recognition:
+        return recognition
+    seg_ids = None
+    if isinstance(recognition, dict):
+        seg_ids = recognition.get("seg_ids")
+        recognition = recognition["segmentations"] if "segmentations" in recognition else recognition["prediction"]
+    ops._chk(recognition, "recognition")
+    seg = recognition.contiguous()
+    if seg.dim() != 3 or seg.shape[0] != counts.numel():
+        raise ValueError("recognition: expected [B, N, C] with B = len(counts)")
+    vals, idx = ops.row_sort_desc(seg)
+    ops.cand_mask_ranks_(idx, counts)
+    sid, _, cnt, nwin, tokens, _ = ops.seg_vote_batched(vals, idx, seg_k)
+    if seg_ids is None:
+        seg_ids = ops.seg_epilogue(seg, counts, 2.0)[0]      # argmax - 1 (frame.py:96-121)
+    return {"win_sid": sid, "win_count": cnt, "n_win": nwin, "tokens": tokens, "seg_ids": seg_ids.contiguous(), "n_class": seg.shape[2]}
+
+
+@torch.no_grad()
+def plan_candidates(features: dict, recognition, store: ReferenceStore, *, seg_k: int, min_kpts: int, semantic_matching: bool = True,
+                    overlap_ratio: float = 0.5) -> dict:
+    """Vote + pram_cand_plan.  -> dict(plan int32 [10, B * seg_k] on the device (ops.CAND_PLAN_FIELDS), vote)."""
+    counts = features["counts"]
+    ops._chk(counts, "counts", torch.int32)
+    v = vote_candidates(features, recognition, seg_k)
+    plan = ops.cand_plan(v["win_sid"], v["win_count"], v["n_win"], v["seg_ids"], counts.contiguous(), v["n_class"], store.tables(counts.device),
+                         min_kpts, overlap_ratio, semantic_matching)
+    return {"plan": plan, "vote": v}
+
+
+def _round_up(x: int, m: int) -> int:
+    return (x + m - 1) // m * m
+
+
+@torch.no_grad()
+def gather_candidates(features: dict, planned: dict, store: ReferenceStore) -> dict:
+    """The ONE host synchronisation of the call: the plan table (40 bytes per pair) is read back to fix the padded size of the
+    grouped call — T = max(lens0, lens1) over the pairs, rounded up to 64 — then pram_cand_gather fills the matcher's inputs.
+    -> the matcher's data dict plus 'plan_host' (numpy [10, P]) and 't0' (largest query side)."""
+    plan = planned["plan"]
+    host = plan.cpu().numpy()
+    f = ops.CAND_PLAN_FIELDS
+    t0, t1 = int(host[f.index("lens0")].max(initial=0)), int(host[f.index("lens1")].max(initial=0))
+    T = max(64, _round_up(max(t0, t1), 64))
+    dev = plan.device
+    data = ops.cand_gather(plan, planned["vote"]["tokens"], store.tables(dev), features["descriptors"], features["keypoints"], features["scores"],
+                           _query_norm(features), T)
+    data["keypoints0"], data["keypoints1"] = data["norm_keypoints0"], data["norm_keypoints1"]
+    data["lens0"], data["lens1"] = plan[f.index("lens0")], plan[f.index("lens1")]
+    data["plan_host"], data["t0"] = host, t0
+    return data
+
+
+@torch.no_grad()
+def match_candidates(features: dict, recognition, store: ReferenceStore, matcher, *, seg_k: int, min_kpts: int,
+                     semantic_matching: bool = True, overlap_ratio: float = 0.5) -> List[List[dict]]:
+    """features: the batched extractor output (``keypoints`` [B, N, 2], ``scores`` [B, N], ``descriptors`` [B, N, 128], ``counts``
+    int32 [B], all on the GPU, plus ``image_size`` = (width, height) of the query camera or the ``image`` batch); recognition: see
+    vote_candidates; matcher: GML / AdaGML (the nn.Module or its localization.matchers wrapper).
+
+    -> per query a list of seg_k candidates in vote order; each a dict with the reference's keys — matched_keypoints [m, 2],
+    matched_keypoint_ids [m] int64, matched_xyzs [m, 3] float64, matched_point3D_ids [m] int64, matched_sids [m] int32,
+    matched_ref_keypoints [m, 2] (device tensors), reference_frame_id — plus sid (global, vote id - 1), semantic_matching,
+    n_query_kpts, n_ref_kpts, order, and n_matches (0-d int32 device tensor).  The matched_* tensors are padded to m = n_query_kpts
+    rows; the first n_matches are valid, in ascending query position (no second synchronisation: ``trim_candidate`` cuts them).
+    Candidates beyond the vote's winners (and landmarks without a reference frame) come back empty with reference_frame_id None."""
+    planned = plan_candidates(features, recognition, store, seg_k=seg_k, min_kpts=min_kpts, semantic_matching=semantic_matching,
+                              overlap_ratio=overlap_ratio)
+    data = gather_candidates(features, planned, store)
+    host, t0 = data.pop("plan_host"), data.pop("t0")
+    net = getattr(matcher, "net", matcher)
+    m = net.produce_matches(data)      # its own precision / range-guard scopes (nets/_blocks.with_model_precision)
+    plan = planned["plan"]
+    cor = ops.cand_correspond(m["matches0"][:, :t0], plan, planned["vote"]["tokens"], store.tables(plan.device),
+                              features["keypoints"].contiguous(), t0)
+    f = ops.CAND_PLAN_FIELDS
+    col = lambda name: host[f.index(name)]
+    B = features["counts"].numel()
+    out: List[List[dict]] = []
+    for b in range(B):
+        cands = []
+        for w in range(seg_k):
+            p = b * seg_k + w
+            l0, fr = int(col("lens0")[p]), int(col("frame")[p])
+            c = {k: cor[k][p, :l0] for k in ("matched_keypoints", "matched_keypoint_ids", "matched_xyzs", "matched_point3D_ids", "matched_sids",
+                                             "matched_ref_keypoints")}
+            c.update(reference_frame_id=store.frame_ids[fr] if fr >= 0 else None, sid=int(col("sid")[p]),
+                     semantic_matching=bool(col("semantic")[p]), n_query_kpts=l0, n_ref_kpts=int(col("lens1")[p]), order=w,
+                     n_matches=cor["count"][p], matches0=m["matches0"][p, :l0], matching_scores0=m["matching_scores0"][p, :l0])
+            cands.append(c)
+        out.append(cands)
+    return out
+
+
+def trim_candidate(c: dict) -> dict:
+    """Cut a candidate's matched_* tensors to their n_matches valid rows (reads one int from the device: synchronises)."""
+    n = int(c["n_matches"].item())
+    return {k: (v[:n] if k.startswith("matched_") else v) for k, v in c.items()}

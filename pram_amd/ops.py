@@ -1365,3 +1365,104 @@ def pack_record(kpts: torch.Tensor, scores: torch.Tensor, landmark: Optional[tor
     _lib.check(L.pram_pack_record_f32(_p(kpts), _p(scores), _p(landmark), _p(matches0), _p(mscores0), B, k, km, _p(rec), _st()),
                "pram_pack_record_f32")
     return rec
+
+
+# ---- candidate-landmark matching (csrc/candidates.hip; pram_amd/localization/candidates.py drives these) -------------------
+CAND_PLAN_COLS = 10      # PRAM_CAND_PLAN_COLS
+CAND_PLAN_FIELDS = ("query", "sid", "frame", "semantic", "lens0", "lens1", "tok_off", "row0", "sel_off", "order")
+
+
+def seg_vote_batched(sorted_vals: torch.Tensor, sorted_ids: torch.Tensor, topk: int):
+    """pram_seg_vote for a batch of queries ([B, N, C] sorted class lists): one launch per query into slices of batched buffers
+    -> (win_sid [B, topk], win_rank, win_count, n_win [B], tokens [B, topk, N], mean_score [B, topk]), all on the device."""
+    L = _lib.load()
+    _chk(sorted_vals, "sorted_vals")
+    _chk(sorted_ids, "sorted_ids", _INT64)
+    assert sorted_vals.is_contiguous() and sorted_ids.is_contiguous() and sorted_vals.dim() == 3 and sorted_ids.shape == sorted_vals.shape
+    B, n, c = sorted_vals.shape
+    dev = sorted_vals.device
+    topk = int(topk)
+    sid, rank, cnt = _filled((B, topk), dev, torch.int32), _filled((B, topk), dev, torch.int32), _filled((B, topk), dev, torch.int32)
+    nwin = _filled((B,), dev, torch.int32)
+    tokens = _filled((B, topk, max(n, 1)), dev, torch.int32)
+    mean = _filled((B, topk), dev)
+    st = _st()
+    for b in range(B):
+        _lib.check(L.pram_seg_vote(_p(sorted_ids[b]), _p(sorted_vals[b]), n, c, topk, _p(sid[b]), _p(rank[b]), _p(cnt[b]), _p(nwin[b:]),
+                                   _p(tokens[b]), _p(mean[b]), st), "pram_seg_vote")
+    return sid, rank, cnt, nwin, tokens, mean
+
+
+def cand_mask_ranks_(sorted_ids: torch.Tensor, counts: torch.Tensor) -> torch.Tensor:
+    """In place: the sorted class ids [B, N, C] of the padded tokens (t >= counts[b]) become 0 (background) at every rank."""
+    L = _lib.load()
+    _chk(sorted_ids, "sorted_ids", _INT64)
+    _chk(counts, "counts", torch.int32)
+    assert sorted_ids.is_contiguous() and sorted_ids.dim() == 3 and counts.is_contiguous() and counts.numel() == sorted_ids.shape[0]
+    B, n, c = sorted_ids.shape
+    _lib.check(L.pram_cand_mask_ranks(_p(sorted_ids), _p(counts), B, n, c, _st()), "pram_cand_mask_ranks")
+    return sorted_ids
+
+
+def cand_plan(win_sid, win_count, n_win, seg_ids, counts, n_class: int, store, min_kpts: int, overlap_ratio: float,
+              semantic_matching: bool) -> torch.Tensor:
+    """-> plan int32 [CAND_PLAN_COLS, B * seg_k] (one contiguous column per CAND_PLAN_FIELDS entry).  ``store``: the device tables
+    of a ReferenceStore (dict of tensors)."""
+    L = _lib.load()
+    for t, nm in ((win_sid, "win_sid"), (win_count, "win_count"), (n_win, "n_win"), (seg_ids, "seg_ids"), (counts, "counts")):
+        _chk(t, nm, torch.int32)
+        assert t.is_contiguous(), nm
+    B, seg_k = win_sid.shape
+    n = seg_ids.shape[1]
+    assert seg_ids.shape[0] == B and counts.numel() == B and n_win.numel() == B and win_count.shape == win_sid.shape
+    plan = torch.empty(CAND_PLAN_COLS, B * seg_k, device=win_sid.device, dtype=torch.int32)
+    s = store
+    _lib.check(L.pram_cand_plan(_p(win_sid), _p(win_count), _p(n_win), _p(seg_ids), _p(counts), B, n, int(n_class), seg_k, _p(s["lm_frame"]),
+                                _p(s["lm_sel_off"]), _p(s["lm_sel_len"]), int(s["n_landmarks"]), int(s["start_sid"]), _p(s["frame_off"]),
+                                _p(s["hist_off"]), _p(s["hist_label"]), _p(s["hist_cnt"]), int(s["n_frames"]), int(min_kpts),
+                                float(overlap_ratio), int(bool(semantic_matching)), _p(plan), _st()), "pram_cand_plan")
+    return plan
+
+
+def cand_gather(plan: torch.Tensor, tokens: torch.Tensor, store, q_desc, q_kpts, q_scores, q_norm, t_pad: int):
+    """-> dict(descriptors0/1 [P, T, 128], norm_keypoints0/1 [P, T, 2], scores0/1 [P, T]) filled from the plan; q_norm = (cx, cy, scale)
+    of the queries' camera.  The two sides of each output are halves of one [2P, ...] buffer."""
+    L = _lib.load()
+    for t, nm in ((q_desc, "descriptors"), (q_kpts, "keypoints"), (q_scores, "scores")):
+        _chk(t, nm)
+        assert t.is_contiguous(), nm
+    B, n, D = q_desc.shape
+    assert D == 128 and tuple(q_kpts.shape) == (B, n, 2) and tuple(q_scores.shape) == (B, n)
+    P, T, dev = plan.shape[1], int(t_pad), q_desc.device
+    d = torch.empty(2 * P, T, 128, device=dev, dtype=torch.float32)
+    k = torch.empty(2 * P, T, 2, device=dev, dtype=torch.float32)
+    sc = torch.empty(2 * P, T, device=dev, dtype=torch.float32)
+    s = store
+    _lib.check(L.pram_cand_gather(_p(plan), _p(tokens), _p(s["sel_rows"]), _p(q_desc), _p(q_kpts), _p(q_scores), n, _p(s["descriptors"]),
+                                  _p(s["keypoints"]), _p(s["scores"]), _p(s["frame_norm"]), int(s["n_rows"]), float(q_norm[0]), float(q_norm[1]),
+                                  float(q_norm[2]), _p(d[:P]), _p(k[:P]), _p(sc[:P]), _p(d[P:]), _p(k[P:]), _p(sc[P:]), P, T, _st()),
+               "pram_cand_gather")
+    return {"descriptors0": d[:P], "descriptors1": d[P:], "norm_keypoints0": k[:P], "norm_keypoints1": k[P:], "scores0": sc[:P], "scores1": sc[P:]}
+
+
+def cand_correspond(matches0: torch.Tensor, plan: torch.Tensor, tokens: torch.Tensor, store, q_kpts: torch.Tensor, cap: int):
+    """matches0 int64 [P, >= T0] -> dict of padded per-pair outputs [P, cap, ...] and count int32 [P] (pram_cand_correspond)."""
+    L = _lib.load()
+    _chk(matches0, "matches0", _INT64)
+    _chk(q_kpts, "keypoints")
+    assert matches0.dim() == 2 and matches0.stride(1) == 1 and q_kpts.is_contiguous()
+    P, t0 = matches0.shape
+    assert plan.shape[1] == P
+    n, dev, cap = q_kpts.shape[1], matches0.device, int(cap)
+    c1 = max(cap, 1)
+    out = {"matched_keypoint_ids": torch.empty(P, c1, device=dev, dtype=_INT64), "matched_keypoints": torch.empty(P, c1, 2, device=dev),
+           "matched_ref_keypoints": torch.empty(P, c1, 2, device=dev), "matched_point3D_ids": torch.empty(P, c1, device=dev, dtype=_INT64),
+           "matched_xyzs": torch.empty(P, c1, 3, device=dev, dtype=torch.float64), "matched_sids": torch.empty(P, c1, device=dev, dtype=torch.int32),
+           "count": torch.empty(P, device=dev, dtype=torch.int32)}
+    s = store
+    _lib.check(L.pram_cand_correspond(_p(matches0), matches0.stride(0), _p(plan), _p(tokens), _p(s["sel_rows"]), _p(q_kpts), n, _p(s["keypoints"]),
+                                      _p(s["xyzs"]), _p(s["point3D_ids"]), _p(s["keypoint_segs"]), int(s["n_rows"]), P, t0, cap,
+                                      _p(out["matched_keypoint_ids"]), _p(out["matched_keypoints"]), _p(out["matched_ref_keypoints"]),
+                                      _p(out["matched_point3D_ids"]), _p(out["matched_xyzs"]), _p(out["matched_sids"]), _p(out["count"]), _st()),
+               "pram_cand_correspond")
+    return out
