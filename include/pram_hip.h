@@ -635,6 +635,73 @@ int pram_cand_correspond(const long long* matches0, int ldm, const int* plan, co
                          const int* r_segs, int ref_rows, int pairs, int t0, int cap, long long* m_kpt_ids, float* m_kpts,
                          float* m_ref_kpts, long long* m_point3d_ids, double* m_xyz, int* m_sids, int* m_count, void* stream);
 
+/* ---------------------------------------------------------------- batched absolute pose: P3P RANSAC, refinement, selection
+ * What SingleMap3D.localize_with_ref_frame asks of pycolmap.absolute_pose_estimation (singlemap3d.py:168-193) and the candidate
+ * loop's verify_and_update with its early exit (multimap3d.py:183-239, 294-313), for all pairs of a batch at once, straight from
+ * pram_cand_correspond's padded outputs: m_kpts [pairs][t0][2] float32 (pixels; + 0.5 is added here, as every call site of the
+ * reference does), m_xyz [pairs][t0][3] float64, count [pairs] (rows at and beyond count[p] are never read).  pairs = batch *
+ * seg_k, pair p = query p / seg_k.  float64 arithmetic throughout; every loop has a compile-time or argument-given bound.
+ *
+ * Cameras: one row per query, cam_model [batch] int32 (COLMAP's model ids below) and cam_params [batch][PRAM_POSE_CAM_PARAMS]
+ * float64 in COLMAP's parameter order, zero padded: SIMPLE_PINHOLE f cx cy, PINHOLE fx fy cx cy, SIMPLE_RADIAL f cx cy k,
+ * RADIAL f cx cy k1 k2, OPENCV fx fy cx cy k1 k2 p1 p2.
+ *
+ * The sampler is a pure function of (seed, p, trial, draw): with sm64(x) = { x += 0x9E3779B97F4A7C15; x = (x ^ x >> 30) *
+ * 0xBF58476D1CE4E5B9; x = (x ^ x >> 27) * 0x94D049BB133111EB; return x ^ x >> 31; } on uint64, key = sm64(sm64(seed) ^ (p << 32
+ * | trial)) and word(draw) = sm64(key + draw).  With n = count[p]: i0 = mulhi64(word(0), n), i1 = mulhi64(word(1), n - 1), i2 =
+ * mulhi64(word(2), n - 2) (mulhi64 = the high 64 bits of the 128-bit product); i1 += (i1 >= i0); lo = min(i0, i1), hi = max(i0,
+ * i1); i2 += (i2 >= lo); i2 += (i2 >= hi).
+ *
+ * Workspaces (the caller allocates; nothing is allocated here): norm_pts pairs * t0 * 2 doubles; poses pairs * trials * 48
+ * doubles; n_sol pairs * trials ints; h_inliers pairs * trials * 4 ints; h_resid pairs * trials * 4 doubles; best pairs ints. */
+#define PRAM_CAM_SIMPLE_PINHOLE 0
+#define PRAM_CAM_PINHOLE 1
+#define PRAM_CAM_SIMPLE_RADIAL 2
+#define PRAM_CAM_RADIAL 3
+#define PRAM_CAM_OPENCV 4
+#define PRAM_POSE_CAM_PARAMS 8
+#define PRAM_POSE_UNDISTORT_STEPS 10
+
+/* One thread per (pair, row < count): norm_pts [pairs][t0][2] = the keypoint + 0.5 on the normalised camera plane; distorted
+ * models are inverted by PRAM_POSE_UNDISTORT_STEPS Newton steps on COLMAP's distortion function.  cam_model_host: a HOST copy of
+ * cam_model, checked here without touching the device: an id outside the five models above -> PRAM_E_UNSUPPORTED. */
+int pram_pose_prepare(const float* m_kpts, const int* count, const int* cam_model, const double* cam_params,
+                      const int* cam_model_host, int batch, int seg_k, int t0, double* norm_pts, void* stream);
+
+/* One thread per (pair, trial): three distinct rows below count[p] from the sampler above, then P3P by Grunert's quartic (the
+ * law-of-cosines system reduced to one quartic in the distance ratio v = s3 / s1; Ferrari's closed form, then 3 Newton steps per
+ * root) and the rigid motion from the three point pairs.  poses [pairs][trials][4][12] (row-major R | t, cam_from_world; the
+ * first n_sol slots hold solutions, the rest zeros), n_sol [pairs][trials].  count < 3, collinear or duplicate triples: n_sol =
+ * 0; a root that puts a point behind the camera is dropped.  triples (may be NULL) [pairs][trials][3]: the sampled rows. */
+int pram_pose_hypotheses(const double* norm_pts, const double* m_xyz, const int* count, int pairs, int t0, int trials,
+                         unsigned long long seed, double* poses, int* n_sol, int* triples, void* stream);
+
+/* One workgroup per (pair, 16 trials): rows through LDS in chunks of 768 (30 KB, always chunked), each wave takes 4 trials in
+ * turn per chunk, the 4 slots of a trial in registers.  Squared reprojection error on the normalised plane; inlier if <= (threshold_px / mean focal)^2 and depth
+ * > 0.  h_inliers [pairs][trials * 4] (-1 = empty slot), h_resid = sum of the inliers' squared errors.  Then per pair best [pairs]
+ * = the slot with (most inliers, then smaller residual sum, then smaller index), -1 if every slot is empty. */
+int pram_pose_score(const double* norm_pts, const double* m_xyz, const int* count, const double* poses, const int* n_sol,
+                    const int* cam_model, const double* cam_params, int pairs, int seg_k, int t0, int trials,
+                    double threshold_px, int* h_inliers, double* h_resid, int* best, void* stream);
+
+/* One workgroup per pair.  From the best hypothesis: refine_iters Levenberg-Marquardt iterations (initial damping 1e-3, x 0.1
+ * on an accepted step, x 10 otherwise) over rotation (left axis-angle increment) and translation on the hypothesis' inliers,
+ * residuals in pixels through the full camera model, Cauchy loss of scale 1 px as weights 1 / (1 + r^2); re-score all rows,
+ * refine again on the new inliers, re-score.  A refined pose with fewer inliers than the hypothesis had is discarded for the
+ * hypothesis.  qvec [pairs][4] (w, x, y, z; w >= 0), tvec [pairs][3], inliers [pairs][t0] bytes, num_inliers, success [pairs].
+ * count < 3, best < 0 or a best support below max(3, min_inlier_ratio * count): success = 0 and zeros everywhere. */
+int pram_pose_refine(const float* m_kpts, const double* norm_pts, const double* m_xyz, const int* count, const double* poses,
+                     const int* h_inliers, const int* best, const int* cam_model, const double* cam_params, int pairs, int seg_k,
+                     int t0, int trials, double threshold_px, double min_inlier_ratio, int refine_iters, double* qvec, double* tvec,
+                     unsigned char* inliers, int* num_inliers, int* success, void* stream);
+
+/* One thread per query over its seg_k candidates in vote order: a failed candidate is skipped; a successful one is kept if none
+ * is kept yet or the kept one has fewer inliers; the walk stops at the first with num_inliers >= min_inliers.  chosen [batch][3]
+ * = kept candidate (-1 = none), tracking status (1 = a candidate reached min_inliers, 0 = some succeeded, -1 = none did), order
+ * of the kept candidate (the reference's ret['order'], the position in the vote: by construction the same number as column 0;
+ * kept as a column of its own so that the row reads like the reference's result). */
+int pram_pose_select(const int* success, const int* num_inliers, int batch, int seg_k, int min_inliers, int* chosen, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -101,6 +101,11 @@ _SIGS = {
     "pram_cand_plan": (I, [P, P, P, P, P, I, I, I, I, P, P, P, I, I, P, P, P, P, I, I, C.c_double, I, P, P]),
     "pram_cand_gather": (I, [P, P, P, P, P, P, I, P, P, P, P, I, F, F, F, P, P, P, P, P, P, I, I, P]),
     "pram_cand_correspond": (I, [P, I, P, P, P, P, I, P, P, P, P, I, I, I, I, P, P, P, P, P, P, P, P]),
+    "pram_pose_prepare": (I, [P, P, P, P, P, I, I, I, P, P]),
+    "pram_pose_hypotheses": (I, [P, P, P, I, I, I, C.c_ulonglong, P, P, P, P]),
+    "pram_pose_score": (I, [P, P, P, P, P, P, P, I, I, I, I, C.c_double, P, P, P, P]),
+    "pram_pose_refine": (I, [P, P, P, P, P, P, P, P, P, I, I, I, I, C.c_double, C.c_double, I, P, P, P, P, P, P]),
+    "pram_pose_select": (I, [P, P, I, I, I, P, P]),
 }
 
 

@@ -6,7 +6,7 @@ get_keypoints_by_sid (localization/refframe.py:34-75): per query, for each of th
 voted to it are matched against that landmark's reference frame and matches0 becomes (keypoint, xyz) lists for a pose solver.
 The reference does this in a host loop with a host <-> device round trip per candidate; here the reference frames are resident
 (ReferenceStore), the pairs of ALL queries are planned and gathered by HIP kernels (csrc/candidates.hip), matched in ONE grouped
-produce_matches call, and the correspondences are compacted on the device.  The pose solver itself is not part of this."""
+produce_matches call, and the correspondences are compacted on the device.  The pose solver is pram_amd.localization.pose."""
 from __future__ import annotations
 
 from typing import Dict, List, Optional, Sequence
@@ -213,18 +213,11 @@ def gather_candidates(features: dict, planned: dict, store: ReferenceStore) -> d
 
 
 @torch.no_grad()
-def match_candidates(features: dict, recognition, store: ReferenceStore, matcher, *, seg_k: int, min_kpts: int,
-                     semantic_matching: bool = True, overlap_ratio: float = 0.5) -> List[List[dict]]:
-    """features: the batched extractor output (``keypoints`` [B, N, 2], ``scores`` [B, N], ``descriptors`` [B, N, 128], ``counts``
-    int32 [B], all on the GPU, plus ``image_size`` = (width, height) of the query camera or the ``image`` batch); recognition: see
-    vote_candidates; matcher: GML / AdaGML (the nn.Module or its localization.matchers wrapper).
-
-    -> per query a list of seg_k candidates in vote order; each a dict with the reference's keys — matched_keypoints [m, 2],
-    matched_keypoint_ids [m] int64, matched_xyzs [m, 3] float64, matched_point3D_ids [m] int64, matched_sids [m] int32,
-    matched_ref_keypoints [m, 2] (device tensors), reference_frame_id — plus sid (global, vote id - 1), semantic_matching,
-    n_query_kpts, n_ref_kpts, order, and n_matches (0-d int32 device tensor).  The matched_* tensors are padded to m = n_query_kpts
-    rows; the first n_matches are valid, in ascending query position (no second synchronisation: ``trim_candidate`` cuts them).
-    Candidates beyond the vote's winners (and landmarks without a reference frame) come back empty with reference_frame_id None."""
+def _match_pairs(features: dict, recognition, store: ReferenceStore, matcher, *, seg_k: int, min_kpts: int, semantic_matching: bool,
+                 overlap_ratio: float):
+    """The stages of match_candidates up to the compacted correspondences (ONE host synchronisation, the plan read-back).
+    -> (cor: pram_cand_correspond's padded outputs [P, t0, ...] and count [P], host: the plan table as numpy [10, P],
+    m: the matcher's outputs)."""
     planned = plan_candidates(features, recognition, store, seg_k=seg_k, min_kpts=min_kpts, semantic_matching=semantic_matching,
                               overlap_ratio=overlap_ratio)
     data = gather_candidates(features, planned, store)
@@ -234,9 +227,12 @@ def match_candidates(features: dict, recognition, store: ReferenceStore, matcher
     plan = planned["plan"]
     cor = ops.cand_correspond(m["matches0"][:, :t0], plan, planned["vote"]["tokens"], store.tables(plan.device),
                               features["keypoints"].contiguous(), t0)
+    return cor, host, m
+
+
+def _candidate_lists(cor: dict, host, m: dict, store: ReferenceStore, B: int, seg_k: int) -> List[List[dict]]:
     f = ops.CAND_PLAN_FIELDS
     col = lambda name: host[f.index(name)]
-    B = features["counts"].numel()
     out: List[List[dict]] = []
     for b in range(B):
         cands = []
@@ -251,6 +247,24 @@ def match_candidates(features: dict, recognition, store: ReferenceStore, matcher
             cands.append(c)
         out.append(cands)
     return out
+
+
+@torch.no_grad()
+def match_candidates(features: dict, recognition, store: ReferenceStore, matcher, *, seg_k: int, min_kpts: int,
+                     semantic_matching: bool = True, overlap_ratio: float = 0.5) -> List[List[dict]]:
+    """features: the batched extractor output (``keypoints`` [B, N, 2], ``scores`` [B, N], ``descriptors`` [B, N, 128], ``counts``
+    int32 [B], all on the GPU, plus ``image_size`` = (width, height) of the query camera or the ``image`` batch); recognition: see
+    vote_candidates; matcher: GML / AdaGML (the nn.Module or its localization.matchers wrapper).
+
+    -> per query a list of seg_k candidates in vote order; each a dict with the reference's keys — matched_keypoints [m, 2],
+    matched_keypoint_ids [m] int64, matched_xyzs [m, 3] float64, matched_point3D_ids [m] int64, matched_sids [m] int32,
+    matched_ref_keypoints [m, 2] (device tensors), reference_frame_id — plus sid (global, vote id - 1), semantic_matching,
+    n_query_kpts, n_ref_kpts, order, and n_matches (0-d int32 device tensor).  The matched_* tensors are padded to m = n_query_kpts
+    rows; the first n_matches are valid, in ascending query position (no second synchronisation: ``trim_candidate`` cuts them).
+    Candidates beyond the vote's winners (and landmarks without a reference frame) come back empty with reference_frame_id None."""
+    cor, host, m = _match_pairs(features, recognition, store, matcher, seg_k=seg_k, min_kpts=min_kpts, semantic_matching=semantic_matching,
+                                overlap_ratio=overlap_ratio)
+    return _candidate_lists(cor, host, m, store, features["counts"].numel(), seg_k)
 
 
 def trim_candidate(c: dict) -> dict:

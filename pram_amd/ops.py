@@ -1466,3 +1466,124 @@ def cand_correspond(matches0: torch.Tensor, plan: torch.Tensor, tokens: torch.Te
                                       _p(out["matched_point3D_ids"]), _p(out["matched_xyzs"]), _p(out["matched_sids"]), _p(out["count"]), _st()),
                "pram_cand_correspond")
     return out
+
+
+# ---- batched absolute pose (csrc/pose.hip; pram_amd/localization/pose.py drives these) ---------------------------------------
+CAMERA_MODELS = {"SIMPLE_PINHOLE": 0, "PINHOLE": 1, "SIMPLE_RADIAL": 2, "RADIAL": 3, "OPENCV": 4}      # PRAM_CAM_*
+POSE_CAM_PARAMS = 8      # PRAM_POSE_CAM_PARAMS
+
+
+def _pose_chk(m_kpts, m_xyz, counts):
+    _chk(m_kpts, "matched_keypoints")
+    _chk(m_xyz, "matched_xyzs", torch.float64)
+    _chk(counts, "counts", torch.int32)
+    assert m_kpts.is_contiguous() and m_xyz.is_contiguous() and counts.is_contiguous()
+    P, t0 = m_kpts.shape[:2]
+    assert tuple(m_kpts.shape) == (P, t0, 2) and tuple(m_xyz.shape) == (P, t0, 3) and counts.numel() == P
+    return P, t0
+
+
+def _pose_chk_stage(norm_pts, m_xyz, counts, cam_model, cam_params, seg_k):
+    """dtype, device, contiguity and shapes of what pose_score / pose_refine hand over as raw pointers -> (P, t0, B)."""
+    _chk(norm_pts, "norm_pts", torch.float64)
+    _chk(m_xyz, "matched_xyzs", torch.float64)
+    _chk(counts, "counts", torch.int32)
+    _chk(cam_model, "cam_model", torch.int32)
+    _chk(cam_params, "cam_params", torch.float64)
+    assert norm_pts.is_contiguous() and m_xyz.is_contiguous() and counts.is_contiguous() and cam_model.is_contiguous() and cam_params.is_contiguous()
+    P, t0 = norm_pts.shape[:2]
+    B, seg_k = cam_model.numel(), int(seg_k)
+    assert tuple(norm_pts.shape) == (P, t0, 2) and tuple(m_xyz.shape) == (P, t0, 3) and counts.numel() == P
+    assert seg_k >= 1 and P == B * seg_k and tuple(cam_params.shape) == (B, POSE_CAM_PARAMS)
+    return P, t0, B
+
+
+def pose_prepare(m_kpts: torch.Tensor, counts: torch.Tensor, cam_model: torch.Tensor, cam_params: torch.Tensor, cam_model_host,
+                 seg_k: int) -> torch.Tensor:
+    """matched_keypoints float32 [P, t0, 2] (+ 0.5 inside) -> normalised camera-plane points float64 [P, t0, 2]; rows >= counts[p]
+    are left unwritten.  cam_model int32 [B], cam_params float64 [B, 8] on the device, cam_model_host: the ids on the host
+    (a sequence of ints), which is what the launcher validates."""
+    import ctypes
+    L = _lib.load()
+    _chk(m_kpts, "matched_keypoints")
+    _chk(counts, "counts", torch.int32)
+    _chk(cam_model, "cam_model", torch.int32)
+    _chk(cam_params, "cam_params", torch.float64)
+    assert m_kpts.is_contiguous() and counts.is_contiguous() and cam_model.is_contiguous() and cam_params.is_contiguous()
+    P, t0 = m_kpts.shape[:2]
+    B, seg_k = cam_model.numel(), int(seg_k)
+    assert seg_k >= 1 and P == B * seg_k and counts.numel() == P and tuple(cam_params.shape) == (B, POSE_CAM_PARAMS) and len(cam_model_host) == B
+    host = (ctypes.c_int * max(B, 1))(*[int(m) for m in cam_model_host])
+    pts = torch.empty(P, t0, 2, device=m_kpts.device, dtype=torch.float64)
+    _lib.check(L.pram_pose_prepare(_p(m_kpts), _p(counts), _p(cam_model), _p(cam_params), ctypes.addressof(host), B, seg_k, t0, _p(pts), _st()),
+               "pram_pose_prepare")
+    return pts
+
+
+def pose_hypotheses(norm_pts: torch.Tensor, m_xyz: torch.Tensor, counts: torch.Tensor, trials: int, seed: int, with_triples: bool = False):
+    """-> (poses float64 [P, trials, 4, 12], n_sol int32 [P, trials][, triples int32 [P, trials, 3]])."""
+    L = _lib.load()
+    _chk(norm_pts, "norm_pts", torch.float64)
+    _chk(m_xyz, "matched_xyzs", torch.float64)
+    _chk(counts, "counts", torch.int32)
+    assert norm_pts.is_contiguous() and m_xyz.is_contiguous() and counts.is_contiguous()
+    P, t0 = norm_pts.shape[:2]
+    assert tuple(m_xyz.shape) == (P, t0, 3) and counts.numel() == P
+    trials, dev = int(trials), norm_pts.device
+    poses = torch.empty(P, max(trials, 1), 4, 12, device=dev, dtype=torch.float64)
+    n_sol = torch.empty(P, max(trials, 1), device=dev, dtype=torch.int32)
+    tri = torch.empty(P, max(trials, 1), 3, device=dev, dtype=torch.int32) if with_triples else None
+    _lib.check(L.pram_pose_hypotheses(_p(norm_pts), _p(m_xyz), _p(counts), P, t0, trials, int(seed) & 0xFFFFFFFFFFFFFFFF, _p(poses), _p(n_sol),
+                                      _p(tri), _st()), "pram_pose_hypotheses")
+    return (poses, n_sol, tri) if with_triples else (poses, n_sol)
+
+
+def pose_score(norm_pts, m_xyz, counts, poses, n_sol, cam_model, cam_params, seg_k: int, threshold: float):
+    """-> (h_inliers int32 [P, trials * 4] (-1 = empty slot), h_resid float64 [P, trials * 4], best int32 [P])."""
+    L = _lib.load()
+    P, t0, B = _pose_chk_stage(norm_pts, m_xyz, counts, cam_model, cam_params, seg_k)
+    trials, dev = poses.shape[1], norm_pts.device
+    _chk(poses, "poses", torch.float64)
+    _chk(n_sol, "n_sol", torch.int32)
+    assert poses.is_contiguous() and n_sol.is_contiguous() and tuple(poses.shape) == (P, trials, 4, 12) and tuple(n_sol.shape) == (P, trials)
+    h_inl = torch.empty(P, trials * 4, device=dev, dtype=torch.int32)
+    h_res = torch.empty(P, trials * 4, device=dev, dtype=torch.float64)
+    best = torch.empty(P, device=dev, dtype=torch.int32)
+    _lib.check(L.pram_pose_score(_p(norm_pts), _p(m_xyz), _p(counts), _p(poses), _p(n_sol), _p(cam_model), _p(cam_params), P, int(seg_k), t0, trials,
+                                 float(threshold), _p(h_inl), _p(h_res), _p(best), _st()), "pram_pose_score")
+    return h_inl, h_res, best
+
+
+def pose_refine(m_kpts, norm_pts, m_xyz, counts, poses, h_inl, best, cam_model, cam_params, seg_k: int, threshold: float,
+                min_inlier_ratio: float, refine_iters: int) -> dict:
+    """-> dict(qvec float64 [P, 4] (w, x, y, z), tvec [P, 3], inliers uint8 [P, t0], num_inliers int32 [P], success int32 [P])."""
+    L = _lib.load()
+    P, t0 = _pose_chk(m_kpts, m_xyz, counts)
+    _pose_chk_stage(norm_pts, m_xyz, counts, cam_model, cam_params, seg_k)
+    trials, dev = poses.shape[1], m_kpts.device
+    _chk(poses, "poses", torch.float64)
+    _chk(h_inl, "h_inliers", torch.int32)
+    _chk(best, "best", torch.int32)
+    assert poses.is_contiguous() and h_inl.is_contiguous() and best.is_contiguous()
+    assert tuple(poses.shape) == (P, trials, 4, 12) and tuple(h_inl.shape) == (P, trials * 4) and best.numel() == P
+    out = {"qvec": torch.empty(P, 4, device=dev, dtype=torch.float64), "tvec": torch.empty(P, 3, device=dev, dtype=torch.float64),
+           "inliers": torch.empty(P, t0, device=dev, dtype=torch.uint8), "num_inliers": torch.empty(P, device=dev, dtype=torch.int32),
+           "success": torch.empty(P, device=dev, dtype=torch.int32)}
+    _lib.check(L.pram_pose_refine(_p(m_kpts), _p(norm_pts), _p(m_xyz), _p(counts), _p(poses), _p(h_inl), _p(best), _p(cam_model), _p(cam_params), P,
+                                  int(seg_k), t0, trials, float(threshold), float(min_inlier_ratio), int(refine_iters), _p(out["qvec"]),
+                                  _p(out["tvec"]), _p(out["inliers"]), _p(out["num_inliers"]), _p(out["success"]), _st()), "pram_pose_refine")
+    return out
+
+
+def pose_select(success: torch.Tensor, num_inliers: torch.Tensor, seg_k: int, min_inliers: int) -> torch.Tensor:
+    """success / num_inliers int32 [B * seg_k] -> int32 [B, 3]: kept candidate (-1 none), tracking status (1 / 0 / -1 none), order."""
+    L = _lib.load()
+    _chk(success, "success", torch.int32)
+    _chk(num_inliers, "num_inliers", torch.int32)
+    seg_k = int(seg_k)
+    assert success.is_contiguous() and num_inliers.is_contiguous() and success.numel() == num_inliers.numel()
+    assert seg_k >= 1 and success.numel() % seg_k == 0
+    B = success.numel() // seg_k
+    chosen = torch.empty(B, 3, device=success.device, dtype=torch.int32)
+    _lib.check(L.pram_pose_select(_p(success), _p(num_inliers), B, seg_k, int(min_inliers), _p(chosen), _st()), "pram_pose_select")
+    return chosen
