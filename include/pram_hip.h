@@ -23,6 +23,8 @@
  *   - keypoint selection sorts a top-k of up to 8192 keypoints per frame in LDS; larger bounds sort in the caller's workspace
  *     (pram_select_keypoints_workspace_bytes accounts for it) and max_keypoints >= h * w keeps everything unsorted;
  *   - AdaGML pruning handles token sets of at most 8192 tokens (pram_adagml_prune_f32);
+ *   - Sinkhorn / dual-softmax matching handles at most 8191 rows (m_max) and 4351 columns (n_max) per pair, the dust-bin row
+ *     and column excluded (pram_sinkhorn_match_f32, pram_dual_softmax_match_f32);
  *   - LayerNorm rows are at most 1024 wide; the split-fp16 GEMMs need K % 32 == 0 (other shapes: the exact-fp32 entry);
  *   - the split-fp16 operands carry value * s in fp16 (s = 16 by default, pram_x3_set_act_scale): a finite |x| >= 65520 / s
  *     (4094.97) does not fit.  This one is NOT a silent limit
@@ -324,7 +326,8 @@ size_t pram_sinkhorn_workspace_bytes(int batch, int m_max, int n_max);
  *   p_out (optional) [batch][m_max+1][ldp] the final P*u*v (for parity with sink_algorithm)
  *   compute_matches (nets/gml.py:304-319; K14) fused into the last pass:
  *   matches0 [batch][m_max] int64 (-1 none), matches1 [batch][n_max], mscores0/1 fp32.
- * Rows >= m_b / cols >= n_b of the outputs are filled with -1 / 0. */
+ * Rows >= m_b / cols >= n_b of the outputs are filled with -1 / 0.
+ * m_max <= 8191 and n_max <= 4351; a larger problem is refused with PRAM_E_ARG. */
 int pram_sinkhorn_match_f32(const float* dist, int ldd, const int* m_lens, const int* n_lens,
                             const float* bin_score, int iters, float match_threshold,
                             float* p_out, int ldp, long long* matches0, long long* matches1,

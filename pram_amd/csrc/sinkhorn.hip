@@ -229,7 +229,7 @@ __global__ __launch_bounds__(256) void sink_iter_kernel(const int* __restrict__ 
         }
     }
     {
-        const int i = rbeg + wave + 4 * lane;      // at most ceil(4352 / 32 / 4) = 34 rows per wave
+        const int i = rbeg + wave + 4 * lane;      // at most ceil(8192 / 32 / 4) = 64 rows per wave: one per lane (dispatch bounds m_max)
         if (i < rend) w.u[(size_t)b * (m_max + 1) + i] = ukeep;
     }
     float* part = w.part + ((size_t)b * NBLK * 4 + blk * 4 + wave) * ldw;
@@ -351,7 +351,7 @@ __global__ __launch_bounds__(256) void sink_final_kernel(const int* __restrict__
         if (lane == ((i - rbeg) >> 2)) { rkeep = best; ikeep = bidx; }
     }
     {
-        const int i = rbeg + wave + 4 * lane;      // at most ceil(4352 / 32 / 4) = 34 rows per wave
+        const int i = rbeg + wave + 4 * lane;      // at most ceil(8192 / 32 / 4) = 64 rows per wave: one per lane (dispatch bounds m_max)
         if (i < rend && i < m) {
             w.rowval[(size_t)b * m_max + i] = rkeep;
             w.rowidx[(size_t)b * m_max + i] = ikeep;
@@ -545,6 +545,8 @@ int dispatch(const float* dist, int ldd, const int* m_lens, const int* n_lens, c
     PRAM_REQUIRE(dist && bin && workspace, "sinkhorn: null pointer");
     PRAM_REQUIRE(batch >= 0 && m_max > 0 && n_max > 0 && iters >= 0, "sinkhorn: bad sizes");
     PRAM_REQUIRE(n_max + 1 <= 17 * 256, "sinkhorn: n_max=%d exceeds 4351 columns", n_max);
+    // a wave keeps one row's u_i / arg-max per lane: NBLK blocks x 4 waves x 64 lanes rows, the dust-bin row included
+    PRAM_REQUIRE(m_max + 1 <= NBLK * 4 * 64, "sinkhorn: m_max=%d exceeds 8191 rows", m_max);
     PRAM_REQUIRE(!p_out || ldp >= n_max + 1, "sinkhorn: ldp too small");
     if (batch == 0) return PRAM_OK;
     SinkWs w = carve(workspace, batch, m_max, n_max, nullptr);

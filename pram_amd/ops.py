@@ -903,7 +903,8 @@ sinkhorn_group_bytes = 135 << 20
 def sinkhorn_match(dist: torch.Tensor, bin_score: torch.Tensor, iters: int, threshold: float,
                    m_lens=None, n_lens=None, want_p: bool = False, dual_softmax: bool = False, n_valid: Optional[int] = None):
     """dist [B, M, ldd] (first n_valid (default ldd) columns valid).  Returns dict with matches0/1 (int64),
-    matching_scores0/1 and optionally the full assignment matrix 'p' [B, M+1, N+1]."""
+    matching_scores0/1 and optionally the full assignment matrix 'p' [B, M+1, N+1].  Limits: M <= 8191 rows and
+    N <= 4351 columns (the dust-bin row and column come on top); a larger problem raises PramHipError."""
     L = _lib.load()
     _chk(dist, "dist")
     assert dist.is_contiguous() and dist.dim() == 3
