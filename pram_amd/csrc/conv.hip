@@ -12,6 +12,7 @@
 #include "gemm_core_f16.h"
 #include "gemm_core_x3.h"
 #include "gemm_core_x3w.h"
+#include "launch.h"
 
 namespace {
 
@@ -834,142 +835,138 @@ __global__ __launch_bounds__(256) void nhwc_to_nchw_kernel(const float* __restri
     }
 }
 
+// What differs between the five pram_conv2d_nhwc_* entries' checks: the channel multiple (0: the exact-fp32 path's "4 or a
+// multiple of 32") and whether the im2col loader's 32-bit offsets bound the image.
+struct ConvRules { int cin_mult; bool offsets32; };
+
+// The checks the five entries share, on the operands and sizes entry `who` has written into p by name
+int conv_check(const char* who, const ConvArgs& p, const ConvRules& r, bool ptrs_ok, float w_scale) {
+    PRAM_REQUIRE(ptrs_ok, "%s: null pointer", who);
+    PRAM_REQUIRE(p.ks == 1 || p.ks == 3, "%s: ks must be 1 or 3", who);
+    PRAM_REQUIRE(!r.offsets32 || (long long)p.h * p.wd * p.cin < (1ll << 31),
+                 "%s: an image of %d x %d x %d elements does not fit the 32-bit offsets of the im2col loader", who, p.h, p.wd, p.cin);
+    PRAM_REQUIRE(p.stride == 1 || p.stride == 2, "%s: stride must be 1 or 2", who);
+    if (r.cin_mult == 0)
+        PRAM_REQUIRE(p.cin == 4 || p.cin % 32 == 0, "%s: cin=%d must be 4 or a multiple of 32", who, p.cin);
+    else
+        PRAM_REQUIRE(p.cin % r.cin_mult == 0 && w_scale > 0.f, "%s: cin=%d must be a multiple of %d", who, p.cin, r.cin_mult);
+    PRAM_REQUIRE((p.scale == nullptr) == (p.shift == nullptr), "%s: scale and shift go together", who);
+    return PRAM_OK;
+}
+
+// conv_check, then the output geometry: pad, ho, wo, m and k are computed here and nowhere else
+int conv_args(const char* who, ConvArgs& p, const ConvRules& r, bool ptrs_ok, float w_scale) {
+    if (int e = conv_check(who, p, r, ptrs_ok, w_scale)) return e;
+    const int pad = p.ks / 2;
+    p.ho = (p.h + 2 * pad - p.ks) / p.stride + 1;
+    p.wo = (p.wd + 2 * pad - p.ks) / p.stride + 1;
+    p.m = p.batch * p.ho * p.wo;
+    p.k = p.ks * p.ks * p.cin;
+    return PRAM_OK;
+}
+
+// Arms the split-fp16 path from one read of the activation scale (status word, plane scale); returns the kernels' `inv`.
+float arm_split(ConvArgs& p, float w_scale) {
+    p.status = pram_status_ptr();
+    p.act_scale = pram_act_scale();
+    return 1.0f / (p.act_scale * w_scale);
+}
+
+constexpr ConvRules CONV_F32{0, false}, CONV_F16{64, true}, CONV_X3{32, true};
+
 }  // namespace
 
 extern "C" int pram_conv2d_nhwc_f32(const float* in, int batch, int h, int w, int cin, const float* wgt,
                                     const float* bias, const float* scale, const float* shift, const float* residual,
                                     float* out, int cout, int ks, int stride, int relu, void* stream) {
-    PRAM_REQUIRE(in && wgt && out, "pram_conv2d_nhwc_f32: null pointer");
-    PRAM_REQUIRE(ks == 1 || ks == 3, "pram_conv2d_nhwc_f32: ks must be 1 or 3");
-    PRAM_REQUIRE(stride == 1 || stride == 2, "pram_conv2d_nhwc_f32: stride must be 1 or 2");
-    PRAM_REQUIRE(cin == 4 || cin % 32 == 0, "pram_conv2d_nhwc_f32: cin=%d must be 4 or a multiple of 32", cin);
-    PRAM_REQUIRE((scale == nullptr) == (shift == nullptr), "pram_conv2d_nhwc_f32: scale and shift go together");
+    const char* who = "pram_conv2d_nhwc_f32";
+    ConvArgs p{};
+    p.in = in; p.w = wgt; p.bias = bias; p.scale = scale; p.shift = shift; p.residual = residual; p.out = out;
+    p.batch = batch; p.h = h; p.wd = w; p.cin = cin; p.cout = cout; p.ks = ks; p.stride = stride; p.relu = relu;
+    if (int e = conv_args(who, p, CONV_F32, in && wgt && out, 1.0f)) return e;
     if (batch == 0) return PRAM_OK;
-    const int pad = ks / 2;
-    ConvArgs p{in, wgt, bias, scale, shift, residual, out, batch, h, w, cin, cout, ks, stride, relu};
-    p.ho = (h + 2 * pad - ks) / stride + 1;
-    p.wo = (w + 2 * pad - ks) / stride + 1;
-    p.m = batch * p.ho * p.wo;
-    p.k = ks * ks * cin;
     int mi, wn;
     gemm::choose_tile(p.m, cout, &mi, &wn);
     hipStream_t st = (hipStream_t)stream;
+    if (cin == 4) {      // the stem's padded RGB input: 256-row tiles whatever the grid
+        dispatch_tile(2, wn, [&](auto, auto WN) {
+            hipLaunchKernelGGL((conv_kernel<true, 2, WN, 16>), dim3(set_tiles<gemm::Cfg<2, WN, 16>>(p, cout)), dim3(gemm::NT), 0, st, p);
+        });
+        return pram_launch_status(who);
+    }
     // 64-channel outputs (conv1a, conv1b: short K, write-heavy) take the 16-deep chunk, the deep-K layers the 32-deep one
-#define LAUNCH(C4, MI_, WN_, BK_)                                                                                   \
-    do {                                                                                                            \
-        p.tiles_m = cdiv(p.m, gemm::Cfg<MI_, WN_, BK_>::BM);                                                        \
-        p.tiles_n = cdiv(cout, gemm::Cfg<MI_, WN_, BK_>::BN);                                                       \
-        hipLaunchKernelGGL((conv_kernel<C4, MI_, WN_, BK_>), dim3(p.tiles_m * p.tiles_n), dim3(gemm::NT), 0, st, p); \
-    } while (0)
-    if (cin == 4) { if (wn == 1) LAUNCH(true, 2, 1, 16); else LAUNCH(true, 2, 2, 16); }
-    else if (wn == 1) { if (mi == 2) LAUNCH(false, 2, 1, 16); else LAUNCH(false, 1, 1, 16); }
-    else { if (mi == 2) LAUNCH(false, 2, 2, 32); else LAUNCH(false, 1, 2, 32); }
-#undef LAUNCH
-    return pram_launch_status("pram_conv2d_nhwc_f32");
+    dispatch_tile(mi, wn, [&](auto MI, auto WN) {
+        constexpr int BKT = WN == 1 ? 16 : 32;
+        hipLaunchKernelGGL((conv_kernel<false, MI, WN, BKT>), dim3(set_tiles<gemm::Cfg<MI, WN, BKT>>(p, cout)), dim3(gemm::NT), 0, st, p);
+    });
+    return pram_launch_status(who);
 }
 
 extern "C" int pram_conv2d_nhwc_f16_f32(const float* in, int batch, int h, int w, int cin, const void* wgt16,
                                         const float* bias, const float* scale, const float* shift, const float* residual,
                                         float* out, int cout, int ks, int stride, int relu, void* stream) {
-    PRAM_REQUIRE(in && wgt16 && out, "pram_conv2d_nhwc_f16_f32: null pointer");
-    PRAM_REQUIRE(ks == 1 || ks == 3, "pram_conv2d_nhwc_f16_f32: ks must be 1 or 3");
-    PRAM_REQUIRE((long long)h * w * cin < (1ll << 31), "pram_conv2d_nhwc_f16_f32: an image of %d x %d x %d elements does not fit the 32-bit offsets of the im2col loader", h, w, cin);
-    PRAM_REQUIRE(stride == 1 || stride == 2, "pram_conv2d_nhwc_f16_f32: stride must be 1 or 2");
-    PRAM_REQUIRE(cin % 64 == 0, "pram_conv2d_nhwc_f16_f32: cin=%d must be a multiple of 64", cin);
-    PRAM_REQUIRE((scale == nullptr) == (shift == nullptr), "pram_conv2d_nhwc_f16_f32: scale and shift go together");
+    const char* who = "pram_conv2d_nhwc_f16_f32";
+    ConvArgs p{};
+    p.in = in; p.bias = bias; p.scale = scale; p.shift = shift; p.residual = residual; p.out = out;
+    p.batch = batch; p.h = h; p.wd = w; p.cin = cin; p.cout = cout; p.ks = ks; p.stride = stride; p.relu = relu;
+    if (int e = conv_args(who, p, CONV_F16, in && wgt16 && out, 1.0f)) return e;
     if (batch == 0) return PRAM_OK;
-    const int pad = ks / 2;
-    ConvArgs p{in, nullptr, bias, scale, shift, residual, out, batch, h, w, cin, cout, ks, stride, relu};
-    p.ho = (h + 2 * pad - ks) / stride + 1;
-    p.wo = (w + 2 * pad - ks) / stride + 1;
-    p.m = batch * p.ho * p.wo;
-    p.k = ks * ks * cin;
     int mi, wn;
     gemm::choose_tile(p.m, cout, &mi, &wn);
-    hipStream_t st = (hipStream_t)stream;
-    const _Float16* w16 = (const _Float16*)wgt16;
-#define LAUNCH16(MI_, WN_)                                                                                          \
-    do {                                                                                                            \
-        p.tiles_m = cdiv(p.m, gemm16::Cfg<MI_, WN_>::BM);                                                           \
-        p.tiles_n = cdiv(cout, gemm16::Cfg<MI_, WN_>::BN);                                                          \
-        hipLaunchKernelGGL((conv_f16_kernel<MI_, WN_>), dim3(p.tiles_m * p.tiles_n), dim3(gemm16::NT), 0, st, p, w16); \
-    } while (0)
-    if (wn == 1) { if (mi == 2) LAUNCH16(2, 1); else LAUNCH16(1, 1); }
-    else { if (mi == 2) LAUNCH16(2, 2); else LAUNCH16(1, 2); }
-#undef LAUNCH16
-    return pram_launch_status("pram_conv2d_nhwc_f16_f32");
+    dispatch_tile(mi, wn, [&](auto MI, auto WN) {
+        const int tiles = set_tiles<gemm16::Cfg<MI, WN>>(p, cout);
+        hipLaunchKernelGGL((conv_f16_kernel<MI, WN>), dim3(tiles), dim3(gemm16::NT), 0, (hipStream_t)stream, p, (const _Float16*)wgt16);
+    });
+    return pram_launch_status(who);
 }
 
 extern "C" int pram_conv2d_nhwc_x3_f32(const float* in, int batch, int h, int w, int cin, const void* wgt_hi, const void* wgt_lo,
                                        float w_scale, const float* bias, const float* scale, const float* shift,
                                        const float* residual, float* out, int cout, int ks, int stride, int relu, void* stream) {
-    PRAM_REQUIRE(in && wgt_hi && wgt_lo && out, "pram_conv2d_nhwc_x3_f32: null pointer");
-    PRAM_REQUIRE(ks == 1 || ks == 3, "pram_conv2d_nhwc_x3_f32: ks must be 1 or 3");
-    PRAM_REQUIRE((long long)h * w * cin < (1ll << 31), "pram_conv2d_nhwc_x3_f32: an image of %d x %d x %d elements does not fit the 32-bit offsets of the im2col loader", h, w, cin);
-    PRAM_REQUIRE(stride == 1 || stride == 2, "pram_conv2d_nhwc_x3_f32: stride must be 1 or 2");
-    PRAM_REQUIRE(cin % 32 == 0 && w_scale > 0.f, "pram_conv2d_nhwc_x3_f32: cin=%d must be a multiple of 32", cin);
-    PRAM_REQUIRE((scale == nullptr) == (shift == nullptr), "pram_conv2d_nhwc_x3_f32: scale and shift go together");
+    const char* who = "pram_conv2d_nhwc_x3_f32";
+    ConvArgs p{};
+    p.in = in; p.bias = bias; p.scale = scale; p.shift = shift; p.residual = residual; p.out = out;
+    p.batch = batch; p.h = h; p.wd = w; p.cin = cin; p.cout = cout; p.ks = ks; p.stride = stride; p.relu = relu;
+    if (int e = conv_args(who, p, CONV_X3, in && wgt_hi && wgt_lo && out, w_scale)) return e;
     if (batch == 0) return PRAM_OK;
-    const int pad = ks / 2;
-    ConvArgs p{in, nullptr, bias, scale, shift, residual, out, batch, h, w, cin, cout, ks, stride, relu};
-    p.ho = (h + 2 * pad - ks) / stride + 1;
-    p.wo = (w + 2 * pad - ks) / stride + 1;
-    p.m = batch * p.ho * p.wo;
-    p.k = ks * ks * cin;
-    p.status = pram_status_ptr();
-    p.act_scale = pram_act_scale();
-    int mi, wn;
-    gemm::choose_tile(p.m, cout, &mi, &wn);
+    const float inv = arm_split(p, w_scale);
     hipStream_t st = (hipStream_t)stream;
     const _Float16* wh = (const _Float16*)wgt_hi;
     const _Float16* wl = (const _Float16*)wgt_lo;
-    const float inv = 1.0f / (pram_act_scale() * w_scale);
-#define LAUNCHX3(MI_, WN_)                                                                                              \
-    do {                                                                                                                \
-        p.tiles_m = cdiv(p.m, gemmx3::Cfg<MI_, WN_>::BM);                                                               \
-        p.tiles_n = cdiv(cout, gemmx3::Cfg<MI_, WN_>::BN);                                                              \
-        hipLaunchKernelGGL((conv_x3_kernel<MI_, WN_>), dim3(p.tiles_m * p.tiles_n), dim3(gemmx3::NT), 0, st, p, wh, wl, inv); \
-    } while (0)
     static const char* force = prof_env("PRAM_X3_TILE");
     const char* halo_env = getenv("PRAM_CONV_HALO");      // "0": the per-tap staging kernel for every layer (profiling / the equality test; read per call)
     // PRAM_CONV_HALO: "0" = never, "w" = the 256-channel form only (what the 128-channel form buys is measured with it)
     if (ks == 3 && stride == 1 && (cout >= 256 || (cout == 128 && !(halo_env && halo_env[0] == 'w'))) && !(force && force[0] == 'n') &&
         !(halo_env && halo_env[0] == '0') && (long long)p.ho * p.wo * cout < (1ll << 31)) {      // (its epilogue: 32-bit offsets per map)
         const int tiles_x = cdiv(p.wo, halo::TW), tiles_y = cdiv(p.ho, halo::TH);
-        p.tiles_m = batch * tiles_x * tiles_y;
+        p.tiles_m = batch * tiles_x * tiles_y;      // spatial tiles, not rows: the one grid set_tiles does not describe
         const bool narrow = cout <= 128;      // one 128-channel column tile
         p.tiles_n = cdiv(cout, narrow ? 128 : 256);
         if ((long)p.tiles_m * p.tiles_n >= 224) {
-            static bool hattr = false;
-            if (!hattr) {
-                (void)hipFuncSetAttribute((const void*)conv3x3_x3h_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(halo::Smem<4>));
-                (void)hipFuncSetAttribute((const void*)conv3x3_x3h_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(halo::Smem<2>));
-                hattr = true;
-            }
-            if (narrow)
+            if (narrow) {
+                opt_in_lds<conv3x3_x3h_kernel<2>>(sizeof(halo::Smem<2>));
                 hipLaunchKernelGGL(conv3x3_x3h_kernel<2>, dim3(p.tiles_m * p.tiles_n), dim3(halo::NT), sizeof(halo::Smem<2>), st, p, wh, wl, inv, tiles_x, tiles_y);
-            else
+            } else {
+                opt_in_lds<conv3x3_x3h_kernel<4>>(sizeof(halo::Smem<4>));
                 hipLaunchKernelGGL(conv3x3_x3h_kernel<4>, dim3(p.tiles_m * p.tiles_n), dim3(halo::NT), sizeof(halo::Smem<4>), st, p, wh, wl, inv, tiles_x, tiles_y);
-            return pram_launch_status("pram_conv2d_nhwc_x3_f32");
+            }
+            return pram_launch_status(who);
         }
     }
     if (cout >= 256 && (long)cdiv(p.m, 256) * cdiv(cout, 256) >= 224 && !(force && force[0] == 'n')) {
         using CW = gemmx3w::Cfg<4, 2, 4>;
         const size_t shm = sizeof(gemmx3w::Smem<4, 2, 4>);
-        static bool attr_set = false;
-        if (!attr_set) {
-            (void)hipFuncSetAttribute((const void*)conv_x3w_kernel<4, 2, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
-            attr_set = true;
-        }
-        p.tiles_m = cdiv(p.m, CW::BM);
-        p.tiles_n = cdiv(cout, CW::BN);
-        hipLaunchKernelGGL((conv_x3w_kernel<4, 2, 4>), dim3(p.tiles_m * p.tiles_n), dim3(CW::NT), shm, st, p, wh, wl, inv);
-        return pram_launch_status("pram_conv2d_nhwc_x3_f32");
+        opt_in_lds<conv_x3w_kernel<4, 2, 4>>(shm);
+        hipLaunchKernelGGL((conv_x3w_kernel<4, 2, 4>), dim3(set_tiles<CW>(p, cout)), dim3(CW::NT), shm, st, p, wh, wl, inv);
+        return pram_launch_status(who);
     }
-    if (wn == 1) { if (mi == 2) LAUNCHX3(2, 1); else LAUNCHX3(1, 1); }
-    else { if (mi == 2) LAUNCHX3(2, 2); else LAUNCHX3(1, 2); }
-#undef LAUNCHX3
-    return pram_launch_status("pram_conv2d_nhwc_x3_f32");
+    int mi, wn;
+    gemm::choose_tile(p.m, cout, &mi, &wn);
+    dispatch_tile(mi, wn, [&](auto MI, auto WN) {
+        const int tiles = set_tiles<gemmx3::Cfg<MI, WN>>(p, cout);
+        hipLaunchKernelGGL((conv_x3_kernel<MI, WN>), dim3(tiles), dim3(gemmx3::NT), 0, st, p, wh, wl, inv);
+    });
+    return pram_launch_status(who);
 }
 
 /* pram_conv2d_nhwc_x3_f32 followed by F.normalize over the channels of every output pixel (x / max(||x||, 1e-12)) in the same
@@ -978,27 +975,19 @@ extern "C" int pram_conv2d_nhwc_x3_f32(const float* in, int batch, int h, int w,
 extern "C" int pram_conv2d_nhwc_x3_l2norm_f32(const float* in, int batch, int h, int w, int cin, const void* wgt_hi, const void* wgt_lo,
                                               float w_scale, const float* bias, const float* scale, const float* shift,
                                               const float* residual, float* out, int cout, int ks, int stride, int relu, void* stream) {
-    PRAM_REQUIRE(in && wgt_hi && wgt_lo && out, "pram_conv2d_nhwc_x3_l2norm_f32: null pointer");
-    PRAM_REQUIRE(ks == 1 || ks == 3, "pram_conv2d_nhwc_x3_l2norm_f32: ks must be 1 or 3");
-    PRAM_REQUIRE((long long)h * w * cin < (1ll << 31), "pram_conv2d_nhwc_x3_l2norm_f32: an image of %d x %d x %d elements does not fit the 32-bit offsets of the im2col loader", h, w, cin);
-    PRAM_REQUIRE(stride == 1 || stride == 2, "pram_conv2d_nhwc_x3_l2norm_f32: stride must be 1 or 2");
-    PRAM_REQUIRE(cin % 32 == 0 && w_scale > 0.f, "pram_conv2d_nhwc_x3_l2norm_f32: cin=%d must be a multiple of 32", cin);
-    PRAM_REQUIRE(cout > 0 && cout <= 128, "pram_conv2d_nhwc_x3_l2norm_f32: cout=%d must be at most 128", cout);
-    PRAM_REQUIRE((scale == nullptr) == (shift == nullptr), "pram_conv2d_nhwc_x3_l2norm_f32: scale and shift go together");
+    const char* who = "pram_conv2d_nhwc_x3_l2norm_f32";
+    ConvArgs p{};
+    p.in = in; p.bias = bias; p.scale = scale; p.shift = shift; p.residual = residual; p.out = out;
+    p.batch = batch; p.h = h; p.wd = w; p.cin = cin; p.cout = cout; p.ks = ks; p.stride = stride; p.relu = relu;
+    if (int e = conv_args(who, p, CONV_X3, in && wgt_hi && wgt_lo && out, w_scale)) return e;
+    PRAM_REQUIRE(cout > 0 && cout <= 128, "%s: cout=%d must be at most 128", who, cout);
     if (batch == 0) return PRAM_OK;
-    const int pad = ks / 2;
-    ConvArgs p{in, nullptr, bias, scale, shift, residual, out, batch, h, w, cin, cout, ks, stride, relu};
-    p.ho = (h + 2 * pad - ks) / stride + 1;
-    p.wo = (w + 2 * pad - ks) / stride + 1;
-    p.m = batch * p.ho * p.wo;
-    p.k = ks * ks * cin;
-    p.status = pram_status_ptr();
-    p.act_scale = pram_act_scale();
+    const float inv = arm_split(p, w_scale);
     p.tiles_m = cdiv(p.m, gemmx3::Cfg<2, 2>::BM);
-    p.tiles_n = 1;
+    p.tiles_n = 1;      // one column tile holds the whole channel vector (cout <= 128 = BN)
     hipLaunchKernelGGL((conv_x3_kernel<2, 2, true>), dim3(p.tiles_m), dim3(gemmx3::NT), 0, (hipStream_t)stream, p, (const _Float16*)wgt_hi,
-                       (const _Float16*)wgt_lo, 1.0f / (pram_act_scale() * w_scale));
-    return pram_launch_status("pram_conv2d_nhwc_x3_l2norm_f32");
+                       (const _Float16*)wgt_lo, inv);
+    return pram_launch_status(who);
 }
 
 /* pram_conv2d_nhwc_x3_f32 with the result as the split operand of the next split-fp16 layer: out_hi = fp16(16 y),
@@ -1008,36 +997,22 @@ extern "C" int pram_conv2d_nhwc_x3_planes(const float* in, int batch, int h, int
                                           float w_scale, const float* bias, const float* scale, const float* shift,
                                           const float* residual, void* out_hi, void* out_lo, int cout, int ks, int stride, int relu,
                                           void* stream) {
-    PRAM_REQUIRE(in && wgt_hi && wgt_lo && out_hi && out_lo, "pram_conv2d_nhwc_x3_planes: null pointer");
-    PRAM_REQUIRE(ks == 1 || ks == 3, "pram_conv2d_nhwc_x3_planes: ks must be 1 or 3");
-    PRAM_REQUIRE((long long)h * w * cin < (1ll << 31), "pram_conv2d_nhwc_x3_planes: an image of %d x %d x %d elements does not fit the 32-bit offsets of the im2col loader", h, w, cin);
-    PRAM_REQUIRE(stride == 1 || stride == 2, "pram_conv2d_nhwc_x3_planes: stride must be 1 or 2");
-    PRAM_REQUIRE(cin % 32 == 0 && w_scale > 0.f, "pram_conv2d_nhwc_x3_planes: cin=%d must be a multiple of 32", cin);
-    PRAM_REQUIRE(cout > 0 && cout % 2 == 0, "pram_conv2d_nhwc_x3_planes: cout=%d must be even", cout);
-    PRAM_REQUIRE((scale == nullptr) == (shift == nullptr), "pram_conv2d_nhwc_x3_planes: scale and shift go together");
+    const char* who = "pram_conv2d_nhwc_x3_planes";
+    ConvArgs p{};
+    p.in = in; p.bias = bias; p.scale = scale; p.shift = shift; p.residual = residual;
+    p.batch = batch; p.h = h; p.wd = w; p.cin = cin; p.cout = cout; p.ks = ks; p.stride = stride; p.relu = relu;
+    if (int e = conv_args(who, p, CONV_X3, in && wgt_hi && wgt_lo && out_hi && out_lo, w_scale)) return e;
+    PRAM_REQUIRE(cout > 0 && cout % 2 == 0, "%s: cout=%d must be even", who, cout);
     if (batch == 0) return PRAM_OK;
-    const int pad = ks / 2;
-    ConvArgs p{in, nullptr, bias, scale, shift, residual, nullptr, batch, h, w, cin, cout, ks, stride, relu};
-    p.ho = (h + 2 * pad - ks) / stride + 1;
-    p.wo = (w + 2 * pad - ks) / stride + 1;
-    p.m = batch * p.ho * p.wo;
-    p.k = ks * ks * cin;
-    p.status = pram_status_ptr();
-    p.act_scale = pram_act_scale();
+    const float inv = arm_split(p, w_scale);
     p.out_hi = (_Float16*)out_hi;
     p.out_lo = (_Float16*)out_lo;
     using CW = gemmx3w::Cfg<4, 2, 4>;
     const size_t shm = sizeof(gemmx3w::Smem<4, 2, 4>);
-    static bool attr_set = false;
-    if (!attr_set) {
-        (void)hipFuncSetAttribute((const void*)conv_x3w_kernel<4, 2, 4, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
-        attr_set = true;
-    }
-    p.tiles_m = cdiv(p.m, CW::BM);
-    p.tiles_n = cdiv(cout, CW::BN);
-    hipLaunchKernelGGL((conv_x3w_kernel<4, 2, 4, true>), dim3(p.tiles_m * p.tiles_n), dim3(CW::NT), shm, (hipStream_t)stream, p,
-                       (const _Float16*)wgt_hi, (const _Float16*)wgt_lo, 1.0f / (pram_act_scale() * w_scale));
-    return pram_launch_status("pram_conv2d_nhwc_x3_planes");
+    opt_in_lds<conv_x3w_kernel<4, 2, 4, true>>(shm);
+    hipLaunchKernelGGL((conv_x3w_kernel<4, 2, 4, true>), dim3(set_tiles<CW>(p, cout)), dim3(CW::NT), shm, (hipStream_t)stream, p,
+                       (const _Float16*)wgt_hi, (const _Float16*)wgt_lo, inv);
+    return pram_launch_status(who);
 }
 
 extern "C" int pram_conv3x3_grouped_nhwc_f32(const float* in, int batch, int h, int w, int c, const float* wgt,
@@ -1294,11 +1269,7 @@ extern "C" int pram_conv3x3_grouped_planes_x3_f32(const void* in_hi, const void*
     if (batch == 0) return PRAM_OK;
     gx::Args p{(const _Float16*)in_hi, (const _Float16*)in_lo, out, (const _Float16*)w_hi, (const _Float16*)w_lo,
                1.0f / (pram_act_scale() * w_scale), scale, shift, batch, h, w, c, relu, cdiv(w, gx::TW), cdiv(h, gx::TH)};
-    static bool attr = false;
-    if (!attr) {
-        (void)hipFuncSetAttribute((const void*)gconv3x3_x3_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, gx::SMEM);
-        attr = true;
-    }
+    opt_in_lds<gconv3x3_x3_kernel>(gx::SMEM);
     const int nq = c / gx::CQ, ntiles = batch * p.tiles_x * p.tiles_y;
     const int per_q = min(ntiles, max(1, pram_cu_count() / nq));      // one resident workgroup per CU, each a (quarter, tile walk)
     hipLaunchKernelGGL(gconv3x3_x3_kernel, dim3(per_q * nq), dim3(gx::NT), gx::SMEM, (hipStream_t)stream, p);

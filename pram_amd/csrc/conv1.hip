@@ -18,6 +18,7 @@
 #include "gemm_core.h"
 #include "gemm_core_x3.h"
 #include "gemm_core_x3w.h"
+#include "launch.h"
 
 namespace {
 namespace c1 {
@@ -269,11 +270,7 @@ extern "C" int pram_sfd2_conv1_x3_f32(const float* img, int batch, int h, int w,
     p.abl = 0;
 #endif
     p.act_scale = pram_act_scale();
-    static bool attr = false;
-    if (!attr) {
-        (void)hipFuncSetAttribute((const void*)conv1ab_x3_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, c1::SMEM_BYTES);
-        attr = true;
-    }
+    opt_in_lds<conv1ab_x3_kernel>(c1::SMEM_BYTES);
     hipLaunchKernelGGL(conv1ab_x3_kernel, dim3(batch * p.tiles_x * p.tiles_y), dim3(c1::NT), c1::SMEM_BYTES, (hipStream_t)stream, p);
     return pram_launch_status("pram_sfd2_conv1_x3_f32");
 }

@@ -5,6 +5,7 @@
 #include "gemm_core_f16.h"
 #include "gemm_core_x3.h"
 #include "gemm_core_x3w.h"
+#include "launch.h"
 
 namespace {
 
@@ -857,12 +858,68 @@ __global__ void fourier_kernel(const float* __restrict__ kpts, const float* __re
     si[idx] = sinf(pr);
 }
 
-template <int MI, int WN, int BKT>
-void launch_linear_t(LinArgs& p, int batch, hipStream_t st) {
-    using C = gemm::Cfg<MI, WN, BKT>;
-    p.tiles_m = cdiv(p.m, C::BM);
-    p.tiles_n = cdiv(p.n, C::BN);
-    hipLaunchKernelGGL((linear_kernel<MI, WN, BKT>), dim3(p.tiles_m * p.tiles_n, batch), dim3(gemm::NT), 0, st, p);
+// ---------------------------------------------------------------- host side: argument structs, checks, launches
+// LinArgs is filled by name only (its layout is the kernels' business): one builder per concern, every field a builder does not
+// name stays zero / null / the default act_scale.
+LinArgs lin_a_f32(const float* a0, int lda0, int k0, const float* a1, int lda1, int k1) {
+    LinArgs p{};
+    p.a0 = a0; p.lda0 = lda0; p.k0 = k0;
+    p.a1 = a1; p.lda1 = lda1; p.k1 = k1;
+    return p;
+}
+// A as split planes: the pointers travel in PlaneArgs, LinArgs keeps the geometry
+LinArgs lin_a_planes(int lda0, int k0, int lda1, int k1) { return lin_a_f32(nullptr, lda0, k0, nullptr, lda1, k1); }
+void lin_out(LinArgs& p, const float* bias, const float* residual, int ldr, float* out, int ldo, int m, int n, float alpha) {
+    p.bias = bias; p.residual = residual; p.ldr = ldr; p.out = out; p.ldo = ldo; p.m = m; p.n = n; p.alpha = alpha;
+}
+void with_rotary(LinArgs& p, int flags, const float* rcos, const float* rsin, int cols) { p.flags = flags; p.rcos = rcos; p.rsin = rsin; p.rot_cols = cols; }
+void with_ragged(LinArgs& p, const int* lens, int t_pad) { p.lens = lens; p.t_pad = t_pad; }
+// the fp16 copy of the output (lo == nullptr) or its split planes
+void with_planes_out(LinArgs& p, void* hi, void* lo, int ldo16) { p.out16 = hi; p.out16_lo = lo; p.ldo16 = ldo16; }
+void with_batch_strides(LinArgs& p, long long sa, long long sw, long long so) { p.sa = sa; p.sw = sw; p.so = so; }
+// the eighteen arguments most entries share: fp32 A, bias / residual / out, rotary
+LinArgs lin_dense(const float* a0, int lda0, int k0, const float* a1, int lda1, int k1, const float* bias, const float* residual, int ldr,
+                  float* out, int ldo, int m, int n, float alpha, int flags, const float* rot_cos, const float* rot_sin, int rot_cols) {
+    LinArgs p = lin_a_f32(a0, lda0, k0, a1, lda1, k1);
+    lin_out(p, bias, residual, ldr, out, ldo, m, n, alpha);
+    with_rotary(p, flags, rot_cos, rot_sin, rot_cols);
+    return p;
+}
+// Arms the split-fp16 path from ONE read of the calling thread's activation scale: the range guard's status word, the scale of
+// the A planes and of the output planes.  Returns the scale: the caller's `inv` is 1 / (scale * the other operand's scale).
+float arm_split(LinArgs& p) {
+    p.status = pram_status_ptr();
+    return p.act_scale = p.out16_scale = pram_act_scale();
+}
+
+// What differs between the families' checks: K (k0 and k1 each when per_segment) % k_mult, lda % lda_mult, k0 % cat_mult for a
+// concatenated input (the second segment starts on a chunk boundary); split_out: the family writes split planes (hi and lo together).
+struct LinRules {
+    int k_mult, lda_mult, cat_mult;
+    bool per_segment, split_out, sizes_in_text;
+    const char* k_text; const char* cat_text;
+};
+constexpr LinRules X3_RULES{8, 4, gemmx3::BK, false, true, false, "K must be a multiple of 8, lda of 4", "concat needs k0 % 32 == 0"};
+constexpr LinRules X3P_RULES{32, 8, 32, true, true, false, "k0, k1 must be multiples of 32, lda of 8", "second segment needs both planes"};
+constexpr LinRules F16_RULES{8, 4, gemm16::BK, false, false, false, "K must be a multiple of 8, lda of 4", "concat needs k0 % 64 == 0"};
+constexpr LinRules F32_RULES{4, 4, 32, false, false, true, "K and lda must be multiples of 4", "concat needs k0 % 32 == 0"};
+
+// The checks the x3, x3p, f16 and f32 entries share, on the built arguments; ptrs_ok / have_a1 say whether the operands the
+// family needs are there (fp32 pointers or plane pairs).  Every message starts with the entry's own name.
+int lin_check(const char* who, const LinRules& r, const LinArgs& p, bool ptrs_ok, bool have_a1, float w_scale) {
+    PRAM_REQUIRE(ptrs_ok, "%s: null pointer", who);
+    PRAM_REQUIRE(!r.split_out || (p.out16 == nullptr) == (p.out16_lo == nullptr), "%s: the split output needs both planes", who);
+    if (r.sizes_in_text)
+        PRAM_REQUIRE(p.m >= 0 && p.n > 0 && p.k0 > 0 && p.k1 >= 0, "%s: bad sizes m=%d n=%d k0=%d k1=%d", who, p.m, p.n, p.k0, p.k1);
+    else
+        PRAM_REQUIRE(p.m >= 0 && p.n > 0 && p.k0 > 0 && p.k1 >= 0 && w_scale > 0.f, "%s: bad sizes", who);
+    PRAM_REQUIRE((r.per_segment ? p.k0 % r.k_mult == 0 && p.k1 % r.k_mult == 0 : (p.k0 + p.k1) % r.k_mult == 0) && p.lda0 % r.lda_mult == 0,
+                 "%s: %s", who, r.k_text);
+    PRAM_REQUIRE(p.k1 == 0 || (have_a1 && p.k0 % r.cat_mult == 0 && p.lda1 % r.lda_mult == 0), "%s: %s", who, r.cat_text);
+    if (p.flags & PRAM_LIN_ROTARY)
+        PRAM_REQUIRE(p.rcos && p.rsin && p.rot_cols % 64 == 0, "%s: rotary needs cos/sin and rot_cols %% 64 == 0", who);
+    PRAM_REQUIRE(!p.lens || p.t_pad > 0, "%s: lens needs t_pad > 0", who);
+    return PRAM_OK;
 }
 
 // Full grids (>= 512 tiles) take the 16-deep chunk (three workgroups per CU); small ones are latency-bound per
@@ -870,63 +927,45 @@ void launch_linear_t(LinArgs& p, int batch, hipStream_t st) {
 void launch_linear(LinArgs& p, int batch, hipStream_t st) {
     int mi, wn;
     gemm::choose_tile(p.m * batch, p.n, &mi, &wn);
-    if (wn == 2) { if (mi == 2) launch_linear_t<2, 2, 16>(p, batch, st); else launch_linear_t<1, 2, 32>(p, batch, st); }
-    else         { if (mi == 2) launch_linear_t<2, 1, 16>(p, batch, st); else launch_linear_t<1, 1, 32>(p, batch, st); }
-}
-
-template <int MI, int WN>
-void launch_linear_f16_t(LinArgs& p, const _Float16* w16, hipStream_t st) {
-    using C = gemm16::Cfg<MI, WN>;
-    p.tiles_m = cdiv(p.m, C::BM);
-    p.tiles_n = cdiv(p.n, C::BN);
-    hipLaunchKernelGGL((linear_f16_kernel<MI, WN>), dim3(p.tiles_m * p.tiles_n, 1), dim3(gemm16::NT), 0, st, p, w16);
+    dispatch_tile(mi, wn, [&](auto MI, auto WN) {
+        constexpr int BKT = MI == 2 ? 16 : 32;
+        hipLaunchKernelGGL((linear_kernel<MI, WN, BKT>), dim3(set_tiles<gemm::Cfg<MI, WN, BKT>>(p, p.n), batch), dim3(gemm::NT), 0, st, p);
+    });
 }
 
 template <int MI, int WN>
 void launch_linear_x3_t(LinArgs& p, const _Float16* wh, const _Float16* wl, float inv, hipStream_t st) {
-    using C = gemmx3::Cfg<MI, WN>;
-    p.tiles_m = cdiv(p.m, C::BM);
-    p.tiles_n = cdiv(p.n, C::BN);
+    const int tiles = set_tiles<gemmx3::Cfg<MI, WN>>(p, p.n);
     if constexpr (WN == 2) {      // the LayerNorm + GELU operand transform exists for outputs wider than 64 columns (pram_linear_x3_lngelu_f32 checks)
         if (p.ln_ssq) {
-            hipLaunchKernelGGL((linear_x3_kernel<MI, WN, true>), dim3(p.tiles_m * p.tiles_n, 1), dim3(gemmx3::NT), 0, st, p, wh, wl, inv);
+            hipLaunchKernelGGL((linear_x3_kernel<MI, WN, true>), dim3(tiles, 1), dim3(gemmx3::NT), 0, st, p, wh, wl, inv);
             return;
         }
     }
-    hipLaunchKernelGGL((linear_x3_kernel<MI, WN>), dim3(p.tiles_m * p.tiles_n, 1), dim3(gemmx3::NT), 0, st, p, wh, wl, inv);
+    hipLaunchKernelGGL((linear_x3_kernel<MI, WN>), dim3(tiles, 1), dim3(gemmx3::NT), 0, st, p, wh, wl, inv);
 }
 
 template <int MI, int WM, int WN, bool APLANES>
 void launch_linear_x3w_t(LinArgs& p, PlaneArgs& a, const _Float16* wh, const _Float16* wl, float inv, hipStream_t st, int batch = 1) {
     using C = gemmx3w::Cfg<MI, WM, WN>;
-    p.tiles_m = cdiv(p.m, C::BM);
-    p.tiles_n = cdiv(p.n, C::BN);
+    const dim3 grid(set_tiles<C>(p, p.n), batch), blk(C::NT);
     const size_t shm = sizeof(gemmx3w::Smem<MI, WM, WN>);
-    static bool attr_set = false;      // > 64 KB of dynamic LDS needs the opt-in once per kernel
-    if (!attr_set) {
-        (void)hipFuncSetAttribute((const void*)linear_x3w_kernel<MI, WM, WN, APLANES>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
-        attr_set = true;
-    }
+    opt_in_lds<linear_x3w_kernel<MI, WM, WN, APLANES>>(shm);
     if constexpr (!APLANES) {
         if (p.ln_ssq) {      // A = GELU(LayerNorm(hidden)) applied while staged: gamma | beta ride behind the stages
             const size_t shm_ln = shm + 2 * (size_t)(p.k0 + p.k1) * sizeof(float);
-            static bool ln_attr_set = false;
-            if (!ln_attr_set) {
-                (void)hipFuncSetAttribute((const void*)linear_x3w_kernel<MI, WM, WN, false, 0, 1, true>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                          (int)(shm + 2 * 1024 * sizeof(float)));
-                ln_attr_set = true;
-            }
-            hipLaunchKernelGGL((linear_x3w_kernel<MI, WM, WN, false, 0, 1, true>), dim3(p.tiles_m * p.tiles_n, batch), dim3(C::NT), shm_ln, st, p, a, wh, wl, inv);
+            opt_in_lds<linear_x3w_kernel<MI, WM, WN, false, 0, 1, true>>(shm + 2 * 1024 * sizeof(float));      // the ceiling: K <= 1024
+            hipLaunchKernelGGL((linear_x3w_kernel<MI, WM, WN, false, 0, 1, true>), grid, blk, shm_ln, st, p, a, wh, wl, inv);
             return;
         }
     }
 #ifdef PRAM_PROFILING      // ablations (garbage results, PRAM_OK): profiling builds only (build_variants.py TAG:linear.hip:-DPRAM_PROFILING)
     static const char* abl = getenv("PRAM_GEMM_ABLATE");
     const int ab = abl ? atoi(abl) : 0;
-    if (ab == 0) { hipLaunchKernelGGL((linear_x3w_kernel<MI, WM, WN, APLANES>), dim3(p.tiles_m * p.tiles_n, batch), dim3(C::NT), shm, st, p, a, wh, wl, inv); return; }
+    if (ab == 0) { hipLaunchKernelGGL((linear_x3w_kernel<MI, WM, WN, APLANES>), grid, blk, shm, st, p, a, wh, wl, inv); return; }
     auto go = [&](auto kern) {
         (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
-        hipLaunchKernelGGL(kern, dim3(p.tiles_m * p.tiles_n, batch), dim3(C::NT), shm, st, p, a, wh, wl, inv);
+        hipLaunchKernelGGL(kern, grid, blk, shm, st, p, a, wh, wl, inv);
     };
     if (ab == 8) go(linear_x3w_kernel<MI, WM, WN, APLANES, 0, 0>);       // register staging for both operands (no LDS-DMA)
     else if (ab == 1) go(linear_x3w_kernel<MI, WM, WN, APLANES, 1>);      // no staging after the first chunk
@@ -940,7 +979,7 @@ void launch_linear_x3w_t(LinArgs& p, PlaneArgs& a, const _Float16* wh, const _Fl
     else if (ab == 256) go(linear_x3w_kernel<MI, WM, WN, APLANES, 256>);  // odd workgroups of the first round walk half their chunks: do de-synchronised CUs overlap store bursts with main loops?
     else go(linear_x3w_kernel<MI, WM, WN, APLANES, 3>);
 #else
-    hipLaunchKernelGGL((linear_x3w_kernel<MI, WM, WN, APLANES>), dim3(p.tiles_m * p.tiles_n, batch), dim3(C::NT), shm, st, p, a, wh, wl, inv);
+    hipLaunchKernelGGL((linear_x3w_kernel<MI, WM, WN, APLANES>), grid, blk, shm, st, p, a, wh, wl, inv);
 #endif
 }
 
@@ -967,12 +1006,20 @@ bool launch_linear_x3_wide(LinArgs& p, PlaneArgs& a, const _Float16* wh, const _
     return true;
 }
 
-template <int MI, int WN>
-void launch_linear_x3p_t(LinArgs& p, PlaneArgs& a, const _Float16* wh, const _Float16* wl, float inv, hipStream_t st, int batch = 1) {
-    using C = gemmx3::Cfg<MI, WN>;
-    p.tiles_m = cdiv(p.m, C::BM);
-    p.tiles_n = cdiv(p.n, C::BN);
-    hipLaunchKernelGGL((linear_x3p_kernel<MI, WN>), dim3(p.tiles_m * p.tiles_n, batch), dim3(gemmx3::NT), 0, st, p, a, wh, wl, inv);
+// split-fp16 GEMM, A as fp32 (a: all null) or as split planes: the wide tiles where they pay, the choose_tile ladder otherwise
+template <bool APLANES>
+void launch_linear_split(LinArgs& p, PlaneArgs& a, const void* w_hi, const void* w_lo, float inv, hipStream_t st, int batch = 1) {
+    const _Float16* wh = (const _Float16*)w_hi;
+    const _Float16* wl = (const _Float16*)w_lo;
+    if (launch_linear_x3_wide<APLANES>(p, a, wh, wl, inv, st, batch)) return;
+    int mi, wn;
+    gemm::choose_tile(p.m, p.n, &mi, &wn);
+    dispatch_tile(mi, wn, [&](auto MI, auto WN) {
+        if constexpr (APLANES)
+            hipLaunchKernelGGL((linear_x3p_kernel<MI, WN>), dim3(set_tiles<gemmx3::Cfg<MI, WN>>(p, p.n), batch), dim3(gemmx3::NT), 0, st, p, a, wh, wl, inv);
+        else
+            launch_linear_x3_t<MI, WN>(p, wh, wl, inv, st);
+    });
 }
 
 }  // namespace
@@ -985,29 +1032,17 @@ extern "C" int pram_linear_x3p_f32(const void* a0_hi, const void* a0_lo, int lda
                                    const float* residual, int ldr, float* out, int ldo, void* out_hi, void* out_lo, int ldo16,
                                    int m, int n, float alpha, int flags, const float* rot_cos, const float* rot_sin, int rot_cols,
                                    void* stream) {
-    PRAM_REQUIRE(a0_hi && a0_lo && w_hi && w_lo && (out || (out_hi && out_lo)), "pram_linear_x3p_f32: null pointer");
-    PRAM_REQUIRE((out_hi == nullptr) == (out_lo == nullptr), "pram_linear_x3p_f32: the split output needs both planes");
-    PRAM_REQUIRE(m >= 0 && n > 0 && k0 > 0 && k1 >= 0 && w_scale > 0.f, "pram_linear_x3p_f32: bad sizes");
-    PRAM_REQUIRE(k0 % 32 == 0 && k1 % 32 == 0 && lda0 % 8 == 0, "pram_linear_x3p_f32: k0, k1 must be multiples of 32, lda of 8");
-    PRAM_REQUIRE(k1 == 0 || (a1_hi && a1_lo && lda1 % 8 == 0), "pram_linear_x3p_f32: second segment needs both planes");
-    if (flags & PRAM_LIN_ROTARY)
-        PRAM_REQUIRE(rot_cos && rot_sin && rot_cols % 64 == 0, "pram_linear_x3p_f32: rotary needs cos/sin and rot_cols %% 64 == 0");
+    const char* who = "pram_linear_x3p_f32";
+    LinArgs p = lin_a_planes(lda0, k0, lda1, k1);
+    lin_out(p, bias, residual, ldr, out, ldo, m, n, alpha);
+    with_rotary(p, flags, rot_cos, rot_sin, rot_cols);
+    with_planes_out(p, out_hi, out_lo, ldo16);
+    if (int e = lin_check(who, X3P_RULES, p, a0_hi && a0_lo && w_hi && w_lo && (out || (out_hi && out_lo)), a1_hi && a1_lo, w_scale)) return e;
     if (m == 0) return PRAM_OK;
-    LinArgs p{nullptr, lda0, k0, nullptr, lda1, k1, nullptr, bias, residual, ldr, out, ldo, m, n, alpha, flags,
-              rot_cos, rot_sin, rot_cols, 0, 0, 0, 0, 0, out_hi, ldo16, out_lo, pram_act_scale()};
     PlaneArgs a{(const _Float16*)a0_hi, (const _Float16*)a0_lo, lda0, (const _Float16*)a1_hi, (const _Float16*)a1_lo, lda1};
-    p.status = pram_status_ptr();
-    p.act_scale = pram_act_scale();
-    int mi, wn;
-    gemm::choose_tile(m, n, &mi, &wn);
-    hipStream_t st = (hipStream_t)stream;
-    const _Float16* wh = (const _Float16*)w_hi;
-    const _Float16* wl = (const _Float16*)w_lo;
-    const float inv = 1.0f / (pram_act_scale() * w_scale);
-    if (launch_linear_x3_wide<true>(p, a, wh, wl, inv, st)) return pram_launch_status("pram_linear_x3p_f32");
-    if (wn == 2) { if (mi == 2) launch_linear_x3p_t<2, 2>(p, a, wh, wl, inv, st); else launch_linear_x3p_t<1, 2>(p, a, wh, wl, inv, st); }
-    else         { if (mi == 2) launch_linear_x3p_t<2, 1>(p, a, wh, wl, inv, st); else launch_linear_x3p_t<1, 1>(p, a, wh, wl, inv, st); }
-    return pram_launch_status("pram_linear_x3p_f32");
+    const float inv = 1.0f / (arm_split(p) * w_scale);
+    launch_linear_split<true>(p, a, w_hi, w_lo, inv, (hipStream_t)stream);
+    return pram_launch_status(who);
 }
 
 /* Profiling aid: the per-phase shader-clock totals the wide split-fp16 GEMM accumulates when PRAM_GEMM_ABLATE=4 (see
@@ -1022,68 +1057,38 @@ extern "C" int pram_debug_gemm_phases(unsigned long long* out72, int reset) {
     return PRAM_OK;
 }
 
-struct VtOut { void* hi; void* lo; int col0, heads, t_seq; };
-// LayerNorm coupling of an MLP tail's two GEMMs (LinArgs::row_ssq / ln_*): ssq_out for the first, the rest for the second
-struct LnIo { float* ssq_out; const float* ssq_in; int parts; const float* gamma; const float* beta; float eps; };
-
 // partials per row the first GEMM of an MLP tail writes: one per 64-column block of its output (pram_linear_x3_ssq_parts)
 static int x3_ssq_parts(int n) { return cdiv(n, 64); }
 
-static int linear_x3_impl(const LnIo* ln, const VtOut* vt, const int* lens, int t_pad, const float* a0, int lda0, int k0, const float* a1, int lda1, int k1, const void* w_hi,
-                                  const void* w_lo, float w_scale, const float* bias, const float* residual, int ldr,
-                                  float* out, int ldo, void* out_hi, void* out_lo, int ldo16, int m, int n, float alpha,
-                                  int flags, const float* rot_cos, const float* rot_sin, int rot_cols, void* stream) {
-    PRAM_REQUIRE(a0 && w_hi && w_lo && (out || (out_hi && out_lo)), "pram_linear_x3_f32: null pointer");
-    PRAM_REQUIRE((out_hi == nullptr) == (out_lo == nullptr), "pram_linear_x3_f32: the split output needs both planes");
-    PRAM_REQUIRE(m >= 0 && n > 0 && k0 > 0 && k1 >= 0 && w_scale > 0.f, "pram_linear_x3_f32: bad sizes");
-    PRAM_REQUIRE((k0 + k1) % 8 == 0 && lda0 % 4 == 0, "pram_linear_x3_f32: K must be a multiple of 8, lda of 4");
-    PRAM_REQUIRE(k1 == 0 || (a1 && k0 % gemmx3::BK == 0 && lda1 % 4 == 0), "pram_linear_x3_f32: concat needs k0 %% 32 == 0");
-    if (flags & PRAM_LIN_ROTARY)
-        PRAM_REQUIRE(rot_cos && rot_sin && rot_cols % 64 == 0, "pram_linear_x3_f32: rotary needs cos/sin and rot_cols %% 64 == 0");
-    if (m == 0) return PRAM_OK;
-    LinArgs p{a0, lda0, k0, a1, lda1, k1, nullptr, bias, residual, ldr, out, ldo, m, n, alpha, flags,
-              rot_cos, rot_sin, rot_cols, 0, 0, 0, 0, 0, out_hi, ldo16, out_lo, pram_act_scale(), lens, t_pad};
-    PRAM_REQUIRE(!lens || t_pad > 0, "pram_linear_x3_f32: lens needs t_pad > 0");
-    p.status = pram_status_ptr();
-    p.act_scale = pram_act_scale();
-    if (ln) {
-        PRAM_REQUIRE(!(ln->ssq_out && (out_hi || vt)), "pram_linear_x3_ssq_f32: row sums go with an fp32 output");
-        p.row_ssq = ln->ssq_out;
-        if (ln->ssq_in) {
-            PRAM_REQUIRE(ln->gamma && ln->beta && ln->parts > 0 && k1 == 0 && k0 % 32 == 0 && k0 <= 1024,
-                         "pram_linear_x3_lngelu_f32: needs gamma / beta / parts, one input segment, K %% 32 == 0, K <= 1024");
-            p.ln_ssq = ln->ssq_in; p.ln_parts = ln->parts; p.ln_gamma = ln->gamma; p.ln_beta = ln->beta; p.ln_eps = ln->eps;
-        }
+// The five fp32-A split-fp16 entries: p carries everything the calling entry `who` was given, the LayerNorm coupling of an MLP
+// tail (row_ssq: first GEMM; ln_*: second) and, with qkv, the transposed value planes (vt_*) included.
+static int linear_x3_impl(const char* who, LinArgs& p, bool qkv, const void* w_hi, const void* w_lo, float w_scale, void* stream) {
+    if (int e = lin_check(who, X3_RULES, p, p.a0 && w_hi && w_lo && (p.out || (p.out16 && p.out16_lo)), p.a1 != nullptr, w_scale)) return e;
+    PRAM_REQUIRE(!(p.row_ssq && (p.out16 || qkv)), "%s: row sums go with an fp32 output", who);
+    if (p.ln_ssq)
+        PRAM_REQUIRE(p.ln_gamma && p.ln_beta && p.ln_parts > 0 && p.k1 == 0 && p.k0 % 32 == 0 && p.k0 <= 1024,
+                     "%s: needs gamma / beta / parts, one input segment, K %% 32 == 0, K <= 1024", who);
+    if (qkv) {
+        PRAM_REQUIRE(p.vt_hi && p.vt_lo && p.out16 && p.out16_lo, "%s: null pointer", who);
+        PRAM_REQUIRE(p.vt_t > 0 && p.vt_t % 64 == 0 && p.m % p.vt_t == 0 && (!p.lens || p.t_pad == p.vt_t),
+                     "%s: sequences must be a multiple of 64 tokens long (and t_pad == t_seq)", who);
+        PRAM_REQUIRE(p.vt_heads > 0 && p.vt_col0 % 64 == 0 && p.n == p.vt_col0 + p.vt_heads * 64 && p.ldo16 >= p.vt_col0,
+                     "%s: the value heads must be the last heads * 64 columns", who);
     }
-    if (vt) {
-        PRAM_REQUIRE(vt->hi && vt->lo && out_hi && out_lo, "pram_linear_x3_qkv_f32: null pointer");
-        PRAM_REQUIRE(vt->t_seq > 0 && vt->t_seq % 64 == 0 && m % vt->t_seq == 0 && (!lens || t_pad == vt->t_seq),
-                     "pram_linear_x3_qkv_f32: sequences must be a multiple of 64 tokens long (and t_pad == t_seq)");
-        PRAM_REQUIRE(vt->heads > 0 && vt->col0 % 64 == 0 && n == vt->col0 + vt->heads * 64 && ldo16 >= vt->col0,
-                     "pram_linear_x3_qkv_f32: the value heads must be the last heads * 64 columns");
-        p.vt_hi = vt->hi; p.vt_lo = vt->lo; p.vt_col0 = vt->col0; p.vt_heads = vt->heads; p.vt_t = vt->t_seq; p.vt_tv = vt->t_seq;
-    }
-    int mi, wn;
-    gemm::choose_tile(m, n, &mi, &wn);
-    hipStream_t st = (hipStream_t)stream;
-    const _Float16* wh = (const _Float16*)w_hi;
-    const _Float16* wl = (const _Float16*)w_lo;
-    const float inv = 1.0f / (pram_act_scale() * w_scale);
-    {
-        PlaneArgs none{nullptr, nullptr, 0, nullptr, nullptr, 0};
-        if (launch_linear_x3_wide<false>(p, none, wh, wl, inv, st)) return pram_launch_status("pram_linear_x3_f32");
-    }
-    if (wn == 2) { if (mi == 2) launch_linear_x3_t<2, 2>(p, wh, wl, inv, st); else launch_linear_x3_t<1, 2>(p, wh, wl, inv, st); }
-    else         { if (mi == 2) launch_linear_x3_t<2, 1>(p, wh, wl, inv, st); else launch_linear_x3_t<1, 1>(p, wh, wl, inv, st); }
-    return pram_launch_status("pram_linear_x3_f32");
+    if (p.m == 0) return PRAM_OK;
+    const float inv = 1.0f / (arm_split(p) * w_scale);
+    PlaneArgs none{nullptr, nullptr, 0, nullptr, nullptr, 0};
+    launch_linear_split<false>(p, none, w_hi, w_lo, inv, (hipStream_t)stream);
+    return pram_launch_status(who);
 }
 
 extern "C" int pram_linear_x3_f32(const float* a0, int lda0, int k0, const float* a1, int lda1, int k1, const void* w_hi,
                                   const void* w_lo, float w_scale, const float* bias, const float* residual, int ldr,
                                   float* out, int ldo, void* out_hi, void* out_lo, int ldo16, int m, int n, float alpha,
                                   int flags, const float* rot_cos, const float* rot_sin, int rot_cols, void* stream) {
-    return linear_x3_impl(nullptr, nullptr, nullptr, 0, a0, lda0, k0, a1, lda1, k1, w_hi, w_lo, w_scale, bias, residual, ldr, out, ldo, out_hi, out_lo, ldo16,
-                          m, n, alpha, flags, rot_cos, rot_sin, rot_cols, stream);
+    LinArgs p = lin_dense(a0, lda0, k0, a1, lda1, k1, bias, residual, ldr, out, ldo, m, n, alpha, flags, rot_cos, rot_sin, rot_cols);
+    with_planes_out(p, out_hi, out_lo, ldo16);
+    return linear_x3_impl("pram_linear_x3_f32", p, false, w_hi, w_lo, w_scale, stream);
 }
 
 /* pram_linear_x3_f32 on a ragged token matrix: rows are sequences of t_pad rows, sequence s has lens[s] (device int32) valid
@@ -1093,8 +1098,10 @@ extern "C" int pram_linear_x3_ragged_f32(const float* a0, int lda0, int k0, cons
                                          float* out, int ldo, void* out_hi, void* out_lo, int ldo16, int m, int n, float alpha,
                                          int flags, const float* rot_cos, const float* rot_sin, int rot_cols, const int* lens,
                                          int t_pad, void* stream) {
-    return linear_x3_impl(nullptr, nullptr, lens, t_pad, a0, lda0, k0, a1, lda1, k1, w_hi, w_lo, w_scale, bias, residual, ldr, out, ldo, out_hi, out_lo, ldo16,
-                          m, n, alpha, flags, rot_cos, rot_sin, rot_cols, stream);
+    LinArgs p = lin_dense(a0, lda0, k0, a1, lda1, k1, bias, residual, ldr, out, ldo, m, n, alpha, flags, rot_cos, rot_sin, rot_cols);
+    with_planes_out(p, out_hi, out_lo, ldo16);
+    with_ragged(p, lens, t_pad);
+    return linear_x3_impl("pram_linear_x3_ragged_f32", p, false, w_hi, w_lo, w_scale, stream);
 }
 
 /* MLP tail, first GEMM (nets/segnetvit.py:87-95 mlp.0; nets/gml.py:118-126; the seg head segnetvit.py:157-164): pram_linear_x3_ragged_f32
@@ -1108,9 +1115,11 @@ extern "C" int pram_linear_x3_ssq_f32(const float* a0, int lda0, int k0, const f
                                       float w_scale, const float* bias, float* out, int ldo, float* row_ssq, int m, int n,
                                       const int* lens, int t_pad, void* stream) {
     PRAM_REQUIRE(row_ssq && out, "pram_linear_x3_ssq_f32: null pointer");
-    LnIo ln{row_ssq, nullptr, 0, nullptr, nullptr, 0.f};
-    return linear_x3_impl(&ln, nullptr, lens, t_pad, a0, lda0, k0, a1, lda1, k1, w_hi, w_lo, w_scale, bias, nullptr, 0, out, ldo, nullptr, nullptr, 0,
-                          m, n, 1.0f, 0, nullptr, nullptr, 0, stream);
+    LinArgs p = lin_a_f32(a0, lda0, k0, a1, lda1, k1);
+    lin_out(p, bias, nullptr, 0, out, ldo, m, n, 1.0f);
+    with_ragged(p, lens, t_pad);
+    p.row_ssq = row_ssq;
+    return linear_x3_impl("pram_linear_x3_ssq_f32", p, false, w_hi, w_lo, w_scale, stream);
 }
 
 /* MLP tail, second GEMM: out = GELU(LayerNorm(hidden)) w^T + bias + residual with the LayerNorm + GELU (nn.LayerNorm + nn.GELU of
@@ -1122,9 +1131,11 @@ extern "C" int pram_linear_x3_lngelu_f32(const float* hidden, int ldh, int k, co
                                          const float* gamma, const float* beta, float eps, const int* lens, int t_pad, void* stream) {
     PRAM_REQUIRE(ln_ssq && out, "pram_linear_x3_lngelu_f32: null pointer");
     PRAM_REQUIRE(n > 64, "pram_linear_x3_lngelu_f32: n = %d must exceed 64 (narrower outputs: pram_layernorm_gelu_f32 + pram_linear_x3_f32)", n);
-    LnIo ln{nullptr, ln_ssq, parts, gamma, beta, eps};
-    return linear_x3_impl(&ln, nullptr, lens, t_pad, hidden, ldh, k, nullptr, 0, 0, w_hi, w_lo, w_scale, bias, residual, ldr, out, ldo, nullptr, nullptr, 0,
-                          m, n, 1.0f, 0, nullptr, nullptr, 0, stream);
+    LinArgs p = lin_a_f32(hidden, ldh, k, nullptr, 0, 0);
+    lin_out(p, bias, residual, ldr, out, ldo, m, n, 1.0f);
+    with_ragged(p, lens, t_pad);
+    p.ln_ssq = ln_ssq; p.ln_parts = parts; p.ln_gamma = gamma; p.ln_beta = beta; p.ln_eps = eps;
+    return linear_x3_impl("pram_linear_x3_lngelu_f32", p, false, w_hi, w_lo, w_scale, stream);
 }
 
 /* The q | k | v projection of an attention block in one call (nets/segnetvit.py:87-95, nets/gml.py:151-159): columns
@@ -1135,31 +1146,27 @@ extern "C" int pram_linear_x3_qkv_f32(const float* a0, int lda0, int k0, const v
                                       const float* bias, void* out_hi, void* out_lo, int ldo16, void* vt_hi, void* vt_lo, int vt_col0,
                                       int heads, int t_seq, int m, int n, int flags, const float* rot_cos, const float* rot_sin,
                                       int rot_cols, const int* lens, void* stream) {
-    VtOut vt{vt_hi, vt_lo, vt_col0, heads, t_seq};
-    return linear_x3_impl(nullptr, &vt, lens, lens ? t_seq : 0, a0, lda0, k0, nullptr, 0, 0, w_hi, w_lo, w_scale, bias, nullptr, 0, nullptr, 0, out_hi,
-                          out_lo, ldo16, m, n, 1.0f, flags, rot_cos, rot_sin, rot_cols, stream);
+    LinArgs p = lin_dense(a0, lda0, k0, nullptr, 0, 0, bias, nullptr, 0, nullptr, 0, m, n, 1.0f, flags, rot_cos, rot_sin, rot_cols);
+    with_planes_out(p, out_hi, out_lo, ldo16);
+    with_ragged(p, lens, lens ? t_seq : 0);
+    p.vt_hi = vt_hi; p.vt_lo = vt_lo; p.vt_col0 = vt_col0; p.vt_heads = heads; p.vt_t = p.vt_tv = t_seq;
+    return linear_x3_impl("pram_linear_x3_qkv_f32", p, true, w_hi, w_lo, w_scale, stream);
 }
 
-static int linear_f16_f32_impl(const char* who, const int* lens, int t_pad, const float* a0, int lda0, int k0, const float* a1, int lda1, int k1,
-                               const void* w16, const float* bias, const float* residual, int ldr, float* out, int ldo, int m, int n,
-                               float alpha, int flags, const float* rot_cos, const float* rot_sin, int rot_cols, void* stream) {
-    PRAM_REQUIRE(a0 && w16 && out, "%s: null pointer", who);
-    PRAM_REQUIRE(m >= 0 && n > 0 && k0 > 0 && k1 >= 0, "%s: bad sizes", who);
-    PRAM_REQUIRE((k0 + k1) % 8 == 0 && lda0 % 4 == 0, "%s: K must be a multiple of 8, lda of 4", who);
-    PRAM_REQUIRE(k1 == 0 || (a1 && k0 % gemm16::BK == 0 && lda1 % 4 == 0), "%s: concat needs k0 %% 64 == 0", who);
-    if (flags & PRAM_LIN_ROTARY)
-        PRAM_REQUIRE(rot_cos && rot_sin && rot_cols % 64 == 0, "%s: rotary needs cos/sin and rot_cols %% 64 == 0", who);
-    if (m == 0) return PRAM_OK;
-    LinArgs p{a0, lda0, k0, a1, lda1, k1, nullptr, bias, residual, ldr, out, ldo, m, n, alpha, flags,
-              rot_cos, rot_sin, rot_cols, 0, 0, 0, 0, 0};
-    p.lens = lens;
-    p.t_pad = t_pad;
+static void launch_linear_f16(LinArgs& p, const _Float16* w16, hipStream_t st) {
     int mi, wn;
-    gemm::choose_tile(m, n, &mi, &wn);
-    hipStream_t st = (hipStream_t)stream;
-    const _Float16* w = (const _Float16*)w16;
-    if (wn == 2) { if (mi == 2) launch_linear_f16_t<2, 2>(p, w, st); else launch_linear_f16_t<1, 2>(p, w, st); }
-    else launch_linear_f16_t<1, 1>(p, w, st);      // 128-row tiles for narrow outputs: the 256-row instantiation spills (43 registers) on this path
+    gemm::choose_tile(p.m, p.n, &mi, &wn);
+    dispatch_tile(mi, wn, [&](auto MI_, auto WN) {
+        constexpr int MI = WN == 1 ? 1 : MI_;      // 128-row tiles for narrow outputs: the 256-row instantiation spills (43 registers) on this path
+        hipLaunchKernelGGL((linear_f16_kernel<MI, WN>), dim3(set_tiles<gemm16::Cfg<MI, WN>>(p, p.n), 1), dim3(gemm16::NT), 0, st, p, w16);
+    });
+}
+
+// The three single-product fp16 entries; out16 (pram_linear_f16_h16) makes the fp32 output optional.
+static int linear_f16_f32_impl(const char* who, LinArgs& p, const void* w16, void* stream) {
+    if (int e = lin_check(who, F16_RULES, p, p.a0 && w16 && (p.out || p.out16), p.a1 != nullptr, 1.0f)) return e;
+    if (p.m == 0) return PRAM_OK;
+    launch_linear_f16(p, (const _Float16*)w16, (hipStream_t)stream);
     return pram_launch_status(who);
 }
 
@@ -1167,8 +1174,8 @@ extern "C" int pram_linear_f16_f32(const float* a0, int lda0, int k0, const floa
                                    const float* bias, const float* residual, int ldr, float* out, int ldo, int m, int n,
                                    float alpha, int flags, const float* rot_cos, const float* rot_sin, int rot_cols,
                                    void* stream) {
-    return linear_f16_f32_impl("pram_linear_f16_f32", nullptr, 0, a0, lda0, k0, a1, lda1, k1, w16, bias, residual, ldr, out, ldo, m, n, alpha, flags,
-                               rot_cos, rot_sin, rot_cols, stream);
+    LinArgs p = lin_dense(a0, lda0, k0, a1, lda1, k1, bias, residual, ldr, out, ldo, m, n, alpha, flags, rot_cos, rot_sin, rot_cols);
+    return linear_f16_f32_impl("pram_linear_f16_f32", p, w16, stream);
 }
 
 /* pram_linear_f16_f32 on a ragged token matrix (as pram_linear_x3_ragged_f32 / pram_linear_ragged_f32): rows are sequences of
@@ -1178,67 +1185,44 @@ extern "C" int pram_linear_f16_ragged_f32(const float* a0, int lda0, int k0, con
                                           const float* bias, const float* residual, int ldr, float* out, int ldo, int m, int n,
                                           float alpha, int flags, const float* rot_cos, const float* rot_sin, int rot_cols,
                                           const int* lens, int t_pad, void* stream) {
-    PRAM_REQUIRE(!lens || t_pad > 0, "pram_linear_f16_ragged_f32: lens needs t_pad > 0");
-    return linear_f16_f32_impl("pram_linear_f16_ragged_f32", lens, t_pad, a0, lda0, k0, a1, lda1, k1, w16, bias, residual, ldr, out, ldo, m, n, alpha,
-                               flags, rot_cos, rot_sin, rot_cols, stream);
+    LinArgs p = lin_dense(a0, lda0, k0, a1, lda1, k1, bias, residual, ldr, out, ldo, m, n, alpha, flags, rot_cos, rot_sin, rot_cols);
+    with_ragged(p, lens, t_pad);
+    return linear_f16_f32_impl("pram_linear_f16_ragged_f32", p, w16, stream);
 }
 
 extern "C" int pram_linear_f16_h16(const float* a0, int lda0, int k0, const float* a1, int lda1, int k1, const void* w16,
                                    const float* bias, const float* residual, int ldr, float* out, int ldo, void* out16,
                                    int ldo16, int m, int n, float alpha, int flags, const float* rot_cos,
                                    const float* rot_sin, int rot_cols, void* stream) {
-    PRAM_REQUIRE(a0 && w16 && out16, "pram_linear_f16_h16: null pointer");
-    PRAM_REQUIRE(m >= 0 && n > 0 && k0 > 0 && k1 >= 0, "pram_linear_f16_h16: bad sizes");
-    PRAM_REQUIRE((k0 + k1) % 8 == 0 && lda0 % 4 == 0, "pram_linear_f16_h16: K must be a multiple of 8, lda of 4");
-    PRAM_REQUIRE(k1 == 0 || (a1 && k0 % gemm16::BK == 0 && lda1 % 4 == 0), "pram_linear_f16_h16: concat needs k0 %% 64 == 0");
-    if (flags & PRAM_LIN_ROTARY)
-        PRAM_REQUIRE(rot_cos && rot_sin && rot_cols % 64 == 0, "pram_linear_f16_h16: rotary needs cos/sin and rot_cols %% 64 == 0");
-    if (m == 0) return PRAM_OK;
-    LinArgs p{a0, lda0, k0, a1, lda1, k1, nullptr, bias, residual, ldr, out, ldo, m, n, alpha, flags,
-              rot_cos, rot_sin, rot_cols, 0, 0, 0, 0, 0, out16, ldo16};
-    int mi, wn;
-    gemm::choose_tile(m, n, &mi, &wn);
-    hipStream_t st = (hipStream_t)stream;
-    const _Float16* w = (const _Float16*)w16;
-    if (wn == 2) { if (mi == 2) launch_linear_f16_t<2, 2>(p, w, st); else launch_linear_f16_t<1, 2>(p, w, st); }
-    else launch_linear_f16_t<1, 1>(p, w, st);      // 128-row tiles for narrow outputs: the 256-row instantiation spills (43 registers) on this path
-    return pram_launch_status("pram_linear_f16_h16");
+    PRAM_REQUIRE(out16, "pram_linear_f16_h16: null pointer");      // the copy is what this entry is for; `out` is optional
+    LinArgs p = lin_dense(a0, lda0, k0, a1, lda1, k1, bias, residual, ldr, out, ldo, m, n, alpha, flags, rot_cos, rot_sin, rot_cols);
+    with_planes_out(p, out16, nullptr, ldo16);
+    return linear_f16_f32_impl("pram_linear_f16_h16", p, w16, stream);
 }
 
-static int linear_f32_impl(const int* lens, int t_pad, const float* a0, int lda0, int k0, const float* a1, int lda1, int k1, const float* w,
-                               const float* bias, const float* residual, int ldr, float* out, int ldo, int m, int n,
-                               float alpha, int flags, const float* rot_cos, const float* rot_sin, int rot_cols,
-                               void* stream) {
-    PRAM_REQUIRE(a0 && w && out, "pram_linear_f32: null pointer");
-    PRAM_REQUIRE(m >= 0 && n > 0 && k0 > 0 && k1 >= 0, "pram_linear_f32: bad sizes m=%d n=%d k0=%d k1=%d", m, n, k0, k1);
-    PRAM_REQUIRE((k0 + k1) % 4 == 0 && lda0 % 4 == 0, "pram_linear_f32: K and lda must be multiples of 4");
-    PRAM_REQUIRE(k1 == 0 || (a1 && k0 % 32 == 0 && lda1 % 4 == 0), "pram_linear_f32: concat needs k0 %% 32 == 0");
-    if (flags & PRAM_LIN_ROTARY)
-        PRAM_REQUIRE(rot_cos && rot_sin && rot_cols % 64 == 0, "pram_linear_f32: rotary needs cos/sin and rot_cols %% 64 == 0");
-    if (m == 0) return PRAM_OK;
-    LinArgs p{a0, lda0, k0, a1, lda1, k1, w, bias, residual, ldr, out, ldo, m, n, alpha, flags,
-              rot_cos, rot_sin, rot_cols, 0, 0, 0, 0, 0};
-    PRAM_REQUIRE(!lens || t_pad > 0, "pram_linear_f32: lens needs t_pad > 0");
-    p.lens = lens;
-    p.t_pad = t_pad;
+static int linear_f32_impl(const char* who, LinArgs& p, const float* w, void* stream) {
+    p.w = w;
+    if (int e = lin_check(who, F32_RULES, p, p.a0 && p.w && p.out, p.a1 != nullptr, 1.0f)) return e;
+    if (p.m == 0) return PRAM_OK;
     launch_linear(p, 1, (hipStream_t)stream);
-    return pram_launch_status("pram_linear_f32");
+    return pram_launch_status(who);
 }
 
 extern "C" int pram_linear_f32(const float* a0, int lda0, int k0, const float* a1, int lda1, int k1, const float* w,
                                const float* bias, const float* residual, int ldr, float* out, int ldo, int m, int n,
                                float alpha, int flags, const float* rot_cos, const float* rot_sin, int rot_cols,
                                void* stream) {
-    return linear_f32_impl(nullptr, 0, a0, lda0, k0, a1, lda1, k1, w, bias, residual, ldr, out, ldo, m, n, alpha, flags, rot_cos, rot_sin,
-                           rot_cols, stream);
+    LinArgs p = lin_dense(a0, lda0, k0, a1, lda1, k1, bias, residual, ldr, out, ldo, m, n, alpha, flags, rot_cos, rot_sin, rot_cols);
+    return linear_f32_impl("pram_linear_f32", p, w, stream);
 }
 
 extern "C" int pram_linear_ragged_f32(const float* a0, int lda0, int k0, const float* a1, int lda1, int k1, const float* w,
                                       const float* bias, const float* residual, int ldr, float* out, int ldo, int m, int n,
                                       float alpha, int flags, const float* rot_cos, const float* rot_sin, int rot_cols,
                                       const int* lens, int t_pad, void* stream) {
-    return linear_f32_impl(lens, t_pad, a0, lda0, k0, a1, lda1, k1, w, bias, residual, ldr, out, ldo, m, n, alpha, flags, rot_cos, rot_sin,
-                           rot_cols, stream);
+    LinArgs p = lin_dense(a0, lda0, k0, a1, lda1, k1, bias, residual, ldr, out, ldo, m, n, alpha, flags, rot_cos, rot_sin, rot_cols);
+    with_ragged(p, lens, t_pad);
+    return linear_f32_impl("pram_linear_ragged_f32", p, w, stream);
 }
 
 extern "C" int pram_bgemm_nt_f32(const float* a, int lda, long long stride_a, const float* b, int ldb,
@@ -1247,8 +1231,10 @@ extern "C" int pram_bgemm_nt_f32(const float* a, int lda, long long stride_a, co
     PRAM_REQUIRE(a && b && c, "pram_bgemm_nt_f32: null pointer");
     PRAM_REQUIRE(k % 4 == 0 && lda % 4 == 0 && ldb == k, "pram_bgemm_nt_f32: need k %% 4 == 0, lda %% 4 == 0, ldb == k");
     if (batch == 0 || m_max == 0 || n_max == 0) return PRAM_OK;
-    LinArgs p{a, lda, k, nullptr, 0, 0, b, nullptr, nullptr, 0, c, ldc, m_max, n_max, alpha, 0,
-              nullptr, nullptr, 0, stride_a, stride_b, stride_c, 0, 0};
+    LinArgs p = lin_a_f32(a, lda, k, nullptr, 0, 0);
+    p.w = b;
+    lin_out(p, nullptr, nullptr, 0, c, ldc, m_max, n_max, alpha);
+    with_batch_strides(p, stride_a, stride_b, stride_c);
     launch_linear(p, batch, (hipStream_t)stream);
     return pram_launch_status("pram_bgemm_nt_f32");
 }
@@ -1263,18 +1249,12 @@ extern "C" int pram_bgemm_nt_x3p_f32(const void* a_hi, const void* a_lo, int lda
     PRAM_REQUIRE(k > 0 && k % 32 == 0 && lda % 8 == 0 && ldb == k && stride_a % 8 == 0 && stride_b % 8 == 0,
                  "pram_bgemm_nt_x3p_f32: need k %% 32 == 0, lda %% 8 == 0, ldb == k, plane strides %% 8 == 0");
     if (batch == 0 || m_max == 0 || n_max == 0) return PRAM_OK;
-    LinArgs p{nullptr, lda, k, nullptr, 0, 0, nullptr, nullptr, nullptr, 0, c, ldc, m_max, n_max, alpha, 0,
-              nullptr, nullptr, 0, stride_a, stride_b, stride_c, 0, 0, nullptr, 0, nullptr, pram_act_scale()};
+    LinArgs p = lin_a_planes(lda, k, 0, 0);
+    lin_out(p, nullptr, nullptr, 0, c, ldc, m_max, n_max, alpha);
+    with_batch_strides(p, stride_a, stride_b, stride_c);
     PlaneArgs a{(const _Float16*)a_hi, (const _Float16*)a_lo, lda, nullptr, nullptr, 0};
-    const _Float16* wh = (const _Float16*)b_hi;
-    const _Float16* wl = (const _Float16*)b_lo;
-    const float inv = 1.0f / (pram_act_scale() * pram_act_scale());
-    hipStream_t st = (hipStream_t)stream;
-    if (launch_linear_x3_wide<true>(p, a, wh, wl, inv, st, batch)) return pram_launch_status("pram_bgemm_nt_x3p_f32");
-    int mi, wn;
-    gemm::choose_tile(m_max, n_max, &mi, &wn);
-    if (wn == 2) { if (mi == 2) launch_linear_x3p_t<2, 2>(p, a, wh, wl, inv, st, batch); else launch_linear_x3p_t<1, 2>(p, a, wh, wl, inv, st, batch); }
-    else         { if (mi == 2) launch_linear_x3p_t<2, 1>(p, a, wh, wl, inv, st, batch); else launch_linear_x3p_t<1, 1>(p, a, wh, wl, inv, st, batch); }
+    const float s = p.out16_scale = pram_act_scale();      // both operands are activation planes: nothing is split, nothing to guard
+    launch_linear_split<true>(p, a, b_hi, b_lo, 1.0f / (s * s), (hipStream_t)stream, batch);
     return pram_launch_status("pram_bgemm_nt_x3p_f32");
 }
 

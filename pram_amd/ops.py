@@ -35,6 +35,26 @@ def _rows2d(t: torch.Tensor, name: str) -> Tuple[int, int]:
     return t.numel() // t.shape[-1], t.shape[-1]
 
 
+def _rotary_args(rotary):
+    """(flags, cos, sin, rot_cols) of a linear entry from the wrappers' optional (cos, sin, rot_cols) triple."""
+    if rotary is None:
+        return 0, None, None, 0
+    rc, rs, rcols = rotary
+    return 1, rc, rs, rcols
+
+
+def _concat_rows(x: torch.Tensor, x2: Optional[torch.Tensor]):
+    """x (and the optional second input segment x2) as contiguous row matrices -> (x, x2, m, k0, k1)."""
+    x = x.contiguous()
+    m, k0 = _rows2d(x, "x")
+    k1 = 0
+    if x2 is not None:
+        x2 = x2.contiguous()
+        m2, k1 = _rows2d(x2, "x2")
+        assert m2 == m
+    return x, x2, m, k0, k1
+
+
 def _filled(shape, device, dtype=torch.float32, word: int = 0) -> torch.Tensor:
     """torch.zeros / torch.full for 32-bit dtypes without a framework kernel: torch.empty + hipMemsetD32Async on the current stream
     (``word`` = the 32-bit pattern; -2 as int32 is 0xFFFFFFFE)."""
@@ -61,15 +81,9 @@ def linear(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None
     without a valid row are skipped and left untouched (and only valid rows are stored).
     out_planes (with split_out): a (hi, lo) pair of existing fp16 buffers to write into instead of fresh ones."""
     L = _lib.load()
-    x = x.contiguous()
-    m, k0 = _rows2d(x, "x")
+    x, x2, m, k0, k1 = _concat_rows(x, x2)
     if lens is not None:
         assert t_pad > 0 and m % t_pad == 0 and lens.dtype == torch.int32 and lens.numel() == m // t_pad
-    k1 = 0
-    if x2 is not None:
-        x2 = x2.contiguous()
-        m2, k1 = _rows2d(x2, "x2")
-        assert m2 == m
     _chk(w, "w")
     w = w.contiguous()
     n = w.shape[0]
@@ -80,10 +94,7 @@ def linear(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None
         out = torch.empty(*x.shape[:-1], n, device=x.device, dtype=torch.float32)
     if residual is not None:
         residual = residual.contiguous()
-    flags, rc, rs, rcols = 0, None, None, 0
-    if rotary is not None:
-        rc, rs, rcols = rotary
-        flags = 1
+    flags, rc, rs, rcols = _rotary_args(rotary)
     K = k0 + k1
     use16 = prec == "f16" and K % 64 == 0 and (k1 == 0 or k0 % 64 == 0)
     x3_shape = K % 32 == 0 and (k1 == 0 or k0 % 32 == 0)
@@ -111,7 +122,7 @@ def linear(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None
             wh, wl, ws = split_weight(w)
             _lib.check(L.pram_linear_x3_ragged_f32(_p(x), k0, k0, _p(x2), k1, k1, _p(wh), _p(wl), ws, _p(bias), _p(residual), n,
                                                    _p(o32), n, _p(planes[0]), _p(planes[1]), n, m, n, float(alpha), flags, _p(rc), _p(rs),
-                                                   int(rcols), _p(lens), int(t_pad), _st()), "pram_linear_x3_f32")
+                                                   int(rcols), _p(lens), int(t_pad), _st()), "pram_linear_x3_ragged_f32")
         return o32, (planes[0], planes[1])
     if m == 0:          # empty token set: nothing to launch (an empty tensor has a null data pointer)
         return out
@@ -119,16 +130,16 @@ def linear(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None
         wh, wl, ws = split_weight(w)
         _lib.check(L.pram_linear_x3_ragged_f32(_p(x), k0, k0, _p(x2), k1, k1, _p(wh), _p(wl), ws, _p(bias), _p(residual), n, _p(out), n,
                                                None, None, 0, m, n, float(alpha), flags, _p(rc), _p(rs), int(rcols), _p(lens), int(t_pad),
-                                               _st()), "pram_linear_x3_f32")
+                                               _st()), "pram_linear_x3_ragged_f32")
         return out
     if use16:      # ragged calls included: tiles without a valid row are skipped, only valid rows are stored (as on the other paths)
         _lib.check(L.pram_linear_f16_ragged_f32(_p(x), k0, k0, _p(x2), k1, k1, _p(_w16(w)), _p(bias), _p(residual),
                                                 n, _p(out), n, m, n, float(alpha), flags, _p(rc), _p(rs), int(rcols), _p(lens), int(t_pad), _st()),
-                   "pram_linear_f16_f32")
+                   "pram_linear_f16_ragged_f32")
         return out
     _lib.check(L.pram_linear_ragged_f32(_p(x), k0, k0, _p(x2), k1, k1, _p(w), _p(bias), _p(residual),
                                         n, _p(out), n, m, n, float(alpha), flags, _p(rc), _p(rs), int(rcols), _p(lens), int(t_pad), _st()),
-               "pram_linear_f32")
+               "pram_linear_ragged_f32")
     return out
 
 
@@ -140,13 +151,7 @@ def mlp_tail(x: torch.Tensor, w0c: torch.Tensor, b0c: torch.Tensor, gamma: torch
     second normalises and GELUs its operand while it stages it (pram_linear_x3_ssq_f32 / pram_linear_x3_lngelu_f32).  Shapes the
     fast path cannot take (K % 32 != 0, hidden > 1024) raise."""
     L = _lib.load()
-    x = x.contiguous()
-    m, k0 = _rows2d(x, "x")
-    k1 = 0
-    if x2 is not None:
-        x2 = x2.contiguous()
-        m2, k1 = _rows2d(x2, "x2")
-        assert m2 == m
+    x, x2, m, k0, k1 = _concat_rows(x, x2)
     hid = w0c.shape[0]
     n = w3.shape[0]
     if (k0 + k1) % 32 or (k1 and k0 % 32) or hid % 32 or hid > 1024 or w0c.shape[1] != k0 + k1 or w3.shape[1] != hid:
@@ -191,10 +196,7 @@ def linear_qkv_planes(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Ten
     assert t_seq % 64 == 0 and m % t_seq == 0 and k0 % 32 == 0 and col0 > 0 and col0 % 64 == 0
     planes = torch.empty(2, m, col0, device=x.device, dtype=torch.float16)
     vt = torch.empty(2, m // t_seq, heads, 64, t_seq, device=x.device, dtype=torch.float16)
-    flags, rc, rs, rcols = 0, None, None, 0
-    if rotary is not None:
-        rc, rs, rcols = rotary
-        flags = 1
+    flags, rc, rs, rcols = _rotary_args(rotary)
     if m:
         wh, wl, ws = split_weight(w.contiguous())
         _lib.check(L.pram_linear_x3_qkv_f32(_p(x), k0, k0, _p(wh), _p(wl), ws, _p(bias), _p(planes[0]), _p(planes[1]), col0, _p(vt[0]), _p(vt[1]),
@@ -220,10 +222,7 @@ def linear_planes(x, w: torch.Tensor, bias: Optional[torch.Tensor] = None, *, x2
     assert w.shape[1] == k0 + k1 and k0 % 32 == 0 and k1 % 32 == 0
     o32 = torch.empty(m, n, device=xh.device, dtype=torch.float32) if out in ("f32", "both") else None
     planes = torch.empty(2, m, n, device=xh.device, dtype=torch.float16) if out in ("planes", "both") else None
-    flags, rc, rs, rcols = 0, None, None, 0
-    if rotary is not None:
-        rc, rs, rcols = rotary
-        flags = 1
+    flags, rc, rs, rcols = _rotary_args(rotary)
     if residual is not None:
         residual = residual.contiguous()
     if m:
@@ -274,7 +273,7 @@ def layernorm_gelu_(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, ep
     rows, cols = _rows2d(x, "x")
     assert x.is_contiguous()
     _lib.check(L.pram_layernorm_gelu_ragged_f32(_p(x), cols, _p(x), cols, _p(gamma), _p(beta), rows, cols, float(eps), _p(lens), int(t_pad),
-                                                _st()), "pram_layernorm_gelu_f32")
+                                                _st()), "pram_layernorm_gelu_ragged_f32")
     return x
 
 
@@ -661,7 +660,7 @@ def attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, batch: int, hea
     else:
         rc = L.pram_attention_f16_f32(_p(q), q.stride(0), _p(k), k.stride(0), _p(v), v.stride(0), _p(out), out.stride(0),
                                       _p(lse), _p(q_lens), _p(k_lens), batch, heads, m_max, n_max, float(scale), _st())
-    _lib.check(rc, "pram_attention_" + prec)
+    _lib.check(rc, "pram_attention_f32" if prec == "f32" else "pram_attention_f16_f32")
     if probe is not None:
         e1.record()
         # algorithmic FLOPs of QK^T + PV: 4 * m_b * n_b * 64 per (batch element, head), from the ACTUAL ragged
@@ -833,7 +832,7 @@ def attention_cross(qk: torch.Tensor, v: torch.Tensor, pairs: int, heads: int, t
     else:
         rc = L.pram_attention_cross_f16_f32(_p(qk), qk.stride(0), _p(v), v.stride(0), _p(out), out.stride(0), _p(lse), _p(lens),
                                             pairs, heads, t_max, float(scale), _st())
-    _lib.check(rc, "pram_attention_cross_" + prec)
+    _lib.check(rc, "pram_attention_cross_f32" if prec == "f32" else "pram_attention_cross_f16_f32")
     if probe is not None:
         e1.record()
         probe.append((lens, None if lens is None else torch.roll(lens, -pairs), t_max, t_max, heads, S, e0, e1, "cross", 16))
