@@ -94,6 +94,7 @@ __global__ __launch_bounds__(256) void row_sort_kernel(const float* __restrict__
         unsigned long long k = 0ull;     // pads sort last
         if (j < c) {
             unsigned u = __float_as_uint(x[(size_t)row * ld + j]);
+            if (u == 0x80000000u) u = 0u;                       // -0.0 == +0.0: one key, so the two tie by index like torch.sort
             u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);     // order-preserving float -> uint
             k = ((unsigned long long)u << 32) | (unsigned long long)(0xFFFFFFFFu - (unsigned)j);
             if (k == 0ull) k = 1ull;
@@ -114,11 +115,9 @@ __global__ __launch_bounds__(256) void row_sort_kernel(const float* __restrict__
             __syncthreads();
         }
     for (int j = threadIdx.x; j < c; j += 256) {
-        const unsigned long long k = keys[j];
-        unsigned u = (unsigned)(k >> 32);
-        u = (u & 0x80000000u) ? (u & 0x7FFFFFFFu) : ~u;
-        vals[(size_t)row * c + j] = __uint_as_float(u);
-        idx[(size_t)row * c + j] = (long long)(0xFFFFFFFFu - (unsigned)(k & 0xFFFFFFFFull));
+        const unsigned src = 0xFFFFFFFFu - (unsigned)(keys[j] & 0xFFFFFFFFull);
+        vals[(size_t)row * c + j] = x[(size_t)row * ld + src];     // the input's own bits (the key does not keep the sign of a zero)
+        idx[(size_t)row * c + j] = (long long)src;
     }
 }
 

@@ -1295,6 +1295,8 @@ def project_points(xyz: torch.Tensor, K: torch.Tensor, Tcw: torch.Tensor, im_w: 
     keep = torch.empty(n, device=dev, dtype=torch.int32)
     uvk = torch.empty(2, max(n, 1), device=dev, dtype=torch.float64)
     count = torch.zeros(1, device=dev, dtype=torch.int32)
+    if n == 0:      # nothing to project: the empty outputs have no storage to hand to the entry
+        return uvd, mask, keep, uvk, count
     _lib.check(L.pram_project_points_f64(_p(xyz), _p(K), _p(Tcw), n, float(im_w), float(im_h), _p(uvd), _p(mask), _p(keep), _p(uvk),
                                          _p(count), _st()), "pram_project_points_f64")
     return uvd, mask, keep, uvk, count
@@ -1313,6 +1315,8 @@ def seg_vote(sorted_vals: torch.Tensor, sorted_ids: torch.Tensor, topk: int):
     nwin = torch.zeros(1, device=dev, dtype=torch.int32)
     tokens = torch.zeros(topk, max(n, 1), device=dev, dtype=torch.int32)
     mean = torch.zeros(topk, device=dev, dtype=torch.float32)
+    if n == 0:      # no tokens, no winners: the empty class lists have no storage to hand to the entry
+        return sid, rank, cnt, nwin, tokens, mean
     _lib.check(L.pram_seg_vote(_p(sorted_ids), _p(sorted_vals), n, c, int(topk), _p(sid), _p(rank), _p(cnt), _p(nwin), _p(tokens), _p(mean),
                                _st()), "pram_seg_vote")
     return sid, rank, cnt, nwin, tokens, mean
@@ -1387,7 +1391,7 @@ def seg_vote_batched(sorted_vals: torch.Tensor, sorted_ids: torch.Tensor, topk: 
     tokens = _filled((B, topk, max(n, 1)), dev, torch.int32)
     mean = _filled((B, topk), dev)
     st = _st()
-    for b in range(B):
+    for b in range(B if n else 0):      # n == 0: no tokens, no winners (the zero fill above)
         _lib.check(L.pram_seg_vote(_p(sorted_ids[b]), _p(sorted_vals[b]), n, c, topk, _p(sid[b]), _p(rank[b]), _p(cnt[b]), _p(nwin[b:]),
                                    _p(tokens[b]), _p(mean[b]), st), "pram_seg_vote")
     return sid, rank, cnt, nwin, tokens, mean
