@@ -465,6 +465,37 @@ int pram_select_keypoints_f32(const float* nms, int batch, int h, int w, float c
 int pram_sample_nhwc_f32(const float* fmap, int batch, int fh, int fw, int c, const float* kpts,
                          const int* lens, int n_max, int s, int l2norm, float* out, void* stream);
 
+/* ---- the descriptor head at the sampled pixels only.  A frame's keypoints read at most four map pixels each; the head's last two
+ * layers (convDa.3, convDb + normalize) are row-wise independent, so they run on the list of those pixels instead of the map:
+ * pram_sfd2_row_list -> pram_conv3x3_rows_x3_f32 -> pram_conv1x1_rows_x3_l2norm_f32 -> pram_sample_rows_f32 gives the bits of
+ * pram_conv2d_nhwc_x3_f32 -> pram_conv2d_nhwc_x3_l2norm_f32 -> pram_sample_nhwc_f32.  No host synchronisation anywhere. */
+
+/* The pixels pram_sample_nhwc_f32 would read for kpts [b][n_max][2] (lens [b] or NULL) on an fh x fw map at stride s — the same
+ * coordinate arithmetic and validity tests, corners outside the map are not listed.  rows [b][rlen]: the distinct pixels
+ * (y * fw + x) in ascending order, then -1;  n_rows [b]: how many;  pix2row [b][fh * fw]: a listed pixel's position in rows
+ * (entries of other pixels are left as they are).  rlen >= min(4 n_max, fh * fw); fh * fw <= 2^18.  The layout is deterministic. */
+int pram_sfd2_row_list(const float* kpts, const int* lens, int batch, int n_max, int fh, int fw, int s, int* rows,
+                       int* n_rows, int* pix2row, int rlen, void* stream);
+
+/* 3x3 / stride 1 split-fp16 convolution of in [batch][h][w][cin] at the listed pixels: out [batch * rlen][cout], row b * rlen + r =
+ * pixel rows[b][r], bit for bit what pram_conv2d_nhwc_x3_f32 gives that pixel.  Tiles of 256 rows: a tile whose first row is
+ * >= n_rows[b] is neither computed nor written; the dead rows of a partly live tile repeat the last live pixel.  rlen % 256 == 0,
+ * cin % 32 == 0. */
+int pram_conv3x3_rows_x3_f32(const float* in, int batch, int h, int w, int cin, const void* wgt_hi, const void* wgt_lo,
+                             float w_scale, const float* bias, const int* rows, const int* n_rows, int rlen, float* out,
+                             int cout, int relu, void* stream);
+
+/* 1x1 split-fp16 convolution + F.normalize over the channels (pram_conv2d_nhwc_x3_l2norm_f32's arithmetic) of the rows matrix
+ * in [batch * rlen][cin] -> out [batch * rlen][cout]; the rows of the 256-row tiles the producer skipped are neither read nor
+ * written.  cout <= 128, cin % 32 == 0, rlen % 256 == 0. */
+int pram_conv1x1_rows_x3_l2norm_f32(const float* in, int batch, int rlen, int cin, const void* wgt_hi, const void* wgt_lo,
+                                    float w_scale, const float* bias, const int* n_rows, float* out, int cout, void* stream);
+
+/* pram_sample_nhwc_f32 on a map that exists at the listed pixels only: rowmap [b * rlen][c], a tap at pixel p reads row
+ * b * rlen + pix2row[b][p].  Same taps in the same order (nw, ne, sw, se), same weights, same normalisation. */
+int pram_sample_rows_f32(const float* rowmap, const int* pix2row, int batch, int rlen, int fh, int fw, int c, const float* kpts,
+                         const int* lens, int n_max, int s, int l2norm, float* out, void* stream);
+
 /* F.normalize(x, dim=channel) of an NHWC map in place (nets/sfd2.py:333). rows = b*h*w */
 int pram_l2norm_rows_f32(float* x, int rows, int cols, void* stream);
 

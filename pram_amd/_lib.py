@@ -85,6 +85,10 @@ _SIGS = {
     "pram_select_keypoints_f32": (I, [P, I, I, I, F, I, I, I, I, P, P, P, P, P]),
     "pram_sample_nhwc_f32": (I, [P, I, I, I, I, P, P, I, I, I, P, P]),
     "pram_l2norm_rows_f32": (I, [P, I, I, P]),
+    "pram_sfd2_row_list": (I, [P, P, I, I, I, I, I, P, P, P, I, P]),
+    "pram_conv3x3_rows_x3_f32": (I, [P, I, I, I, I, P, P, F, P, P, P, I, P, I, I, P]),
+    "pram_conv1x1_rows_x3_l2norm_f32": (I, [P, I, I, I, P, P, F, P, P, P, I, P]),
+    "pram_sample_rows_f32": (I, [P, P, I, I, I, I, I, P, P, I, I, I, P, P]),
     "pram_resize_bilinear_f32": (I, [P, P, I, I, I, I, I, P]),
     "pram_seg_epilogue_f32": (I, [P, P, I, I, I, F, P, P, P, P, P]),
     "pram_row_sort_desc_f32": (I, [P, I, I, I, P, P, P]),

@@ -25,7 +25,15 @@ struct ConvArgs {
     unsigned int* status;      // range guard of the split-fp16 path (common.h), or nullptr
     _Float16* out_hi; _Float16* out_lo;      // PLANES epilogue: the output * act_scale as two fp16 planes (the next layer's split operand)
     float act_scale = gemmx3::ACT_SCALE;     // split-fp16 path: scale of the activation planes (pram_act_scale() at launch)
+    // Row-list forms (pram_conv3x3_rows_x3_f32 / pram_conv1x1_rows_x3_l2norm_f32): the output is a [batch * rlen][cout] matrix, frame b owns
+    // rows [b * rlen, (b + 1) * rlen) and only its first n_rows[b] are wanted.  rows [batch][rlen] = their pixels (y * wo + x).
+    const int* rows = nullptr; const int* n_rows = nullptr; int rlen = 0;
 };
+
+// Rows of the producer's tile in a row-list chain (conv_x3w_kernel<4, 2, 4>): rlen is a multiple of it, so a tile lies in one frame,
+// and the tile is the unit of the skip rule — a tile whose first row is not live is neither computed nor stored, and a consumer
+// skips exactly the rows of skipped producer tiles, so that nothing reads what nothing wrote.
+constexpr int ROWS_BM = 256;
 
 // Shared epilogue of the fp32 and fp16 main loops: bias -> BN scale/shift -> residual -> ReLU.
 template <int MI, int WN>
@@ -334,7 +342,9 @@ __global__ __launch_bounds__(gemm16::NT, 2) void conv_f16_kernel(ConvArgs p, con
 
 // split-fp16 variant (gemm_core_x3.h): wh / wl = [cout][ks][ks][cin] * w_scale split into two fp16 planes on the host,
 // cin % 32 == 0 (a 32-deep chunk never straddles taps); the im2col rows are split while they are staged.
-template <int MI, int WN, bool L2N = false>
+// ROWS: the input is the [batch * rlen][cin] matrix of a row-list chain (ks = 1, one "image" of 1 x m pixels): a tile inside a
+// producer tile that was skipped exits before it reads anything.
+template <int MI, int WN, bool L2N = false, bool ROWS = false>
 __global__ __launch_bounds__(gemmx3::NT, 2) void conv_x3_kernel(ConvArgs p, const _Float16* __restrict__ wh,
                                                                  const _Float16* __restrict__ wl, float inv) {
     using namespace gemmx3;
@@ -347,6 +357,11 @@ __global__ __launch_bounds__(gemmx3::NT, 2) void conv_x3_kernel(ConvArgs p, cons
     const int tid = threadIdx.x;
     const int arow = tid >> 3, akq = tid & 7, brow = tid >> 2, bsl = tid & 3;
     const int row0 = tm * BM, col0 = tn * BN;
+    if constexpr (ROWS) {
+        static_assert(ROWS_BM % BM == 0, "a tile must lie inside one producer tile");
+        const int fb = row0 / p.rlen;
+        if ((row0 - fb * p.rlen) / ROWS_BM * ROWS_BM >= p.n_rows[fb]) return;      // workgroup-uniform
+    }
     const int pad = p.ks >> 1;
     int iy0[C::PA], ix0[C::PA], roff[C::PA];
     const float* base[C::PA];
@@ -413,7 +428,12 @@ __global__ __launch_bounds__(gemmx3::NT, 2) void conv_x3_kernel(ConvArgs p, cons
 // wide-tile split-fp16 convolution (gemm_core_x3w.h): 256 output pixels x 256 channels per 512-thread workgroup — the 256-channel
 // layers (conv3a / conv3b / convDa.* / convPa.* / conv4 1x1: 80 % of the stack's MACs).  Same arithmetic and accumulation order
 // as conv_x3_kernel: bit-identical results.
-template <int MI, int WM, int WN, bool PLANES = false>
+// GATHER: the output rows are the pixels of a row list (p.rows / p.n_rows / p.rlen) instead of the whole map: row r of frame
+// segment b is pixel rows[b][r], output row b * rlen + r.  Only where a row's pixel comes from differs — the tap walk, the
+// weights, the main loop and the epilogue are the dense kernel's, so a listed pixel gets the bits it has in the dense map.  A tile
+// whose first row is not live exits before the main loop (the list is live-first: workgroup-uniform); in a partly live tile the
+// dead rows repeat the last live pixel and are stored like the others, so every row of a tile that ran is defined.
+template <int MI, int WM, int WN, bool PLANES = false, bool GATHER = false>
 __global__ __launch_bounds__(64 * WM * WN, 2) void conv_x3w_kernel(ConvArgs p, const _Float16* __restrict__ wh,
                                                                     const _Float16* __restrict__ wl, float inv) {
     using namespace gemmx3w;
@@ -428,6 +448,14 @@ __global__ __launch_bounds__(64 * WM * WN, 2) void conv_x3w_kernel(ConvArgs p, c
     const int arow = tid >> 3, akq = tid & 7, qrow = tid >> 2, qsl = tid & 3;
     const int row0 = tm * BM, col0 = tn * BN;
     const int pad = p.ks >> 1;
+    int seg = 0, seg_row0 = 0, live = 0;      // GATHER: the tile's frame segment, its first row inside it, the segment's live rows
+    if constexpr (GATHER) {
+        static_assert(BM == ROWS_BM, "the row-list chain's skip rule is written for this tile");
+        seg = row0 / p.rlen;
+        seg_row0 = row0 - seg * p.rlen;
+        live = p.n_rows[seg];
+        if (seg_row0 >= live) return;
+    }
     int iy0[C::PA], ix0[C::PA], roff[C::PA];
     const float* base[C::PA];
     bool ok[C::PA];
@@ -436,10 +464,16 @@ __global__ __launch_bounds__(64 * WM * WN, 2) void conv_x3w_kernel(ConvArgs p, c
         const int row = row0 + arow + C::RA * pp;
         ok[pp] = row < p.m;
         const int rr = ok[pp] ? row : 0;
-        const int ox = rr % p.wo;
+        int ox = rr % p.wo;
         const int t = rr / p.wo;
-        const int oy = t % p.ho;
-        const int b = t / p.ho;
+        int oy = t % p.ho;
+        int b = t / p.ho;
+        if constexpr (GATHER) {
+            const int px = p.rows[(size_t)seg * p.rlen + min(seg_row0 + arow + C::RA * pp, live - 1)];
+            oy = px / p.wo;
+            ox = px - oy * p.wo;
+            b = seg;
+        }
         iy0[pp] = oy * p.stride - pad;
         ix0[pp] = ox * p.stride - pad;
         base[pp] = p.in + (size_t)b * p.h * p.wd * p.cin;
@@ -987,6 +1021,55 @@ extern "C" int pram_conv2d_nhwc_x3_l2norm_f32(const float* in, int batch, int h,
     p.tiles_n = 1;      // one column tile holds the whole channel vector (cout <= 128 = BN)
     hipLaunchKernelGGL((conv_x3_kernel<2, 2, true>), dim3(p.tiles_m), dim3(gemmx3::NT), 0, (hipStream_t)stream, p, (const _Float16*)wgt_hi,
                        (const _Float16*)wgt_lo, inv);
+    return pram_launch_status(who);
+}
+
+/* A 3x3 / stride 1 split-fp16 convolution at the pixels of a row list only (pram_sfd2_row_list): out [batch * rlen][cout], row
+   b * rlen + r = pixel rows[b][r] of frame b, the bits pram_conv2d_nhwc_x3_f32 gives that pixel.  Tiles of 256 rows past
+   n_rows[b] are neither computed nor written.  cin % 32 == 0, rlen % 256 == 0. */
+extern "C" int pram_conv3x3_rows_x3_f32(const float* in, int batch, int h, int w, int cin, const void* wgt_hi, const void* wgt_lo,
+                                        float w_scale, const float* bias, const int* rows, const int* n_rows, int rlen, float* out,
+                                        int cout, int relu, void* stream) {
+    const char* who = "pram_conv3x3_rows_x3_f32";
+    ConvArgs p{};
+    p.in = in; p.bias = bias; p.out = out;
+    p.batch = batch; p.h = h; p.wd = w; p.cin = cin; p.cout = cout; p.ks = 3; p.stride = 1; p.relu = relu;
+    if (int e = conv_args(who, p, CONV_X3, in && wgt_hi && wgt_lo && out && rows && n_rows, w_scale)) return e;
+    PRAM_REQUIRE(cout > 0 && rlen > 0 && rlen % ROWS_BM == 0 && (long long)batch * rlen < (1ll << 31),
+                 "%s: rlen=%d must be a positive multiple of %d (batch * rlen < 2^31), cout=%d positive", who, rlen, ROWS_BM, cout);
+    if (batch == 0) return PRAM_OK;
+    const float inv = arm_split(p, w_scale);
+    p.rows = rows; p.n_rows = n_rows; p.rlen = rlen;
+    p.m = batch * rlen;      // the rows of the output matrix (conv_args set the map's)
+    using CW = gemmx3w::Cfg<4, 2, 4>;
+    static_assert(CW::BM == ROWS_BM, "ROWS_BM is this tile's height");
+    const size_t shm = sizeof(gemmx3w::Smem<4, 2, 4>);
+    opt_in_lds<conv_x3w_kernel<4, 2, 4, false, true>>(shm);
+    hipLaunchKernelGGL((conv_x3w_kernel<4, 2, 4, false, true>), dim3(set_tiles<CW>(p, cout)), dim3(CW::NT), shm, (hipStream_t)stream, p,
+                       (const _Float16*)wgt_hi, (const _Float16*)wgt_lo, inv);
+    return pram_launch_status(who);
+}
+
+/* pram_conv2d_nhwc_x3_l2norm_f32 (1x1) on the [batch * rlen][cin] matrix pram_conv3x3_rows_x3_f32 wrote: out [batch * rlen][cout],
+   the same arithmetic per row, and the same skip rule — rows of a 256-row tile the producer skipped are not read and not written.
+   cout <= 128, cin % 32 == 0, rlen % 256 == 0. */
+extern "C" int pram_conv1x1_rows_x3_l2norm_f32(const float* in, int batch, int rlen, int cin, const void* wgt_hi, const void* wgt_lo,
+                                               float w_scale, const float* bias, const int* n_rows, float* out, int cout, void* stream) {
+    const char* who = "pram_conv1x1_rows_x3_l2norm_f32";
+    ConvArgs p{};
+    p.in = in; p.bias = bias; p.out = out;
+    PRAM_REQUIRE(batch >= 0 && rlen > 0 && rlen % ROWS_BM == 0 && (long long)batch * rlen < (1ll << 31),
+                 "%s: rlen=%d must be a positive multiple of %d (batch * rlen < 2^31)", who, rlen, ROWS_BM);
+    p.batch = 1; p.h = 1; p.wd = batch * rlen; p.cin = cin; p.cout = cout; p.ks = 1; p.stride = 1; p.relu = 0;
+    if (int e = conv_args(who, p, CONV_X3, in && wgt_hi && wgt_lo && out && n_rows, w_scale)) return e;
+    PRAM_REQUIRE(cout > 0 && cout <= 128, "%s: cout=%d must be at most 128", who, cout);
+    if (batch == 0) return PRAM_OK;
+    const float inv = arm_split(p, w_scale);
+    p.n_rows = n_rows; p.rlen = rlen;
+    p.tiles_m = cdiv(p.m, gemmx3::Cfg<2, 2>::BM);
+    p.tiles_n = 1;      // one column tile holds the whole channel vector (cout <= 128 = BN)
+    hipLaunchKernelGGL((conv_x3_kernel<2, 2, true, true>), dim3(p.tiles_m), dim3(gemmx3::NT), 0, (hipStream_t)stream, p,
+                       (const _Float16*)wgt_hi, (const _Float16*)wgt_lo, inv);
     return pram_launch_status(who);
 }
 

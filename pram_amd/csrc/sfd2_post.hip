@@ -390,16 +390,15 @@ __global__ __launch_bounds__(SEL_T) void sel_select_kernel(const float* __restri
 }
 
 // ---------------------------------------------------------------- K5: bilinear sampling of an NHWC map
-// one wave per keypoint; grid_sample(bilinear, align_corners=True, zeros padding) arithmetic.
-__global__ __launch_bounds__(256) void sample_kernel(const float* __restrict__ fmap, int fh, int fw, int c,
-                                                     const float* __restrict__ kpts, const int* __restrict__ lens,
-                                                     int n_max, float s, int l2norm, float* __restrict__ out) {
-    const int b = blockIdx.y;
-    const int lane = threadIdx.x & 63;
-    const int n = blockIdx.x * 4 + (threadIdx.x >> 6);
-    const int len = lens ? lens[b] : n_max;
-    if (n >= len) return;
-    const float kx = kpts[((size_t)b * n_max + n) * 2], ky = kpts[((size_t)b * n_max + n) * 2 + 1];
+// The four corner pixels of a keypoint and their weights: grid_sample(bilinear, align_corners=True, zeros padding) arithmetic.
+// sample_kernel and row_list_kernel both take them from here, so the pixels the list marks are the pixels the sampler reads.
+struct Corners {
+    int x0, y0;                    // north-west corner; the others are x0 + 1 / y0 + 1
+    float wnw, wne, wsw, wse;
+    bool vx0, vx1, vy0, vy1;       // column / row inside the map
+};
+
+__device__ __forceinline__ Corners sample_corners(float kx, float ky, int fh, int fw, float s) {
     // s > 0: sample_descriptors map  k = k - s/2 + 0.5 ; k /= (w*s - s/2 - 0.5, h*s - s/2 - 0.5) ; k = k*2 - 1
     // s <= 0: kpts are already normalised grid coordinates in [-1, 1] (plain F.grid_sample)
     float gx = kx, gy = ky;
@@ -417,14 +416,43 @@ __global__ __launch_bounds__(256) void sample_kernel(const float* __restrict__ f
     const float ix = ((gx + 1.f) / 2.f) * (float)(fw - 1);
     const float iy = ((gy + 1.f) / 2.f) * (float)(fh - 1);
     const float fx0 = floorf(ix), fy0 = floorf(iy);
-    const int x0 = (int)fx0, y0 = (int)fy0, x1 = x0 + 1, y1 = y0 + 1;
-    const float wnw = ((fx0 + 1.f) - ix) * ((fy0 + 1.f) - iy);
-    const float wne = (ix - fx0) * ((fy0 + 1.f) - iy);
-    const float wsw = ((fx0 + 1.f) - ix) * (iy - fy0);
-    const float wse = (ix - fx0) * (iy - fy0);
-    const bool vx0 = (unsigned)x0 < (unsigned)fw, vx1 = (unsigned)x1 < (unsigned)fw;
-    const bool vy0 = (unsigned)y0 < (unsigned)fh, vy1 = (unsigned)y1 < (unsigned)fh;
-    const float* base = fmap + (size_t)b * fh * fw * c;
+    Corners c;
+    c.x0 = (int)fx0;
+    c.y0 = (int)fy0;
+    c.wnw = ((fx0 + 1.f) - ix) * ((fy0 + 1.f) - iy);
+    c.wne = (ix - fx0) * ((fy0 + 1.f) - iy);
+    c.wsw = ((fx0 + 1.f) - ix) * (iy - fy0);
+    c.wse = (ix - fx0) * (iy - fy0);
+    c.vx0 = (unsigned)c.x0 < (unsigned)fw;
+    c.vx1 = (unsigned)(c.x0 + 1) < (unsigned)fw;
+    c.vy0 = (unsigned)c.y0 < (unsigned)fh;
+    c.vy1 = (unsigned)(c.y0 + 1) < (unsigned)fh;
+    return c;
+}
+
+// Live keypoints of frame b: lens[b] (n_max without lens), never more than the n_max the buffers hold.  Both kernels below take
+// the count from here, like the corners: what the list covers is what the sampler reads.
+__device__ __forceinline__ int live_keypoints(const int* __restrict__ lens, int b, int n_max) {
+    return min(lens ? lens[b] : n_max, n_max);
+}
+
+// one wave per keypoint.  ROWS: the map exists only at the pixels of a row list (row_list_kernel) — fmap is the [batch * rlen][c]
+// matrix of those pixels and a tap finds its row through pix2row; same taps, same order, same arithmetic.
+template <bool ROWS>
+__global__ __launch_bounds__(256) void sample_kernel(const float* __restrict__ fmap, int fh, int fw, int c,
+                                                     const float* __restrict__ kpts, const int* __restrict__ lens,
+                                                     int n_max, float s, int l2norm, float* __restrict__ out,
+                                                     const int* __restrict__ pix2row, int rlen) {
+    const int b = blockIdx.y;
+    const int lane = threadIdx.x & 63;
+    const int n = blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int len = live_keypoints(lens, b, n_max);
+    if (n >= len) return;
+    const float kx = kpts[((size_t)b * n_max + n) * 2], ky = kpts[((size_t)b * n_max + n) * 2 + 1];
+    const Corners k = sample_corners(kx, ky, fh, fw, s);
+    const int x0 = k.x0, y0 = k.y0, x1 = x0 + 1, y1 = y0 + 1;
+    const float* base = fmap + (size_t)b * (ROWS ? rlen : fh * fw) * c;
+    const int* p2r = ROWS ? pix2row + (size_t)b * fh * fw : nullptr;
     float* dst = out + ((size_t)b * n_max + n) * c;
     // up to two float4 per lane (c <= 512), named registers (no runtime-indexed arrays)
     auto gather = [&](int c4) -> float4 {
@@ -432,14 +460,15 @@ __global__ __launch_bounds__(256) void sample_kernel(const float* __restrict__ f
         if (c4 * 4 < c) {
             auto tap = [&](bool ok, int yy, int xx, float wgt) {
                 if (ok) {
-                    const float4 v = *reinterpret_cast<const float4*>(base + ((size_t)yy * fw + xx) * c + c4 * 4);
+                    const int px = yy * fw + xx;
+                    const float4 v = *reinterpret_cast<const float4*>(base + (size_t)(ROWS ? p2r[px] : px) * c + c4 * 4);
                     a.x += v.x * wgt; a.y += v.y * wgt; a.z += v.z * wgt; a.w += v.w * wgt;
                 }
             };
-            tap(vx0 && vy0, y0, x0, wnw);
-            tap(vx1 && vy0, y0, x1, wne);
-            tap(vx0 && vy1, y1, x0, wsw);
-            tap(vx1 && vy1, y1, x1, wse);
+            tap(k.vx0 && k.vy0, y0, x0, k.wnw);
+            tap(k.vx1 && k.vy0, y0, x1, k.wne);
+            tap(k.vx0 && k.vy1, y1, x0, k.wsw);
+            tap(k.vx1 && k.vy1, y1, x1, k.wse);
         }
         return a;
     };
@@ -453,6 +482,74 @@ __global__ __launch_bounds__(256) void sample_kernel(const float* __restrict__ f
     }
     if (lane * 4 < c) *reinterpret_cast<float4*>(dst + lane * 4) = a0;
     if ((lane + 64) * 4 < c) *reinterpret_cast<float4*>(dst + (lane + 64) * 4) = a1;
+}
+
+// The map pixels a frame's keypoints sample, as a list: one workgroup per frame marks the valid corners of every live keypoint in
+// an LDS bitmap (sample_corners: what sample_kernel reads), then compacts the marked pixels in ascending order — a thread owns a
+// run of bitmap words, a prefix scan over the runs' counts places them.  Marking is an atomic OR (the bitmap does not depend on
+// its order); placement uses none, so the layout is the same in every run and every graph replay.
+//   rows [b][rlen]: the pixels (y * fw + x), live first, then -1      n_rows [b]: how many      pix2row [b][fh * fw]: a listed
+//   pixel's position in rows (other entries are not written)
+constexpr int RL_T = 1024;
+
+__global__ __launch_bounds__(RL_T) void row_list_kernel(const float* __restrict__ kpts, const int* __restrict__ lens, int n_max,
+                                                        int fh, int fw, float s, int* __restrict__ rows, int* __restrict__ n_rows,
+                                                        int* __restrict__ pix2row, int rlen) {
+    extern __shared__ unsigned int rl_bits[];      // [nwords] bitmap, then [RL_T / 64] wave totals
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int npix = fh * fw, nwords = (npix + 31) >> 5;
+    unsigned int* wtot = rl_bits + nwords;
+    for (int i = tid; i < nwords; i += RL_T) rl_bits[i] = 0u;
+    __syncthreads();
+    const int len = live_keypoints(lens, b, n_max);
+    for (int n = tid; n < len; n += RL_T) {
+        const Corners k = sample_corners(kpts[((size_t)b * n_max + n) * 2], kpts[((size_t)b * n_max + n) * 2 + 1], fh, fw, s);
+        auto mark = [&](bool ok, int yy, int xx) {
+            if (ok) {
+                const int px = yy * fw + xx;
+                atomicOr(&rl_bits[px >> 5], 1u << (px & 31));
+            }
+        };
+        mark(k.vx0 && k.vy0, k.y0, k.x0);
+        mark(k.vx1 && k.vy0, k.y0, k.x0 + 1);
+        mark(k.vx0 && k.vy1, k.y0 + 1, k.x0);
+        mark(k.vx1 && k.vy1, k.y0 + 1, k.x0 + 1);
+    }
+    __syncthreads();
+    const int wpt = (nwords + RL_T - 1) / RL_T;      // bitmap words per thread
+    const int w0 = min(tid * wpt, nwords), w1 = min(w0 + wpt, nwords);
+    int cnt = 0;
+    for (int w = w0; w < w1; ++w) cnt += __popc(rl_bits[w]);
+    int inc = cnt;                                   // inclusive scan inside the wave
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const int v = __shfl_up(inc, o, 64);
+        if (lane >= o) inc += v;
+    }
+    if (lane == 63) wtot[wave] = (unsigned int)inc;
+    __syncthreads();
+    int before = 0, total = 0;
+#pragma unroll
+    for (int w = 0; w < RL_T / 64; ++w) {
+        const int t = (int)wtot[w];
+        if (w < wave) before += t;
+        total += t;
+    }
+    int pos = before + inc - cnt;                    // marked pixels in front of this thread's run (total <= min(4 len, npix) <= rlen)
+    int* rb = rows + (size_t)b * rlen;
+    int* pb = pix2row + (size_t)b * npix;
+    for (int w = w0; w < w1; ++w) {
+        unsigned int m = rl_bits[w];
+        while (m) {
+            const int px = (w << 5) + __ffs((int)m) - 1;
+            m &= m - 1;
+            rb[pos] = px;
+            pb[px] = pos;
+            ++pos;
+        }
+    }
+    for (int i = total + tid; i < rlen; i += RL_T) rb[i] = -1;
+    if (tid == 0) n_rows[b] = total;
 }
 
 // F.normalize over the channel (last NHWC) dim, in place: x / max(||x||, 1e-12)
@@ -579,9 +676,33 @@ extern "C" int pram_sample_nhwc_f32(const float* fmap, int batch, int fh, int fw
     PRAM_REQUIRE(fmap && kpts && out, "pram_sample_nhwc_f32: null pointer");
     PRAM_REQUIRE(c % 4 == 0 && c <= 512, "pram_sample_nhwc_f32: c=%d must be a multiple of 4 and <= 512", c);
     if (batch == 0 || n_max == 0) return PRAM_OK;
-    hipLaunchKernelGGL(sample_kernel, dim3(cdiv(n_max, 4), batch), dim3(256), 0, (hipStream_t)stream, fmap, fh, fw, c, kpts,
-                       lens, n_max, (float)s, l2norm, out);
+    hipLaunchKernelGGL(sample_kernel<false>, dim3(cdiv(n_max, 4), batch), dim3(256), 0, (hipStream_t)stream, fmap, fh, fw, c, kpts,
+                       lens, n_max, (float)s, l2norm, out, (const int*)nullptr, 0);
     return pram_launch_status("pram_sample_nhwc_f32");
+}
+
+extern "C" int pram_sfd2_row_list(const float* kpts, const int* lens, int batch, int n_max, int fh, int fw, int s, int* rows,
+                                  int* n_rows, int* pix2row, int rlen, void* stream) {
+    PRAM_REQUIRE(kpts && rows && n_rows && pix2row, "pram_sfd2_row_list: null pointer");
+    PRAM_REQUIRE(fh > 0 && fw > 0 && (long long)fh * fw <= (1 << 18), "pram_sfd2_row_list: a map of %d x %d pixels does not fit the LDS bitmap (2^18)", fh, fw);
+    PRAM_REQUIRE(n_max >= 0 && rlen > 0 && (long long)rlen >= (4ll * n_max < (long long)fh * fw ? 4ll * n_max : (long long)fh * fw),
+                 "pram_sfd2_row_list: rlen=%d is less than min(4 * n_max, fh * fw)", rlen);
+    if (batch == 0) return PRAM_OK;
+    const size_t shm = ((size_t)(fh * fw + 31) / 32 + RL_T / 64) * sizeof(unsigned int);
+    hipLaunchKernelGGL(row_list_kernel, dim3(batch), dim3(RL_T), shm, (hipStream_t)stream, kpts, lens, n_max, fh, fw, (float)s, rows,
+                       n_rows, pix2row, rlen);
+    return pram_launch_status("pram_sfd2_row_list");
+}
+
+extern "C" int pram_sample_rows_f32(const float* rowmap, const int* pix2row, int batch, int rlen, int fh, int fw, int c, const float* kpts,
+                                    const int* lens, int n_max, int s, int l2norm, float* out, void* stream) {
+    PRAM_REQUIRE(rowmap && pix2row && kpts && out, "pram_sample_rows_f32: null pointer");
+    PRAM_REQUIRE(c % 4 == 0 && c <= 512, "pram_sample_rows_f32: c=%d must be a multiple of 4 and <= 512", c);
+    PRAM_REQUIRE(rlen > 0 && (long long)fh * fw < (1ll << 31), "pram_sample_rows_f32: bad sizes rlen=%d fh=%d fw=%d", rlen, fh, fw);
+    if (batch == 0 || n_max == 0) return PRAM_OK;
+    hipLaunchKernelGGL(sample_kernel<true>, dim3(cdiv(n_max, 4), batch), dim3(256), 0, (hipStream_t)stream, rowmap, fh, fw, c, kpts,
+                       lens, n_max, (float)s, l2norm, out, pix2row, rlen);
+    return pram_launch_status("pram_sample_rows_f32");
 }
 
 extern "C" int pram_l2norm_rows_f32(float* x, int rows, int cols, void* stream) {

@@ -138,9 +138,11 @@ class ResNet4x(blk.PackedCache, nn.Module):
         logits = ops.conv2d_nhwc(pa, P["convPb.w"], P["convPb.b"], ks=1)
         return logits, ops.score_map(logits)
 
+    def _desc_stem(self, P, o4):
+        return ops.conv2d_nhwc(o4, P["convDa.w0"], P["convDa.b0"], P["convDa.s0"], P["convDa.t0"], ks=3, relu=True)
+
     def _desc_head(self, P, o4):
-        da = ops.conv2d_nhwc(o4, P["convDa.w0"], P["convDa.b0"], P["convDa.s0"], P["convDa.t0"], ks=3, relu=True)
-        da = ops.conv2d_nhwc(da, P["convDa.w3"], P["convDa.b3"], ks=3)
+        da = ops.conv2d_nhwc(self._desc_stem(P, o4), P["convDa.w3"], P["convDa.b3"], ks=3)
         return ops.conv2d_nhwc(da, P["convDb.w"], P["convDb.b"], ks=1, l2norm=True)           # convDb, then F.normalize(desc, dim=1)
 
     @staticmethod
@@ -172,9 +174,12 @@ class ResNet4x(blk.PackedCache, nn.Module):
 
     @torch.no_grad()
     @blk.with_model_precision
-    def extract_batched(self, image: torch.Tensor, config: dict, per_image_fallback: bool = True):
+    def extract_batched(self, image: torch.Tensor, config: dict, per_image_fallback: bool = True, dense_desc: bool = True):
         """Device-resident, sync-free form of extract_local_global for batches of independent queries:
-        padded keypoints [B,k,2], scores [B,k], descriptors [B,k,128], counts int32 [B] (device)."""
+        padded keypoints [B,k,2], scores [B,k], descriptors [B,k,128], counts int32 [B] (device).
+        dense_desc=False: the caller does not read ``desc_map`` (it is None) — the head's last two layers then run only at the
+        map pixels the keypoints sample (ops.sparse_descriptors: the same descriptor bits) where that is the faster form: on the
+        split-fp16 path, with a bounded keypoint count, and a pixel list shorter than ops.SPARSE_DESC_MAX_FRACTION of the map (ops.sparse_desc_rows)."""
         cfg = {**self.default_config, **config}
         b, _, ih, iw = image.shape
         P, o1b, o2b, o3b, o4 = self._backbone(image)
@@ -193,8 +198,13 @@ class ResNet4x(blk.PackedCache, nn.Module):
         else:
             kpts, scores, counts = ops.select_keypoints(nms, cfg['conf_th'], cfg['min_keypoints'], cfg['remove_borders'],
                                                         cfg['max_keypoints'], -1 if per_image_fallback else 0)
-        desc_map = self._desc_head(P, o4)
-        descs = ops.sample_nhwc(desc_map, kpts, counts, 4, True)
+        if not dense_desc and cfg['max_keypoints'] >= 0 and ops.gemm_prec() == "x3":
+            desc_map = None
+            descs = ops.sampled_descriptors(self._desc_stem(P, o4), P["convDa.w3"], P["convDa.b3"], P["convDb.w"], P["convDb.b"],
+                                            kpts, counts, 4)
+        else:
+            desc_map = self._desc_head(P, o4)
+            descs = ops.sample_nhwc(desc_map, kpts, counts, 4, True)
         return dict(score_map=score, desc_map=desc_map, mid_features=o4, global_nhwc=[o1b, o2b, o3b, o4],
                     keypoints=kpts, scores=scores, descriptors=descs, counts=counts)
 

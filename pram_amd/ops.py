@@ -1178,6 +1178,66 @@ def sample_nhwc(fmap: torch.Tensor, kpts: torch.Tensor, lens: Optional[torch.Ten
     return out
 
 
+# The descriptor head at the sampled pixels only (sparse_descriptors): taken when the row list is shorter than this fraction of the
+# map.  Measured back to back on 16 frames of 120 x 160 (profiles/r07_sparse_desc_head.txt): the dense chain takes 1245 us whatever
+# k is; the list chain 552 / 818 / 1067 us at k = 2048 / 3072 / 4096 (lists of 0.427 / 0.640 / 0.853 of the map), i.e. 45 us +
+# 62 us per 1024 listed rows, which meets the dense chain at a list of about the whole map.  0.9 keeps the largest list that was
+# measured (0.853: 14 % faster, the spread is 0.5 %) and nothing beyond it.
+SPARSE_DESC_MAX_FRACTION = 0.9
+SPARSE_ROWS_TILE = 256      # rows of a tile of the row-list chain (conv.hip ROWS_BM)
+
+
+def sparse_desc_rows(n_max: int, fh: int, fw: int) -> int:
+    """Rows per frame of the row-list chain for n_max keypoints on an fh x fw map, or 0 where the dense head is to be used."""
+    r = -(-min(4 * n_max, fh * fw) // SPARSE_ROWS_TILE) * SPARSE_ROWS_TILE
+    return r if 0 < r < SPARSE_DESC_MAX_FRACTION * fh * fw and fh * fw <= (1 << 18) else 0
+
+
+def sparse_descriptors(x: torch.Tensor, w3: torch.Tensor, b3, w1: torch.Tensor, b1, kpts: torch.Tensor, lens: Optional[torch.Tensor],
+                       s: int, rlen: int, want_parts: bool = False):
+    """sample_nhwc(conv2d_nhwc(conv2d_nhwc(x, w3, b3, ks=3), w1, b1, ks=1, l2norm=True), kpts, lens, s, True), bit for bit, with the
+    two convolutions computed only at the map pixels the keypoints sample (split-fp16 path; x [B,fh,fw,Cin] NHWC, w3 [C,3,3,Cin],
+    w1 [Cout<=128,1,1,C], kpts [B,N,2]).  rlen: rows per frame (sparse_desc_rows).  No host synchronisation.
+    want_parts: also return (rows, n_rows, pix2row)."""
+    L = _lib.load()
+    _chk(x, "x")
+    assert x.is_contiguous() and w3.is_contiguous() and w1.is_contiguous()
+    kpts = kpts.contiguous()
+    B, fh, fw, Cin = x.shape
+    N = kpts.shape[1]
+    Cm, Cout = w3.shape[0], w1.shape[0]
+    dev = x.device
+    rows = torch.empty(B, rlen, device=dev, dtype=torch.int32)
+    n_rows = torch.empty(B, device=dev, dtype=torch.int32)
+    pix2row = torch.empty(B, fh * fw, device=dev, dtype=torch.int32)
+    _lib.check(L.pram_sfd2_row_list(_p(kpts), _p(lens), B, N, fh, fw, int(s), _p(rows), _p(n_rows), _p(pix2row), rlen, _st()),
+               "pram_sfd2_row_list")
+    mid = torch.empty(B * rlen, Cm, device=dev, dtype=torch.float32)
+    wh, wl, ws = split_weight(w3)
+    _lib.check(L.pram_conv3x3_rows_x3_f32(_p(x), B, fh, fw, Cin, _p(wh), _p(wl), ws, _p(b3), _p(rows), _p(n_rows), rlen, _p(mid), Cm, 0,
+                                          _st()), "pram_conv3x3_rows_x3_f32")
+    dmat = torch.empty(B * rlen, Cout, device=dev, dtype=torch.float32)
+    wh, wl, ws = split_weight(w1)
+    _lib.check(L.pram_conv1x1_rows_x3_l2norm_f32(_p(mid), B, rlen, Cm, _p(wh), _p(wl), ws, _p(b1), _p(n_rows), _p(dmat), Cout, _st()),
+               "pram_conv1x1_rows_x3_l2norm_f32")
+    out = _filled((B, N, Cout), dev)
+    _lib.check(L.pram_sample_rows_f32(_p(dmat), _p(pix2row), B, rlen, fh, fw, Cout, _p(kpts), _p(lens), N, int(s), 1, _p(out), _st()),
+               "pram_sample_rows_f32")
+    return (out, rows, n_rows, pix2row) if want_parts else out
+
+
+def sampled_descriptors(x: torch.Tensor, w3: torch.Tensor, b3, w1: torch.Tensor, b1, kpts: torch.Tensor, lens: Optional[torch.Tensor],
+                        s: int) -> torch.Tensor:
+    """The descriptor head behind its first layer for a caller that wants the keypoints' descriptors and not the map:
+    sparse_descriptors where the pixel list is short enough to pay (sparse_desc_rows), the dense layers and sample_nhwc
+    otherwise — the same bits either way.  Split-fp16 path only."""
+    rlen = sparse_desc_rows(kpts.shape[1], x.shape[1], x.shape[2]) if FUSED_L2NORM else 0
+    if rlen:
+        return sparse_descriptors(x, w3, b3, w1, b1, kpts, lens, s, rlen)
+    dm = conv2d_nhwc(conv2d_nhwc(x, w3, b3, ks=3, precision="x3"), w1, b1, ks=1, precision="x3", l2norm=True)
+    return sample_nhwc(dm, kpts, lens, s, True)
+
+
 def l2norm_rows_(x: torch.Tensor) -> torch.Tensor:
     L = _lib.load()
     assert x.is_contiguous()

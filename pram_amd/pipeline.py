@@ -86,10 +86,12 @@ class QueryPipeline:
     when an activation left the fp16 parts' range; "raise" raises instead; "deferred" never synchronises (batches in flight,
     hipGraph capture): the caller asks ``ops.x3_range_exceeded()`` when it reads the results.
     match_keypoints: only the first (= best-scoring) M keypoints of every query enter the matcher (SURVEY.md §8(d)'s secondary
-    shape: the keypoints voted to one landmark, localization/multimap3d.py:131-139); 0 = all."""
+    shape: the keypoints voted to one landmark, localization/multimap3d.py:131-139); 0 = all.
+    dense_desc: False (default): nothing here reads SFD2's dense descriptor map, so the extraction may compute the descriptor head's
+    last two layers only at the sampled pixels (ResNet4x.extract_batched; same descriptor bits); True builds the whole map."""
 
     def __init__(self, sfd2, segnet, matcher, max_keypoints: int = 2048, min_keypoints: int = 128, bg_threshold: float = 0.95,
-                 overlap_below: int = 8, guard: str = "fallback", match_keypoints: int = 0):
+                 overlap_below: int = 8, guard: str = "fallback", match_keypoints: int = 0, dense_desc: bool = False):
         self.sfd2, self.segnet, self.matcher = sfd2, segnet, matcher
         self.bg_threshold = bg_threshold
         self.cfg = {'min_keypoints': min_keypoints, 'max_keypoints': max_keypoints}
@@ -97,6 +99,7 @@ class QueryPipeline:
         self.guard = guard
         self.match_keypoints = int(match_keypoints)
         self._side, self._side_main = None, None
+        self.dense_desc = bool(dense_desc)
 
     def warm_up(self, device, main: Optional[torch.cuda.Stream] = None) -> None:
         """Measure the side stream of forked steps (batches below overlap_below) beside ``main`` (default: the current stream) NOW:
@@ -133,7 +136,7 @@ class QueryPipeline:
             return ops.guarded_call(lambda: self._run(images, ref, stages), images.device)
 
     def _extract(self, images):
-        return self.sfd2.extract_batched(images, self.cfg, per_image_fallback=True)
+        return self.sfd2.extract_batched(images, self.cfg, per_image_fallback=True, dense_desc=self.dense_desc)
 
     def _recognise(self, ex, images, out):
         kpts, counts = ex['keypoints'], ex['counts']
