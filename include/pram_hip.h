@@ -48,6 +48,11 @@ extern "C" {
 
 int pram_hip_version(void);
 const char* pram_last_error(void);
+/* Which kernel instantiation the last size-dependent launch of the CALLING HOST THREAD took, e.g. "conv_x3<2,1>",
+ * "linear_x3w<4,2,4,planes>", "attention_x3_pipe<ps,mode0,w8,phases>" ("" before the first one).  The GEMM, convolution and
+ * attention entries pick their tile from the launch grid; this is how a test knows which one it exercised.  Entries whose
+ * kernel is fixed by the entry leave the record alone.  The string is valid until the thread's next call of this function. */
+const char* pram_last_kernel(void);
 
 /* ---------------------------------------------------------------- range guard of the split-fp16 ("x3") entries
  * The x3 entries carry every fp32 activation as two fp16 parts of value * s (s = the activation scale below, 16 by default).  A finite

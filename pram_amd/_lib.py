@@ -21,6 +21,7 @@ SZ = C.c_size_t
 _SIGS = {
     "pram_hip_version": (I, []),
     "pram_last_error": (C.c_char_p, []),
+    "pram_last_kernel": (C.c_char_p, []),
     "pram_set_status_word": (I, [P]),
     "pram_read_status_word": (I, [P, I, P]),
     "pram_x3_set_act_scale": (F, [F]),

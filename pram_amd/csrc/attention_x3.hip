@@ -19,7 +19,7 @@
 // index in every accumulator (online-softmax state lane-local, P never leaves registers); K tile [key][d] and V tile
 // TRANSPOSED and key-permuted [d][pos(key)] in LDS so that both MFMA operands are single ds_read_b128s.
 // Per 64-key tile per wave: 48 MFMA x 32 cycles = 1536 matrix cycles (40 / 1280 without the P_lo product; the f32-MFMA kernel: 8192).
-#include "common.h"
+#include "launch.h"
 #include <math.h>
 #include <stdlib.h>
 #include <type_traits>
@@ -1321,8 +1321,10 @@ extern "C" int pram_attention_x3_f32(const void* q_hi, const void* q_lo, int ldq
             const long u256 = (long)batch * heads * cdiv(m_max, 2 * BQ);
             if (u256 >= 256 && !(wv4 && wv4[0] == '4')) {
                 p.q_tiles = cdiv(m_max, 2 * BQ);
+                PRAM_NOTE_LAUNCH("attention_x3_pipe", 1, 0, 2 * NW | style_phases(0, 2 * NW) << 8);
                 hipLaunchKernelGGL((attention_x3_pipe_kernel<true, false, 0, 2 * NW>), dim3(batch * heads * p.q_tiles), dim3(2 * NW * 64), 0, st, p);
             } else {
+                PRAM_NOTE_LAUNCH("attention_x3_pipe", 1, 0, NW | style_phases(0, NW) << 8);
                 hipLaunchKernelGGL((attention_x3_pipe_kernel<true, false, 0>), grid, blk, 0, st, p);
             }
             return pram_launch_status("pram_attention_x3_f32");
@@ -1333,6 +1335,7 @@ extern "C" int pram_attention_x3_f32(const void* q_hi, const void* q_lo, int ldq
         // per SIMD, nothing to overlap with; 512-key groups: the longer prologue of the phases form is not won back)
 #define PRAM_LAUNCH_PIPE_(MODE_, GRID_, PH_)                                                                                  \
     do {                                                                                                                      \
+        PRAM_NOTE_LAUNCH("attention_x3_pipe", psplit, MODE_, NW | (PH_) << 8);                                                \
         if (psplit) hipLaunchKernelGGL((attention_x3_pipe_kernel<true, false, MODE_, NW, PH_>), GRID_, blk, 0, st, p);        \
         else hipLaunchKernelGGL((attention_x3_pipe_kernel<false, false, MODE_, NW, PH_>), GRID_, blk, 0, st, p);              \
     } while (0)
@@ -1356,6 +1359,7 @@ extern "C" int pram_attention_x3_f32(const void* q_hi, const void* q_lo, int ldq
             if (units256 >= 256 && !(wv && wv[0] == '4')) {
                 p.q_tiles = cdiv(m_max, 2 * BQ);
                 const dim3 grid8(batch * heads * p.q_tiles), blk8(2 * NW * 64);
+                PRAM_NOTE_LAUNCH("attention_x3_pipe", psplit, 0, 2 * NW | style_phases(0, 2 * NW) << 8);
                 if (psplit) hipLaunchKernelGGL((attention_x3_pipe_kernel<true, false, 0, 2 * NW>), grid8, blk8, 0, st, p);
                 else hipLaunchKernelGGL((attention_x3_pipe_kernel<false, false, 0, 2 * NW>), grid8, blk8, 0, st, p);
                 return pram_launch_status("pram_attention_x3_f32");
@@ -1389,9 +1393,11 @@ static void launch_h16t(ArgsX& p, hipStream_t st) {
     const long units256 = (long)p.batch * p.heads * cdiv(p.m_max, 2 * BQ);
     if (units256 >= 256 && !(wv && wv[0] == '4')) {
         p.q_tiles = cdiv(p.m_max, 2 * BQ);
+        PRAM_NOTE_LAUNCH("attention_h16t", 2 * NW, -1, -1);
         hipLaunchKernelGGL((attention_x3_pipe_kernel<false, true, 0, 2 * NW>), dim3(p.batch * p.heads * p.q_tiles), dim3(2 * NW * 64), 0, st, p);
         return;
     }
+    PRAM_NOTE_LAUNCH("attention_h16t", NW, -1, -1);
     hipLaunchKernelGGL((attention_x3_pipe_kernel<false, true, 0>), dim3(p.batch * p.heads * p.q_tiles), dim3(256), 0, st, p);
 }
 

@@ -2,7 +2,8 @@
 #include <stdarg.h>
 #include <math.h>
 #include <stdio.h>
-#include "common.h"
+#include <string.h>
+#include "launch.h"
 
 static thread_local char g_err[512] = "";
 
@@ -11,6 +12,29 @@ void pram_set_error(const char* fmt, ...) {
     va_start(ap, fmt);
     vsnprintf(g_err, sizeof(g_err), fmt, ap);
     va_end(ap);
+}
+
+// ---- the last size-dependent launch (launch.h, PRAM_NOTE_LAUNCH): per host thread, formatted only when asked for
+thread_local PramLaunchNote g_pram_last_launch = {nullptr, -1, -1, -1};
+static thread_local char g_last_kernel[96] = "";
+
+extern "C" const char* pram_last_kernel(void) {
+    const PramLaunchNote n = g_pram_last_launch;
+    if (!n.family) { g_last_kernel[0] = 0; return g_last_kernel; }
+    const char* slash = strchr(n.family, '/');
+    const int flen = slash ? (int)(slash - n.family) : (int)strlen(n.family);
+    char args[64];
+    int o = 0;
+    if (strncmp(n.family, "attention_x3_pipe", flen) == 0 && flen == 17) {
+        // a = PSPLIT, b = MODE, c = NWV | PHASES << 8
+        o = snprintf(args, sizeof(args), "%s,mode%d,w%d,%s", n.a ? "ps" : "p1", n.b, n.c & 0xff, (n.c >> 8) ? "phases" : "interleaved");
+    } else {
+        const int v[3] = {n.a, n.b, n.c};
+        for (int i = 0; i < 3 && v[i] >= 0; ++i) o += snprintf(args + o, sizeof(args) - o, "%s%d", i ? "," : "", v[i]);
+        args[o] = 0;
+    }
+    snprintf(g_last_kernel, sizeof(g_last_kernel), "%.*s<%s%s%s>", flen, n.family, args, (slash && o) ? "," : "", slash ? slash + 1 : "");
+    return g_last_kernel;
 }
 
 extern "C" int pram_hip_version(void) { return 110; }

@@ -924,6 +924,7 @@ extern "C" int pram_conv2d_nhwc_f32(const float* in, int batch, int h, int w, in
     hipStream_t st = (hipStream_t)stream;
     if (cin == 4) {      // the stem's padded RGB input: 256-row tiles whatever the grid
         dispatch_tile(2, wn, [&](auto, auto WN) {
+            PRAM_NOTE_LAUNCH("conv_f32_cin4", 2, WN, 16);
             hipLaunchKernelGGL((conv_kernel<true, 2, WN, 16>), dim3(set_tiles<gemm::Cfg<2, WN, 16>>(p, cout)), dim3(gemm::NT), 0, st, p);
         });
         return pram_launch_status(who);
@@ -931,6 +932,7 @@ extern "C" int pram_conv2d_nhwc_f32(const float* in, int batch, int h, int w, in
     // 64-channel outputs (conv1a, conv1b: short K, write-heavy) take the 16-deep chunk, the deep-K layers the 32-deep one
     dispatch_tile(mi, wn, [&](auto MI, auto WN) {
         constexpr int BKT = WN == 1 ? 16 : 32;
+        PRAM_NOTE_LAUNCH("conv_f32", MI, WN, BKT);
         hipLaunchKernelGGL((conv_kernel<false, MI, WN, BKT>), dim3(set_tiles<gemm::Cfg<MI, WN, BKT>>(p, cout)), dim3(gemm::NT), 0, st, p);
     });
     return pram_launch_status(who);
@@ -949,6 +951,7 @@ extern "C" int pram_conv2d_nhwc_f16_f32(const float* in, int batch, int h, int w
     gemm::choose_tile(p.m, cout, &mi, &wn);
     dispatch_tile(mi, wn, [&](auto MI, auto WN) {
         const int tiles = set_tiles<gemm16::Cfg<MI, WN>>(p, cout);
+        PRAM_NOTE_LAUNCH("conv_f16", MI, WN, -1);
         hipLaunchKernelGGL((conv_f16_kernel<MI, WN>), dim3(tiles), dim3(gemm16::NT), 0, (hipStream_t)stream, p, (const _Float16*)wgt16);
     });
     return pram_launch_status(who);
@@ -979,9 +982,11 @@ extern "C" int pram_conv2d_nhwc_x3_f32(const float* in, int batch, int h, int w,
         if ((long)p.tiles_m * p.tiles_n >= 224) {
             if (narrow) {
                 opt_in_lds<conv3x3_x3h_kernel<2>>(sizeof(halo::Smem<2>));
+                PRAM_NOTE_LAUNCH("conv_x3h", 2, -1, -1);
                 hipLaunchKernelGGL(conv3x3_x3h_kernel<2>, dim3(p.tiles_m * p.tiles_n), dim3(halo::NT), sizeof(halo::Smem<2>), st, p, wh, wl, inv, tiles_x, tiles_y);
             } else {
                 opt_in_lds<conv3x3_x3h_kernel<4>>(sizeof(halo::Smem<4>));
+                PRAM_NOTE_LAUNCH("conv_x3h", 4, -1, -1);
                 hipLaunchKernelGGL(conv3x3_x3h_kernel<4>, dim3(p.tiles_m * p.tiles_n), dim3(halo::NT), sizeof(halo::Smem<4>), st, p, wh, wl, inv, tiles_x, tiles_y);
             }
             return pram_launch_status(who);
@@ -991,6 +996,7 @@ extern "C" int pram_conv2d_nhwc_x3_f32(const float* in, int batch, int h, int w,
         using CW = gemmx3w::Cfg<4, 2, 4>;
         const size_t shm = sizeof(gemmx3w::Smem<4, 2, 4>);
         opt_in_lds<conv_x3w_kernel<4, 2, 4>>(shm);
+        PRAM_NOTE_LAUNCH("conv_x3w", 4, 2, 4);
         hipLaunchKernelGGL((conv_x3w_kernel<4, 2, 4>), dim3(set_tiles<CW>(p, cout)), dim3(CW::NT), shm, st, p, wh, wl, inv);
         return pram_launch_status(who);
     }
@@ -998,6 +1004,7 @@ extern "C" int pram_conv2d_nhwc_x3_f32(const float* in, int batch, int h, int w,
     gemm::choose_tile(p.m, cout, &mi, &wn);
     dispatch_tile(mi, wn, [&](auto MI, auto WN) {
         const int tiles = set_tiles<gemmx3::Cfg<MI, WN>>(p, cout);
+        PRAM_NOTE_LAUNCH("conv_x3", MI, WN, -1);
         hipLaunchKernelGGL((conv_x3_kernel<MI, WN>), dim3(tiles), dim3(gemmx3::NT), 0, st, p, wh, wl, inv);
     });
     return pram_launch_status(who);

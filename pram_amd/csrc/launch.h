@@ -14,6 +14,14 @@ void dispatch_tile(int mi, int wn, F&& f) {
     else         { if (mi == 2) f(two{}, one{}); else f(one{}, one{}); }
 }
 
+// Record of the last size-dependent launch of the calling host thread (capi.hip keeps it next to the error text; the tests read it
+// through pram_last_kernel()).  PRAM_NOTE_LAUNCH("family", a, b, c) goes immediately before every hipLaunchKernelGGL whose
+// instantiation the problem size picks: a string literal and up to three template arguments (negative = none), a few word stores and
+// no formatting — the text is made when somebody asks.  "family/variant" prints the variant as a last argument.
+struct PramLaunchNote { const char* family; int a, b, c; };
+extern thread_local PramLaunchNote g_pram_last_launch;
+#define PRAM_NOTE_LAUNCH(family, a, b, c) (g_pram_last_launch = PramLaunchNote{family, (int)(a), (int)(b), (int)(c)})
+
 // The output tiles of an m x n problem cut into Cfg::BM x Cfg::BN blocks, written to p.tiles_m / p.tiles_n (the kernels find
 // their tile from them); returns their product, the 1-D grid.
 template <class Cfg, class Args>

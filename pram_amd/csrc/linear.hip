@@ -929,6 +929,7 @@ void launch_linear(LinArgs& p, int batch, hipStream_t st) {
     gemm::choose_tile(p.m * batch, p.n, &mi, &wn);
     dispatch_tile(mi, wn, [&](auto MI, auto WN) {
         constexpr int BKT = MI == 2 ? 16 : 32;
+        PRAM_NOTE_LAUNCH("linear_f32", MI, WN, BKT);
         hipLaunchKernelGGL((linear_kernel<MI, WN, BKT>), dim3(set_tiles<gemm::Cfg<MI, WN, BKT>>(p, p.n), batch), dim3(gemm::NT), 0, st, p);
     });
 }
@@ -938,10 +939,12 @@ void launch_linear_x3_t(LinArgs& p, const _Float16* wh, const _Float16* wl, floa
     const int tiles = set_tiles<gemmx3::Cfg<MI, WN>>(p, p.n);
     if constexpr (WN == 2) {      // the LayerNorm + GELU operand transform exists for outputs wider than 64 columns (pram_linear_x3_lngelu_f32 checks)
         if (p.ln_ssq) {
+            PRAM_NOTE_LAUNCH("linear_x3/lngelu", MI, WN, -1);
             hipLaunchKernelGGL((linear_x3_kernel<MI, WN, true>), dim3(tiles, 1), dim3(gemmx3::NT), 0, st, p, wh, wl, inv);
             return;
         }
     }
+    PRAM_NOTE_LAUNCH("linear_x3", MI, WN, -1);
     hipLaunchKernelGGL((linear_x3_kernel<MI, WN>), dim3(tiles, 1), dim3(gemmx3::NT), 0, st, p, wh, wl, inv);
 }
 
@@ -955,10 +958,13 @@ void launch_linear_x3w_t(LinArgs& p, PlaneArgs& a, const _Float16* wh, const _Fl
         if (p.ln_ssq) {      // A = GELU(LayerNorm(hidden)) applied while staged: gamma | beta ride behind the stages
             const size_t shm_ln = shm + 2 * (size_t)(p.k0 + p.k1) * sizeof(float);
             opt_in_lds<linear_x3w_kernel<MI, WM, WN, false, 0, 1, true>>(shm + 2 * 1024 * sizeof(float));      // the ceiling: K <= 1024
+            PRAM_NOTE_LAUNCH("linear_x3w/lngelu", MI, WM, WN);
             hipLaunchKernelGGL((linear_x3w_kernel<MI, WM, WN, false, 0, 1, true>), grid, blk, shm_ln, st, p, a, wh, wl, inv);
             return;
         }
     }
+    if constexpr (APLANES) PRAM_NOTE_LAUNCH("linear_x3w/planes", MI, WM, WN);
+    else PRAM_NOTE_LAUNCH("linear_x3w", MI, WM, WN);
 #ifdef PRAM_PROFILING      // ablations (garbage results, PRAM_OK): profiling builds only (build_variants.py TAG:linear.hip:-DPRAM_PROFILING)
     static const char* abl = getenv("PRAM_GEMM_ABLATE");
     const int ab = abl ? atoi(abl) : 0;
@@ -1015,10 +1021,12 @@ void launch_linear_split(LinArgs& p, PlaneArgs& a, const void* w_hi, const void*
     int mi, wn;
     gemm::choose_tile(p.m, p.n, &mi, &wn);
     dispatch_tile(mi, wn, [&](auto MI, auto WN) {
-        if constexpr (APLANES)
+        if constexpr (APLANES) {
+            PRAM_NOTE_LAUNCH("linear_x3p", MI, WN, -1);
             hipLaunchKernelGGL((linear_x3p_kernel<MI, WN>), dim3(set_tiles<gemmx3::Cfg<MI, WN>>(p, p.n), batch), dim3(gemmx3::NT), 0, st, p, a, wh, wl, inv);
-        else
+        } else {
             launch_linear_x3_t<MI, WN>(p, wh, wl, inv, st);
+        }
     });
 }
 
@@ -1158,6 +1166,7 @@ static void launch_linear_f16(LinArgs& p, const _Float16* w16, hipStream_t st) {
     gemm::choose_tile(p.m, p.n, &mi, &wn);
     dispatch_tile(mi, wn, [&](auto MI_, auto WN) {
         constexpr int MI = WN == 1 ? 1 : MI_;      // 128-row tiles for narrow outputs: the 256-row instantiation spills (43 registers) on this path
+        PRAM_NOTE_LAUNCH("linear_f16", MI, WN, -1);
         hipLaunchKernelGGL((linear_f16_kernel<MI, WN>), dim3(set_tiles<gemm16::Cfg<MI, WN>>(p, p.n), 1), dim3(gemm16::NT), 0, st, p, w16);
     });
 }

@@ -65,6 +65,12 @@ def _filled(shape, device, dtype=torch.float32, word: int = 0) -> torch.Tensor:
     return t
 
 
+def last_kernel() -> str:
+    """The kernel instantiation the calling thread's last GEMM / convolution / attention launch took (pram_last_kernel), e.g.
+    'linear_x3w<4,2,4>': the entries choose it from the launch grid.  '' before the first such launch."""
+    return (_lib.load().pram_last_kernel() or b"").decode()
+
+
 def linear(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None, *, x2: Optional[torch.Tensor] = None,
            residual: Optional[torch.Tensor] = None, alpha: float = 1.0, out: Optional[torch.Tensor] = None,
            rotary: Optional[Tuple[torch.Tensor, torch.Tensor, int]] = None, half_copy: str = "no", split_out: str = "no",

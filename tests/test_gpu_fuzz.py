@@ -1,6 +1,7 @@
 """GPU: seeded random shapes through the split-fp16 kernels (the default path) against fp64 — the tile choice (narrow / 128 x 256 /
 256 x 256), ragged edges in every dimension, concatenated inputs, split-plane outputs, ragged sequences, cross-attention shifts.
 The hand-picked shapes of test_gpu_x3.py pin the error bars; this file hunts for shape-dependent addressing bugs."""
+import collections
 import math
 import random
 
@@ -17,6 +18,18 @@ pytestmark = pytest.mark.gpu
 def dev(hip_lib):
     assert torch.cuda.is_available(), "these tests need the MI355X"
     return torch.device("cuda:0")
+
+
+# which instantiation every fuzzed launch took (ops.last_kernel()), printed once when the module is done: what this file reaches
+# and what it leaves to tests/test_gpu_tile_instances.py (profiles/tile_instances.md has the tally of seeds 0..5)
+# (the line is printed while the module's fixture is torn down: run the file with `pytest -s` to see it)
+TALLY = collections.Counter()
+
+
+@pytest.fixture(scope="module", autouse=True)
+def tally_report():
+    yield
+    print("\nfuzz tally: " + ", ".join(f"{k} x{v}" for k, v in sorted(TALLY.items())))
 
 
 def err(a, ref64):
@@ -49,6 +62,7 @@ def test_linear_x3_random_shapes(dev, seed):
             ref = ref + res.double()
         kw = dict(x2=None if x2 is None else x2.to(dev), residual=None if res is None else res.to(dev), precision="x3")
         got = ops.linear(x.to(dev), w.to(dev), b.to(dev), **kw)
+        TALLY[ops.last_kernel()] += 1
         e = err(got, ref)
         assert e < 6e-6, (m, k0, k1, n, e)
         if res is None and n % 8 == 0:
@@ -70,6 +84,7 @@ def test_ragged_linear_x3_random(dev, seed):
     lens_l = [rng.choice([0, 1, T // 3, T - 1, T]) for _ in range(S)]
     lens = torch.tensor(lens_l, dtype=torch.int32, device=dev)
     full = ops.linear(x, w, None, precision="x3")
+    TALLY[ops.last_kernel()] += 1
     out = torch.full((S * T, n), 3.0, device=dev)
     ops.linear(x, w, None, precision="x3", out=out, lens=lens, t_pad=T)
     o3, f3 = out.view(S, T, n), full.view(S, T, n)
@@ -100,6 +115,7 @@ def test_attention_x3_random_shapes(dev, seed):
     kl = torch.tensor(klens, dtype=torch.int32, device=dev)
     pq, pk = _planes(qd), _planes(kd)
     out, lse = ops.attention_x3(pq, pk, ops.value_planes_t(_planes(vd), B, Hh, N, kl), B, Hh, M, N, 0.125, ql, kl, want_lse=True)
+    TALLY[ops.last_kernel()] += 1
     out = out.view(B, M, 256)
     col = ops.attention_colmean_x3(pq, pk, lse, B, Hh, M, N, 0.125, ql, kl)
     for b in range(B):
@@ -126,4 +142,5 @@ def test_conv_x3_random_shapes(dev, seed):
         ref = torch.relu(F.conv2d(x.double(), wt.double(), b.double(), stride=stride, padding=ks // 2)).permute(0, 2, 3, 1)
         got = ops.conv2d_nhwc(x.permute(0, 2, 3, 1).contiguous().to(dev), ResNet4x._ohwi(wt).to(dev), b.to(dev), None, None, ks=ks, stride=stride,
                               relu=True, precision="x3")
+        TALLY[ops.last_kernel()] += 1
         assert tuple(got.shape) == tuple(ref.shape) and err(got, ref) < 1e-5, (cin, cout, ks, stride, bsz, h, w)

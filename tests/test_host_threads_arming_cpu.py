@@ -105,7 +105,7 @@ import sys
 sys.path.insert(0, %r)
 from pram_amd import _lib
 L = _lib.load()
-helpers = {"pram_hip_version", "pram_last_error", "pram_fill_u32", "pram_linear_x3_ssq_parts", "pram_attention_x3_is_split",
+helpers = {"pram_hip_version", "pram_last_error", "pram_last_kernel", "pram_fill_u32", "pram_linear_x3_ssq_parts", "pram_attention_x3_is_split",
            "pram_attention_x3_mfma_per_tile", "pram_attention_x3_set_chunk_keys", "pram_attention_x3_set_p_split",
            "pram_attention_x3_set_split_target", "pram_x3_set_act_scale"}
 for name, (res, args) in sorted(_lib._SIGS.items()):
