@@ -741,6 +741,57 @@ int pram_pose_refine(const float* m_kpts, const double* norm_pts, const double* 
  * kept as a column of its own so that the row reads like the reference's result). */
 int pram_pose_select(const int* success, const int* num_inliers, int batch, int seg_k, int min_inliers, int* chosen, void* stream);
 
+/* ---------------------------------------------------------------- pose refinement by matching over covisible frames
+ * SingleMap3D.refine_pose_by_matching (singlemap3d.py:268-365) for a whole batch of located queries: ALL keypoints of a query are
+ * matched against the WHOLE of each frame covisible with the localisation's reference frame, the matches are stacked in list
+ * order with the localisation's own matches last, one pose is estimated on the stack, and find_reference_frames (singlemap3d.py:
+ * 500-511) votes for the new reference frames.  A refinement pair is a row of the plan table above with token offset -1 and
+ * sel_rows offset -1, so pram_cand_gather and pram_cand_correspond run on pram_refine_plan's table unchanged (they take the
+ * query from the plan's column), and pram_pose_* run on pram_refine_merge's list with seg_k = 1.  refine pairs = batch * n_cov,
+ * pair p = query p / n_cov, slot p % n_cov.
+ *
+ * Store tables (ReferenceStore builds them): the covisibility graph in CSR form, covis_frames[covis_off[f] .. covis_off[f + 1]]
+ * = the frames sharing most points with frame f in (count descending, frame index ascending), empty for a frame that is no
+ * landmark's reference frame ("vrf"), n_covis entries in all; the point table pt_ids [n_points] int64 (sorted, unique, no -1)
+ * with pt_frames[pt_off[i] .. pt_off[i + 1]] = the frames observing point i (duplicates counted), n_entries in all; is_vrf
+ * [n_frames] int32.  Every index read from a table is checked against the size given beside it before it is used.
+ *
+ * One thread per (query, slot).  chosen [batch][3] = pram_pose_select's; loc_plan = the localisation's plan table [..][batch *
+ * seg_k] (its frame and sid columns at pair b * seg_k + kept); counts [batch]; enable [batch] (NULL = every located query).
+ * plan [PRAM_CAND_PLAN_COLS][batch * n_cov]: query b, the kept candidate's sid, frame = entry j of the covisible list of the
+ * kept candidate's frame (the list cut to n_cov), semantic 0, lens0 = counts[b], lens1 = the frame's rows, token offset -1,
+ * first row of the frame, sel offset -1, order j; beyond the list, for a query that is not located (kept < 0) or not enabled:
+ * frame -1 and lens0 = lens1 = 0.  Per query ref_frame (store index of the kept candidate's frame, -1 = not refined),
+ * n_cov_used (slots in use) and init_on = 1 iff tracking status is 1 and the reference frame is in its own (cut) list — then
+ * singlemap3d.py:273-278 keeps the localisation's matches, and, its remove() acting on a copy, matches the frame again. */
+int pram_refine_plan(const int* chosen, const int* loc_plan, const int* counts, const int* enable, const int* frame_off,
+                     const int* covis_off, const int* covis_frames, int batch, int seg_k, int n_cov, int n_frames, int n_covis,
+                     int* plan, int* ref_frame, int* n_cov_used, int* init_on, void* stream);
+
+/* One workgroup per query.  r_*: pram_cand_correspond's outputs for the refinement pairs, [batch * n_cov][t0]... with r_count;
+ * a_*: the same for the localisation's pairs, [batch * seg_k][t0a]... with a_count.  Per query ONE list [batch][cap]..., cap >=
+ * n_cov * t0 + t0a: the slots in ascending order, inside a slot the order pram_cand_correspond left, then (init_on[b]) the rows
+ * of the kept candidate.  m_kpt_ids int64, m_kpts / m_ref_kpts [..][2], m_point3d_ids int64, m_xyz [..][3] float64 (copied as
+ * 64-bit words), m_sids, m_src int32 (slot of origin; n_cov = the localisation's), m_count [batch].  Offsets = the exclusive scan
+ * of the counts; an empty slot costs one load; rows at and beyond m_count[b] are not written. */
+int pram_refine_merge(const long long* r_kpt_ids, const float* r_kpts, const float* r_ref_kpts, const long long* r_point3d_ids,
+                      const double* r_xyz, const int* r_sids, const int* r_count, int t0, const long long* a_kpt_ids,
+                      const float* a_kpts, const float* a_ref_kpts, const long long* a_point3d_ids, const double* a_xyz,
+                      const int* a_sids, const int* a_count, int t0a, const int* chosen, const int* init_on, int batch,
+                      int seg_k, int n_cov, int cap, long long* m_kpt_ids, float* m_kpts, float* m_ref_kpts,
+                      long long* m_point3d_ids, double* m_xyz, int* m_sids, int* m_src, int* m_count, void* stream);
+
+/* find_reference_frames, one workgroup per query: over the rows r < m_count[b] of m_point3d_ids [batch][cap] — those with
+ * inliers [batch][cap] != 0 when success[b], all of them otherwise (singlemap3d.py:353-359) — the point id is looked up in pt_ids
+ * by binary search (an unknown id votes for nothing) and every entry of its frame list that is_vrf gets + 1 by an integer atomic
+ * in hist [batch][n_frames], a workspace of the caller in global memory which the entry zeroes (no limit on the map's size from
+ * LDS).  Then k selection rounds over the histogram: best_frames [batch][k] = the first k frames in (count descending, frame
+ * index ascending) with count > 0, -1 padded, best_counts [batch][k] (0 padded), n_best [batch].  1 <= k <= n_frames. */
+int pram_refine_frame_vote(const long long* m_point3d_ids, const int* m_count, const unsigned char* inliers, const int* success,
+                           int batch, int cap, const long long* pt_ids, const int* pt_off, const int* pt_frames, int n_points,
+                           int n_entries, const int* is_vrf, int n_frames, int k, int* hist, int* best_frames, int* best_counts,
+                           int* n_best, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

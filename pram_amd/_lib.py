@@ -111,6 +111,9 @@ _SIGS = {
     "pram_pose_score": (I, [P, P, P, P, P, P, P, I, I, I, I, C.c_double, P, P, P, P]),
     "pram_pose_refine": (I, [P, P, P, P, P, P, P, P, P, I, I, I, I, C.c_double, C.c_double, I, P, P, P, P, P, P]),
     "pram_pose_select": (I, [P, P, I, I, I, P, P]),
+    "pram_refine_plan": (I, [P, P, P, P, P, P, P, I, I, I, I, I, P, P, P, P, P]),
+    "pram_refine_merge": (I, [P, P, P, P, P, P, P, I, P, P, P, P, P, P, P, I, P, P, I, I, I, I, P, P, P, P, P, P, P, P, P]),
+    "pram_refine_frame_vote": (I, [P, P, P, P, I, I, P, P, P, I, I, P, I, I, P, P, P, P, P]),
 }
 
 

@@ -33,9 +33,19 @@ class ReferenceStore:
     frame_off[f] .. frame_off[f + 1] (RefFrame.get_keypoints = that range).  ``sel_rows`` holds, per frame, the frame's rows
     stably sorted by keypoint_segs, so get_keypoints_by_sid(sid) = one slice of it (rows with keypoint_segs == sid in their
     original order); the slice of every landmark in its own reference frame is tabulated for the device (lm_sel_off / lm_sel_len).
-    Per frame the label histogram that check_semantic_consistency needs (hist_label / hist_cnt)."""
+    Per frame the label histogram that check_semantic_consistency needs (hist_label / hist_cnt).
 
-    def __init__(self, frames: Sequence[dict], seg_ref_frame_ids, start_sid: int = 0, device=None):
+    For the refinement (localization/refine.py; singlemap3d.py:228-258, 500-511): point3D_frame_ids, a dict from point id to the
+    frame ids observing it (COLMAP's image_ids; duplicates are kept and counted, ids of frames outside the store are dropped);
+    None derives it from the rows (the frames holding a row with that id, one entry per such row, ascending frame index).  It
+    becomes the sorted point table pt_ids with the CSR lists pt_off / pt_frames (store frame indices).  is_vrf marks the frames
+    named ANYWHERE in seg_ref_frame_ids; for each of them the covisibility graph (covis_off / covis_frames / covis_count, CSR
+    over all frames, empty for the others) lists the covisibility_frame frames sharing most points with it: per row of the frame
+    with a known point id (not -1), every frame of that point's list counts once, the frame itself included.  Where the reference
+    leaves ties to argsort / argpartition the order here is (count descending, store frame index ascending), at the cut too."""
+
+    def __init__(self, frames: Sequence[dict], seg_ref_frame_ids, start_sid: int = 0, device=None, *, point3D_frame_ids=None,
+                 covisibility_frame: int = 20):
         frames = list(frames)
         for i, f in enumerate(frames):
             missing = [k for k in _FRAME_KEYS if k not in f]
@@ -97,9 +107,84 @@ class ReferenceStore:
             f = index_of[fid]
             self.lm_frame[k] = f
             self.lm_sel_off[k], self.lm_sel_len[k] = self._slices[f].get(k, (0, 0))
+        self.covisibility_frame = int(covisibility_frame)
+        if self.covisibility_frame < 1:
+            raise ValueError("covisibility_frame < 1")
+        self.is_vrf = np.zeros(len(frames), dtype=np.int32)
+        for _, v in items:
+            for fid in np.atleast_1d(np.asarray(v)).tolist():
+                if fid in index_of:      # singlemap3d.py:91-92: vrf frames the map does not hold are passed over
+                    self.is_vrf[index_of[fid]] = 1
+        self._build_point_table(point3D_frame_ids, index_of)
+        self._build_covisibility()
         self._dev: Dict[str, dict] = {}
         if device is not None:
             self.tables(device)
+
+    def _build_point_table(self, point3D_frame_ids, index_of) -> None:
+        F = len(self.frame_ids)
+        row_frame = np.repeat(np.arange(F, dtype=np.int32), np.diff(self.frame_off))
+        if point3D_frame_ids is None:
+            rows = np.nonzero(self.point3D_ids != -1)[0]
+            self.pt_ids, inv = np.unique(self.point3D_ids[rows], return_inverse=True)
+            order = np.argsort(inv.reshape(-1), kind="stable")      # rows are in ascending frame order already
+            self.pt_frames = row_frame[rows][order].astype(np.int32)
+            lens = np.bincount(inv.reshape(-1), minlength=len(self.pt_ids))
+        else:
+            keys = np.fromiter((int(k) for k in point3D_frame_ids.keys()), dtype=np.int64, count=len(point3D_frame_ids))
+            if len(np.unique(keys)) != len(keys):
+                raise ValueError("point3D_frame_ids: point ids are not unique")
+            vals = [np.atleast_1d(np.asarray(v)).reshape(-1) for v in point3D_frame_ids.values()]
+            lens = np.array([v.shape[0] for v in vals], dtype=np.int64)
+            flat = np.concatenate(vals) if vals and lens.sum() else np.zeros(0, dtype=np.int64)
+            fids = np.asarray(self.frame_ids)
+            if fids.dtype.kind in "iu" and flat.dtype.kind in "iu" and F:
+                srt = np.argsort(fids, kind="stable")
+                pos = np.clip(np.searchsorted(fids[srt], flat), 0, F - 1)
+                fidx = np.where(fids[srt][pos] == flat, srt[pos], -1)
+            else:
+                fidx = np.array([index_of.get(x, -1) for x in flat.tolist()], dtype=np.int64).reshape(-1)
+            owner = np.repeat(np.argsort(np.argsort(keys, kind="stable"), kind="stable"), lens)      # rank of the entry's point
+            keep = (fidx >= 0) & np.repeat(keys != -1, lens)
+            owner, fidx = owner[keep], fidx[keep]
+            order = np.argsort(owner, kind="stable")
+            known = np.sort(keys)
+            lens = np.bincount(owner, minlength=len(keys))[known != -1]
+            self.pt_ids = known[known != -1]
+            self.pt_frames = fidx[order].astype(np.int32)
+        self.pt_ids = np.ascontiguousarray(self.pt_ids, dtype=np.int64)
+        self.pt_off = np.zeros(len(self.pt_ids) + 1, dtype=np.int32)
+        self.pt_off[1:] = np.cumsum(lens)
+
+    def _build_covisibility(self) -> None:
+        """build_covisibility_graph (singlemap3d.py:228-258) for all vrf frames at once: every (row of a vrf frame, entry of its
+        point's frame list) is one count for the pair (frame, listed frame)."""
+        F = len(self.frame_ids)
+        row_frame = np.repeat(np.arange(F, dtype=np.int64), np.diff(self.frame_off))
+        rows = np.nonzero(self.is_vrf[row_frame].astype(bool) & (self.point3D_ids != -1))[0] if F else np.zeros(0, dtype=np.int64)
+        pi = np.searchsorted(self.pt_ids, self.point3D_ids[rows])
+        ok = pi < len(self.pt_ids)
+        ok[ok] = self.pt_ids[pi[ok]] == self.point3D_ids[rows][ok]
+        rows, pi = rows[ok], pi[ok]
+        lens = (self.pt_off[pi + 1] - self.pt_off[pi]).astype(np.int64)
+        start = np.cumsum(lens) - lens
+        ent = np.repeat(self.pt_off[pi].astype(np.int64) - start, lens) + np.arange(int(lens.sum()), dtype=np.int64)
+        key, cnt = np.unique(np.repeat(row_frame[rows], lens) * max(F, 1) + self.pt_frames[ent], return_counts=True)
+        f, g = key // max(F, 1), key % max(F, 1)
+        order = np.lexsort((g, -cnt, f))      # per frame: count descending, frame index ascending
+        f, g, cnt = f[order], g[order], cnt[order]
+        first = np.zeros(F + 1, dtype=np.int64)
+        first[1:] = np.cumsum(np.bincount(f, minlength=F))
+        keep = np.arange(len(f)) - first[f] < self.covisibility_frame
+        f, g, cnt = f[keep], g[keep], cnt[keep]
+        self.covis_off = np.zeros(F + 1, dtype=np.int32)
+        self.covis_off[1:] = np.cumsum(np.bincount(f, minlength=F))
+        self.covis_frames, self.covis_count = g.astype(np.int32), cnt.astype(np.int32)
+
+    def covisible(self, frame: int) -> np.ndarray:
+        """covisible_graph[frame]: the store indices of the frames covisible with store frame `frame`, best first (empty for a
+        frame that is no landmark's reference frame)."""
+        return self.covis_frames[self.covis_off[frame]:self.covis_off[frame + 1]].astype(np.int64)
 
     # ---- host views (what the two RefFrame accessors select; used by the tests and by anyone who wants to look)
     @property
@@ -135,9 +220,12 @@ class ReferenceStore:
             pad = lambda a: np.concatenate([a, np.zeros(1, dtype=a.dtype)])      # never an empty allocation behind a pointer
             t = {name: up(getattr(self, name)) if getattr(self, name).size else up(np.zeros((1,) + getattr(self, name).shape[1:], dtype=getattr(self, name).dtype))
                  for name in ("descriptors", "keypoints", "scores", "xyzs", "point3D_ids", "keypoint_segs", "frame_norm")}
-            for name in ("sel_rows", "hist_label", "hist_cnt", "lm_frame", "lm_sel_off", "lm_sel_len", "frame_off", "hist_off"):
+            for name in ("sel_rows", "hist_label", "hist_cnt", "lm_frame", "lm_sel_off", "lm_sel_len", "frame_off", "hist_off",
+                         "pt_ids", "pt_off", "pt_frames", "is_vrf", "covis_off", "covis_frames", "covis_count"):
                 t[name] = up(pad(getattr(self, name)))
-            t.update(n_rows=self.n_rows, n_frames=self.n_frames, n_landmarks=len(self.lm_frame), start_sid=self.start_sid)
+            t.update(n_rows=self.n_rows, n_frames=self.n_frames, n_landmarks=len(self.lm_frame), start_sid=self.start_sid,
+                     n_points=len(self.pt_ids), n_pt_entries=len(self.pt_frames), n_covis=len(self.covis_frames),
+                     covisibility_frame=self.covisibility_frame)
             self._dev[key] = t
         return self._dev[key]
 
@@ -220,6 +308,13 @@ def _match_pairs(features: dict, recognition, store: ReferenceStore, matcher, *,
     m: the matcher's outputs)."""
     planned = plan_candidates(features, recognition, store, seg_k=seg_k, min_kpts=min_kpts, semantic_matching=semantic_matching,
                               overlap_ratio=overlap_ratio)
+    return _match_planned(features, planned, store, matcher)
+
+
+@torch.no_grad()
+def _match_planned(features: dict, planned: dict, store: ReferenceStore, matcher):
+    """_match_pairs from a plan table on: gather, ONE grouped matcher call, correspondences.  The refinement hands its own plan
+    over (localization/refine.py); planned = dict(plan, vote = dict(tokens))."""
     data = gather_candidates(features, planned, store)
     host, t0 = data.pop("plan_host"), data.pop("t0")
     net = getattr(matcher, "net", matcher)

@@ -84,8 +84,20 @@ def localize_candidates(features: dict, recognition, store, matcher, cameras, *,
     -> per query a dict: success (a candidate was kept), tracking_status (True / False / None), qvec (w, x, y, z), tvec, num_inliers,
     inliers (bool [n_matches]), order, reference_frame_id, sid and the matched_* tensors of the kept candidate cut to n_matches,
     plus candidates: the per-candidate list of match_candidates, each with success, qvec, tvec, num_inliers and inliers (padded)."""
-    cor, host, m = _cand._match_pairs(features, recognition, store, matcher, seg_k=seg_k, min_kpts=min_kpts,
-                                      semantic_matching=semantic_matching, overlap_ratio=overlap_ratio)
+    return _localize(features, recognition, store, matcher, cameras, seg_k=seg_k, min_kpts=min_kpts, threshold=threshold,
+                     min_inliers=min_inliers, semantic_matching=semantic_matching, overlap_ratio=overlap_ratio, trials=trials,
+                     min_inlier_ratio=min_inlier_ratio, refine_iters=refine_iters, seed=seed)[0]
+
+
+@torch.no_grad()
+def _localize(features: dict, recognition, store, matcher, cameras, *, seg_k: int, min_kpts: int, threshold: float, min_inliers: int,
+              semantic_matching: bool, overlap_ratio: float, trials: int, min_inlier_ratio: float, refine_iters: int, seed: int):
+    """localize_candidates' body -> (its result, state): state keeps what stays on the device for a later stage (the refinement):
+    chosen int32 [B, 3], plan, tokens, cor (pram_cand_correspond's outputs), est (the per-pair estimates), seg_k, plus the
+    read-back selection sel [B, 3] on the host."""
+    planned = _cand.plan_candidates(features, recognition, store, seg_k=seg_k, min_kpts=min_kpts, semantic_matching=semantic_matching,
+                                    overlap_ratio=overlap_ratio)
+    cor, host, m = _cand._match_planned(features, planned, store, matcher)
     B = features["counts"].numel()
     est = estimate_poses(cor["matched_keypoints"], cor["matched_xyzs"], cor["count"], cameras, seg_k=seg_k, threshold=threshold, trials=trials,
                          min_inlier_ratio=min_inlier_ratio, refine_iters=refine_iters, seed=seed)
@@ -113,4 +125,5 @@ def localize_candidates(features: dict, recognition, store, matcher, cameras, *,
         else:
             r.update(qvec=None, tvec=None, num_inliers=0, inliers=None, order=-1, reference_frame_id=None, sid=None)
         out.append(r)
-    return out
+    state = {"chosen": chosen, "plan": planned["plan"], "tokens": planned["vote"]["tokens"], "cor": cor, "est": est, "seg_k": seg_k, "sel": sel}
+    return out, state

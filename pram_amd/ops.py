@@ -1657,3 +1657,93 @@ def pose_select(success: torch.Tensor, num_inliers: torch.Tensor, seg_k: int, mi
     chosen = torch.empty(B, 3, device=success.device, dtype=torch.int32)
     _lib.check(L.pram_pose_select(_p(success), _p(num_inliers), B, seg_k, int(min_inliers), _p(chosen), _st()), "pram_pose_select")
     return chosen
+
+
+# ---- pose refinement by matching over covisible frames (csrc/refine.hip; pram_amd/localization/refine.py drives these) ---------
+def refine_plan(chosen: torch.Tensor, loc_plan: torch.Tensor, counts: torch.Tensor, store, n_cov: int, enable: Optional[torch.Tensor] = None):
+    """chosen int32 [B, 3] (pose_select), loc_plan int32 [CAND_PLAN_COLS, B * seg_k], counts int32 [B], ``store``: the device tables
+    of a ReferenceStore -> (plan int32 [CAND_PLAN_COLS, B * n_cov], ref_frame, n_cov_used, init_on int32 [B])."""
+    L = _lib.load()
+    for t, nm in ((chosen, "chosen"), (loc_plan, "plan"), (counts, "counts")) + (((enable, "enable"),) if enable is not None else ()):
+        _chk(t, nm, torch.int32)
+        assert t.is_contiguous(), nm
+    B, n_cov = counts.numel(), int(n_cov)
+    assert tuple(chosen.shape) == (B, 3) and loc_plan.dim() == 2 and loc_plan.shape[0] == CAND_PLAN_COLS and (enable is None or enable.numel() == B)
+    seg_k = loc_plan.shape[1] // B if B else 1
+    assert seg_k >= 1 and loc_plan.shape[1] == B * seg_k
+    dev = counts.device
+    plan = torch.empty(CAND_PLAN_COLS, B * max(n_cov, 0), device=dev, dtype=torch.int32)
+    ref_frame, used, init_on = (torch.empty(B, device=dev, dtype=torch.int32) for _ in range(3))
+    s = store
+    _lib.check(L.pram_refine_plan(_p(chosen), _p(loc_plan), _p(counts), _p(enable), _p(s["frame_off"]), _p(s["covis_off"]), _p(s["covis_frames"]),
+                                  B, seg_k, n_cov, int(s["n_frames"]), int(s["n_covis"]), _p(plan), _p(ref_frame), _p(used), _p(init_on), _st()),
+               "pram_refine_plan")
+    return plan, ref_frame, used, init_on
+
+
+_COR_KEYS = ("matched_keypoint_ids", "matched_keypoints", "matched_ref_keypoints", "matched_point3D_ids", "matched_xyzs", "matched_sids")
+
+
+def _cor_chk(cor: dict, name: str):
+    dts = (_INT64, torch.float32, torch.float32, _INT64, torch.float64, torch.int32)
+    P, t = cor["matched_keypoint_ids"].shape
+    tails = ((), (2,), (2,), (), (3,), ())
+    for k, dt, tail in zip(_COR_KEYS, dts, tails):
+        _chk(cor[k], f"{name}.{k}", dt)
+        assert cor[k].is_contiguous() and tuple(cor[k].shape) == (P, t) + tail, (name, k)
+    _chk(cor["count"], f"{name}.count", torch.int32)
+    assert cor["count"].is_contiguous() and cor["count"].numel() == P
+    return P, t
+
+
+def refine_merge(cor_ref: dict, cor_loc: dict, chosen: torch.Tensor, init_on: torch.Tensor, n_cov: int, out: Optional[dict] = None) -> dict:
+    """cor_ref / cor_loc: cand_correspond's dicts for the B * n_cov refinement pairs and the B * seg_k localisation pairs
+    -> one list per query, dict of [B, cap, ...] tensors (cap = n_cov * t0 + t0a) with the keys of cand_correspond plus
+    matched_src int32 and count int32 [B].  ``out``: buffers to write into (the tests pre-fill them)."""
+    L = _lib.load()
+    Pr, t0 = _cor_chk(cor_ref, "refinement")
+    Pa, t0a = _cor_chk(cor_loc, "localisation")
+    _chk(chosen, "chosen", torch.int32)
+    _chk(init_on, "init_on", torch.int32)
+    B, n_cov = init_on.numel(), int(n_cov)
+    assert chosen.is_contiguous() and init_on.is_contiguous() and tuple(chosen.shape) == (B, 3) and Pr == B * n_cov
+    seg_k = Pa // B if B else 1
+    assert seg_k >= 1 and Pa == B * seg_k
+    dev = init_on.device
+    if out is None:
+        cap = max(n_cov * t0 + t0a, 1)
+        out = {"matched_keypoint_ids": torch.empty(B, cap, device=dev, dtype=_INT64), "matched_keypoints": torch.empty(B, cap, 2, device=dev),
+               "matched_ref_keypoints": torch.empty(B, cap, 2, device=dev), "matched_point3D_ids": torch.empty(B, cap, device=dev, dtype=_INT64),
+               "matched_xyzs": torch.empty(B, cap, 3, device=dev, dtype=torch.float64), "matched_sids": torch.empty(B, cap, device=dev, dtype=torch.int32),
+               "matched_src": torch.empty(B, cap, device=dev, dtype=torch.int32), "count": torch.empty(B, device=dev, dtype=torch.int32)}
+    else:
+        _cor_chk(out, "out")
+        _chk(out["matched_src"], "out.matched_src", torch.int32)
+        assert out["matched_src"].is_contiguous() and tuple(out["matched_src"].shape) == tuple(out["matched_sids"].shape) and out["count"].numel() == B
+    cap = out["matched_sids"].shape[1]
+    r, a, o = cor_ref, cor_loc, out
+    _lib.check(L.pram_refine_merge(*[_p(r[k]) for k in _COR_KEYS], _p(r["count"]), t0, *[_p(a[k]) for k in _COR_KEYS], _p(a["count"]), t0a,
+                                   _p(chosen), _p(init_on), B, seg_k, n_cov, cap, *[_p(o[k]) for k in _COR_KEYS], _p(o["matched_src"]),
+                                   _p(o["count"]), _st()), "pram_refine_merge")
+    return out
+
+
+def refine_frame_vote(m_point3d_ids: torch.Tensor, m_count: torch.Tensor, inliers: torch.Tensor, success: torch.Tensor, store, k: int):
+    """find_reference_frames per query over the merged list -> (best_frames int32 [B, k] (store frame indices, -1 padded),
+    best_counts int32 [B, k], n_best int32 [B])."""
+    L = _lib.load()
+    _chk(m_point3d_ids, "matched_point3D_ids", _INT64)
+    _chk(m_count, "count", torch.int32)
+    _chk(inliers, "inliers", torch.uint8)
+    _chk(success, "success", torch.int32)
+    B, cap = m_point3d_ids.shape
+    assert m_point3d_ids.is_contiguous() and m_count.is_contiguous() and inliers.is_contiguous() and success.is_contiguous()
+    assert tuple(inliers.shape) == (B, cap) and m_count.numel() == B and success.numel() == B
+    dev, k, s = m_point3d_ids.device, int(k), store
+    hist = torch.empty(B, max(int(s["n_frames"]), 1), device=dev, dtype=torch.int32)      # zeroed by the entry
+    best_f, best_c = torch.empty(B, max(k, 1), device=dev, dtype=torch.int32), torch.empty(B, max(k, 1), device=dev, dtype=torch.int32)
+    n_best = torch.empty(B, device=dev, dtype=torch.int32)
+    _lib.check(L.pram_refine_frame_vote(_p(m_point3d_ids), _p(m_count), _p(inliers), _p(success), B, cap, _p(s["pt_ids"]), _p(s["pt_off"]),
+                                        _p(s["pt_frames"]), int(s["n_points"]), int(s["n_pt_entries"]), _p(s["is_vrf"]), int(s["n_frames"]), k,
+                                        _p(hist), _p(best_f), _p(best_c), _p(n_best), _st()), "pram_refine_frame_vote")
+    return best_f, best_c, n_best
