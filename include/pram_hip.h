@@ -792,6 +792,64 @@ int pram_refine_frame_vote(const long long* m_point3d_ids, const int* m_count, c
                            int n_entries, const int* is_vrf, int n_frames, int k, int* hist, int* best_frames, int* best_counts,
                            int* n_best, void* stream);
 
+/* ---------------------------------------------------------------- pose refinement by projection over covisible frames
+ * SingleMap3D.refine_pose_by_projection (singlemap3d.py:367-498) for a whole batch of located queries, on the localisation's
+ * device-side state (chosen, loc_plan and the per-pair qvec / tvec of pram_pose_refine) and the store's tables above plus the
+ * per-point values aligned with pt_ids: pt_xyz [n_points][3] float64, pt_desc [n_points][128] float32, pt_sid [n_points] int32
+ * (point3Ds[pid].xyz / .descriptor / .seg_id).  Four entries, run in this order; pram_pose_* (seg_k = 1) and
+ * pram_refine_frame_vote then run on pram_projref_correspond's lists unchanged.  n_points >= 1 everywhere.
+ *
+ * Deviations: a row whose point id is -1 or is not in pt_ids marks nothing (the reference raises KeyError at :392); the
+ * reference's in-place append of the reference frame to its graph list (:381) is not reproduced, the frame is one more slot.
+ *
+ * singlemap3d.py:378-387.  Grid (n_cov + 1, batch), one workgroup per (slot, query), threads over the rows of the slot's frame.
+ * Slots j < n_cov: entry j of the covisible list of the kept candidate's frame, the list cut to n_cov (chosen, loc_plan, enable,
+ * covis_* as in pram_refine_plan); slot n_cov: that frame itself when the cut list does not hold it (:380-381).  Every row's
+ * point id (point3d_ids [n_rows], rows frame_off[g] .. frame_off[g + 1]) is looked up in pt_ids by binary search and its bit set
+ * in bitmap [batch][ceil(n_points / 32)] (bit i & 31 of word i >> 5), which the entry zeroes, by an integer atomic OR.  A query
+ * that is not located or not enabled marks nothing; ref_frame [batch] = the kept frame's store index, or -1. */
+int pram_projref_mark(const int* chosen, const int* loc_plan, const int* enable, const int* frame_off, const int* covis_off,
+                      const int* covis_frames, const long long* point3d_ids, const long long* pt_ids, int batch, int seg_k,
+                      int n_cov, int n_frames, int n_covis, int n_rows, int n_points, unsigned int* bitmap, int* ref_frame,
+                      void* stream);
+
+/* singlemap3d.py:369-377, 387-415.  One workgroup per query: the marked points in ascending table index (= ascending point id,
+ * np.unique's order at :387), n_union [batch] of them; each projected in float64, p = K (R X + t) in pram_project_points_f64's
+ * operation order, R from qvec [batch * seg_k][4] (w, x, y, z) by qvec2rotmat's formula in its operation order and t = tvec
+ * [batch * seg_k][3] of pair b * seg_k + chosen[b][0]; K from cam_model / cam_params [batch][PRAM_POSE_CAM_PARAMS] by
+ * Frame.get_intrinsics' mapping (frame.py:154-175: f, cx, cy for SIMPLE_PINHOLE, SIMPLE_RADIAL, RADIAL; fx, fy, cx, cy for
+ * PINHOLE, OPENCV; no distortion, :401).  Kept: 0 < p2 < 100, 0 <= u < width, 0 <= v < height with image_size [batch][2] int32
+ * (width, height).  Ordered compaction into cand_pt [batch][cap] (point-table indices), cand_uv [batch][2][cap] (u row, v row),
+ * n_cand [batch].  cap >= the marked points of any query (min(n_points, (n_cov + 1) * the largest frame) always is; marks beyond
+ * cap are dropped).  Entries of cand_pt / cand_uv at and beyond n_cand[b] are unspecified. */
+int pram_projref_project(const unsigned int* bitmap, int n_points, const double* pt_xyz, const int* chosen, const double* qvec,
+                         const double* tvec, const int* cam_model, const double* cam_params, const int* image_size, int batch,
+                         int seg_k, int cap, int* cand_pt, double* cand_uv, int* n_union, int* n_cand, void* stream);
+
+/* singlemap3d.py:423-437, fused: no [keypoints][candidates] matrix is written.  One wave per (query b, keypoint i < n); a keypoint
+ * i >= counts[b] gets best -1, d0 = d1 = +inf, accept 0.  Over the query's candidates c < n_cand[b] in ascending order: the pixel
+ * error sqrt((kx - u)^2 + (ky - v)^2) in float64, the float32 keypoint (q_kpts [batch][n][2]) widened first; c is in range when
+ * that error is NOT >= 2 * threshold.  For in-range candidates only: sim = the 128-term fp32 dot product of q_desc [batch][n][128]
+ * row i with pt_desc row cand_pt[b][c] in ONE fixed order — lane l of the wave forms (q[2l] * r[2l]) + (q[2l + 1] * r[2l + 1]),
+ * then the 64 lane values are summed by a butterfly, lane l adding the value of lane l ^ 32, then ^ 16, 8, 4, 2, 1 — and
+ * d = sqrtf((2 - 2 sim) + 1e-6f); top-2 update with strict <, so the lowest index wins ties.  best [batch][n] = the candidate
+ * index of the smallest d (-1: none in range), d0 / d1 [batch][n] the smallest and second smallest (+inf where there is none),
+ * accept [batch][n] = 1 iff n_cand[b] >= 2 and (exactly one candidate is in range, or two or more and d0 / d1 <= 0.995f).
+ * Those are the reference's decisions: an out-of-range candidate carries + 100 there, so it never displaces an in-range one from
+ * the top-2, and against it the ratio is at most about 0.02.  threshold > 0, finite. */
+int pram_projref_match(const float* q_kpts, const float* q_desc, const int* counts, int batch, int n, const int* cand_pt,
+                       const double* cand_uv, const int* n_cand, int cap, const float* pt_desc, int n_points, double threshold,
+                       int* best, float* d0, float* d1, unsigned char* accept, void* stream);
+
+/* singlemap3d.py:446-450.  One workgroup per query: the accepted keypoints i < counts[b] in ascending index, in
+ * pram_cand_correspond's layout with n rows per query: m_kpt_ids [batch][n] int64, m_kpts [batch][n][2] float32, m_point3d_ids
+ * [batch][n] int64 (pt_ids), m_xyz [batch][n][3] float64 (pt_xyz, copied as 64-bit words), m_sids [batch][n] int32 (pt_sid),
+ * m_count [batch]; rows at and beyond m_count[b] are not written. */
+int pram_projref_correspond(const unsigned char* accept, const int* best, const int* counts, const float* q_kpts, int batch, int n,
+                            const int* cand_pt, const int* n_cand, int cap, const long long* pt_ids, const double* pt_xyz,
+                            const int* pt_sid, int n_points, long long* m_kpt_ids, float* m_kpts, long long* m_point3d_ids,
+                            double* m_xyz, int* m_sids, int* m_count, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

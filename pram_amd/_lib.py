@@ -114,6 +114,10 @@ _SIGS = {
     "pram_refine_plan": (I, [P, P, P, P, P, P, P, I, I, I, I, I, P, P, P, P, P]),
     "pram_refine_merge": (I, [P, P, P, P, P, P, P, I, P, P, P, P, P, P, P, I, P, P, I, I, I, I, P, P, P, P, P, P, P, P, P]),
     "pram_refine_frame_vote": (I, [P, P, P, P, I, I, P, P, P, I, I, P, I, I, P, P, P, P, P]),
+    "pram_projref_mark": (I, [P, P, P, P, P, P, P, P, I, I, I, I, I, I, I, P, P, P]),
+    "pram_projref_project": (I, [P, I, P, P, P, P, P, P, P, I, I, I, P, P, P, P, P]),
+    "pram_projref_match": (I, [P, P, P, I, I, P, P, P, I, P, I, C.c_double, P, P, P, P, P]),
+    "pram_projref_correspond": (I, [P, P, P, P, I, I, P, P, I, P, P, P, I, P, P, P, P, P, P, P]),
 }
 
 

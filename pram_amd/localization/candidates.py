@@ -42,10 +42,18 @@ class ReferenceStore:
     named ANYWHERE in seg_ref_frame_ids; for each of them the covisibility graph (covis_off / covis_frames / covis_count, CSR
     over all frames, empty for the others) lists the covisibility_frame frames sharing most points with it: per row of the frame
     with a known point id (not -1), every frame of that point's list counts once, the frame itself included.  Where the reference
-    leaves ties to argsort / argpartition the order here is (count descending, store frame index ascending), at the cut too."""
+    leaves ties to argsort / argpartition the order here is (count descending, store frame index ascending), at the cut too.
+
+    For the refinement by projection (singlemap3d.py:387-399 reads point3Ds[pid].xyz / .descriptor / .seg_id): point3D_xyzs,
+    point3D_descriptors, point3D_sids, dicts from point id to value, become pt_xyz [n_points, 3] float64, pt_desc [n_points, 128]
+    float32 and pt_sid [n_points] int32, aligned with pt_ids.  A point a dict does not name (None: every point) takes the value of
+    the first row, in store order, that carries its id (the row's xyz, descriptor and keypoint_segs); a point that neither covers
+    is a ValueError — raised by the constructor when one of the three arguments is given, and otherwise where the values are
+    first asked for (a point table that only votes may name points without rows).  point_tables() uploads them; tables() keeps
+    the keys it had."""
 
     def __init__(self, frames: Sequence[dict], seg_ref_frame_ids, start_sid: int = 0, device=None, *, point3D_frame_ids=None,
-                 covisibility_frame: int = 20):
+                 covisibility_frame: int = 20, point3D_xyzs=None, point3D_descriptors=None, point3D_sids=None):
         frames = list(frames)
         for i, f in enumerate(frames):
             missing = [k for k in _FRAME_KEYS if k not in f]
@@ -117,7 +125,14 @@ class ReferenceStore:
                     self.is_vrf[index_of[fid]] = 1
         self._build_point_table(point3D_frame_ids, index_of)
         self._build_covisibility()
+        # a store whose point table names points without rows (a vote-only table) stays valid as long as nobody asks for the
+        # per-point values: without the three arguments they are derived, and checked, on first use
+        self._pt_given = (point3D_xyzs, point3D_descriptors, point3D_sids)
+        self._pt_values: Optional[dict] = None
+        if any(g is not None for g in self._pt_given):
+            self._point_values()
         self._dev: Dict[str, dict] = {}
+        self._dev_points: Dict[str, dict] = {}
         if device is not None:
             self.tables(device)
 
@@ -155,6 +170,39 @@ class ReferenceStore:
         self.pt_ids = np.ascontiguousarray(self.pt_ids, dtype=np.int64)
         self.pt_off = np.zeros(len(self.pt_ids) + 1, dtype=np.int32)
         self.pt_off[1:] = np.cumsum(lens)
+
+    pt_xyz = property(lambda self: self._point_values()["pt_xyz"])
+    pt_desc = property(lambda self: self._point_values()["pt_desc"])
+    pt_sid = property(lambda self: self._point_values()["pt_sid"])
+
+    def _point_values(self) -> dict:
+        if self._pt_values is not None:
+            return self._pt_values
+        xyzs, descriptors, sids = self._pt_given
+        out = {}
+        n = len(self.pt_ids)
+        rows = np.nonzero(self.point3D_ids != -1)[0]
+        pi = np.searchsorted(self.pt_ids, self.point3D_ids[rows])
+        ok = pi < n
+        ok[ok] = self.pt_ids[pi[ok]] == self.point3D_ids[rows][ok]
+        has, at = np.unique(pi[ok], return_index=True)      # the first row, in store order, of every point that has one
+        first = rows[ok][at]
+        index_of = {int(p): i for i, p in enumerate(self.pt_ids.tolist())}
+        for name, given, src, dt, tail in (("pt_xyz", xyzs, self.xyzs, np.float64, (3,)), ("pt_desc", descriptors, self.descriptors, np.float32, (128,)),
+                                           ("pt_sid", sids, self.keypoint_segs, np.int32, ())):
+            val = np.zeros((n,) + tail, dtype=dt)
+            covered = np.zeros(n, dtype=bool)
+            val[has], covered[has] = src[first], True
+            for pid, v in (given or {}).items():
+                i = index_of.get(int(pid))
+                if i is not None:      # ids outside the point table are passed over
+                    val[i], covered[i] = np.asarray(v, dtype=dt).reshape(tail), True
+            if not covered.all():
+                raise ValueError(f"{name}: {int((~covered).sum())} points of the point table have neither a value nor a row, "
+                                 f"e.g. point id {int(self.pt_ids[np.argmin(covered)])}")
+            out[name] = val
+        self._pt_values = out
+        return out
 
     def _build_covisibility(self) -> None:
         """build_covisibility_graph (singlemap3d.py:228-258) for all vrf frames at once: every (row of a vrf frame, entry of its
@@ -228,6 +276,17 @@ class ReferenceStore:
                      covisibility_frame=self.covisibility_frame)
             self._dev[key] = t
         return self._dev[key]
+
+    def point_tables(self, device) -> dict:
+        """tables() plus the per-point values pt_xyz, pt_desc, pt_sid (uploaded on first use, then resident, padded like the
+        others): what the refinement by projection reads."""
+        t = self.tables(device)
+        key = str(torch.device(device))
+        if key not in self._dev_points:
+            pad = lambda a: np.concatenate([a, np.zeros((1,) + a.shape[1:], dtype=a.dtype)])
+            self._dev_points[key] = {**t, **{name: torch.from_numpy(np.ascontiguousarray(pad(getattr(self, name)))).to(t["pt_ids"].device)
+                                             for name in ("pt_xyz", "pt_desc", "pt_sid")}}
+        return self._dev_points[key]
 
 
 def _query_norm(features: dict):

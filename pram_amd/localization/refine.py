@@ -1,4 +1,5 @@
-"""Pose refinement by matching over covisible frames, on the device.
+"""Pose refinement over covisible frames, on the device: by matching (refine_by_matching) and by projection
+(refine_by_projection, at the end of this file with its own notes).
 
 Reference: SingleMap3D.refine_pose_by_matching (localization/singlemap3d.py:268-365) as MultiMap3D.run calls it after a query is
 located (multimap3d.py:245-271), with build_covisibility_graph (singlemap3d.py:228-258) and find_reference_frames
@@ -97,20 +98,141 @@ def refine_by_matching(features: dict, state: dict, store, matcher, cameras, *, 
     return out
 
 
+def image_size_table(cameras) -> np.ndarray:
+    """camera tuples (model_name, width, height, params) -> int32 [B, 2] (width, height)."""
+    return np.array([[int(c[1]), int(c[2])] for c in cameras], dtype=np.int32).reshape(-1, 2)
+
+
+_PROJ_MATCHED = ("matched_keypoints", "matched_keypoint_ids", "matched_xyzs", "matched_point3D_ids", "matched_sids")
+
+
+@torch.no_grad()
+def refine_by_projection(features: dict, state: dict, store, cameras, *, threshold: float, covisibility_frame: Optional[int] = None,
+                         trials: int = 1000, min_inlier_ratio: float = 0.01, refine_iters: int = _pose.DEFAULT_REFINE_ITERS, seed: int = 0,
+                         enable=None, image_sizes=None) -> List[Optional[dict]]:
+    """SingleMap3D.refine_pose_by_projection (singlemap3d.py:367-498) for all located queries of a batch: the points the frames
+    covisible with the localisation's reference frame observe (and that frame's own) are projected with the localisation's pose,
+    every keypoint is matched against the points projecting within 2 * threshold pixels of it (descriptor distance, 0.995 ratio
+    test), one pose is estimated on those matches and they vote for the new reference frames.
+
+    Stages: pram_projref_mark, pram_projref_project, pram_projref_match, pram_projref_correspond, the four pose kernels,
+    pram_refine_frame_vote.  ONE host synchronisation, the read-back of the per-query results; every buffer is sized on the host
+    (candidates per query: min(n_points, (n_cov + 1) * store.max_frame_rows)).  No network runs, PRAM_PRECISION does not apply:
+    the projection is float64, the descriptor products fp32.
+
+    Arguments as refine_by_matching's, without the matcher.  image_sizes: int32 [B, 2] (width, height), needed when ``cameras`` is
+    device_cameras' result (camera tuples carry them).  -> per query None (not located, or not enabled) or success, qvec, tvec,
+    num_inliers, inliers, the matched_* lists (keypoints, keypoint ids, xyzs, point ids, landmarks: what the reference returns),
+    refinement_reference_frame_ids, reference_frame_id, plus n_union (points marked), n_projected (points in the frustum) and dists
+    [n_query_kpts, 2] (smallest and second smallest in-range descriptor distance, +inf where there is none).
+
+    Deviations: the pose stage's, as in refine_by_matching; rows with point id -1 or an id outside the point
+    table mark nothing (the reference raises KeyError); a failed solver comes back with success False and zeros and the vote over
+    all matched ids (the reference fails at its own print of ret['num_inliers']); with an empty vote reference_frame_id stays the
+    localisation's."""
+    counts = features["counts"]
+    ops._chk(counts, "counts", torch.int32)
+    dev, B = counts.device, counts.numel()
+    n_cov = int(store.covisibility_frame if covisibility_frame is None else covisibility_frame)
+    if n_cov < 1:
+        raise ValueError("covisibility_frame < 1")
+    if B == 0:
+        return []
+    resident = isinstance(cameras, tuple) and len(cameras) == 3 and torch.is_tensor(cameras[0])
+    if image_sizes is None:
+        if resident:
+            raise ValueError("refine_by_projection: image_sizes is needed when cameras is device_cameras' result")
+        image_sizes = image_size_table(cameras)
+    if not torch.is_tensor(image_sizes):
+        image_sizes = torch.from_numpy(np.ascontiguousarray(np.asarray(image_sizes, dtype=np.int32).reshape(-1, 2)))
+    image_sizes = image_sizes.to(device=dev, dtype=torch.int32).contiguous()
+    if tuple(image_sizes.shape) != (B, 2):
+        raise ValueError("image_sizes: expected one (width, height) per query")
+    tables = store.point_tables(dev)
+    if int(tables["n_points"]) < 1:
+        return [None] * B      # a map without points: nothing to project
+    if enable is not None:
+        enable = torch.as_tensor(np.asarray(enable.cpu() if torch.is_tensor(enable) else enable).astype(np.int32).reshape(-1)).to(dev)
+        if enable.numel() != B:
+            raise ValueError("enable: expected one entry per query")
+    cams = _pose._device_cameras(cameras, dev)
+    chosen, loc = state["chosen"], state["est"]
+    cap = max(1, min(int(tables["n_points"]), (n_cov + 1) * store.max_frame_rows))
+    bitmap, ref_frame = ops.projref_mark(chosen, state["plan"], tables, n_cov, enable)
+    cand_pt, cand_uv, n_union, n_cand = ops.projref_project(bitmap, chosen, loc["qvec"].contiguous(), loc["tvec"].contiguous(), cams[0], cams[1],
+                                                            image_sizes, tables, cap)
+    kpts = features["keypoints"].contiguous()
+    best, d0, d1, accept = ops.projref_match(kpts, features["descriptors"].contiguous(), counts.contiguous(), cand_pt, cand_uv, n_cand, tables,
+                                             threshold)
+    cor = ops.projref_correspond(accept, best, counts.contiguous(), kpts, cand_pt, n_cand, tables)
+    est = _pose.estimate_poses(cor["matched_keypoints"], cor["matched_xyzs"], cor["count"], cams, seg_k=1, threshold=threshold, trials=trials,
+                               min_inlier_ratio=min_inlier_ratio, refine_iters=refine_iters, seed=seed)
+    k = max(1, min(n_cov, store.n_frames))
+    best_f, _, n_best = ops.refine_frame_vote(cor["matched_point3D_ids"], cor["count"], est["inliers"], est["success"], tables, k)
+    # the one read-back: 7 doubles and 8 + k ints per query
+    ints = torch.stack([est["success"], est["num_inliers"], cor["count"], ref_frame, n_union, n_cand, n_best, counts], 1)
+    packed = torch.cat([est["qvec"], est["tvec"], ints.double(), best_f.double()], 1).cpu().numpy()
+    dists = torch.stack([d0, d1], 2)
+    out: List[Optional[dict]] = []
+    for b in range(B):
+        succ, ninl, n, rf, nu, nc, nb, nq = (int(v) for v in packed[b, 7:15])
+        if rf < 0:
+            out.append(None)
+            continue
+        frames = [store.frame_ids[int(i)] for i in packed[b, 15:15 + nb]]
+        r = {"success": bool(succ), "qvec": packed[b, :4].copy(), "tvec": packed[b, 4:7].copy(), "num_inliers": ninl,
+             "inliers": est["inliers"][b, :n].bool(), "refinement_reference_frame_ids": frames,
+             "reference_frame_id": frames[0] if frames else store.frame_ids[rf], "n_union": nu, "n_projected": nc,
+             "dists": dists[b, :max(0, min(nq, dists.shape[1]))]}
+        r.update({key: cor[key][b, :n] for key in _PROJ_MATCHED})
+        out.append(r)
+    return out
+
+
 @torch.no_grad()
 def localize_and_refine(features: dict, recognition, store, matcher, cameras, *, seg_k: int, min_kpts: int, threshold: float,
                         min_inliers: int, semantic_matching: bool = True, overlap_ratio: float = 0.5, trials: int = 1000,
                         min_inlier_ratio: float = 0.01, refine_iters: int = _pose.DEFAULT_REFINE_ITERS, seed: int = 0,
-                        covisibility_frame: Optional[int] = None, enable=None) -> List[dict]:
-    """localize_candidates, then refine_by_matching on its device-side state (do_refinement: true with refinement_method
-    'matching', multimap3d.py:245-271).  -> per query localize_candidates' dict plus ``refinement``: refine_by_matching's dict, or
-    None for a query that was not refined; the localisation's entries are left as they are (a failed refinement changes nothing).
-    Four host synchronisations in all: two per stage."""
+                        covisibility_frame: Optional[int] = None, enable=None, refinement_method: str = "matching",
+                        projection_min_inliers: int = 64, image_sizes=None) -> List[dict]:
+    """localize_candidates, then the refinement on its device-side state (do_refinement: true, multimap3d.py:245-271).
+    refinement_method 'matching': refine_by_matching for every located query.  'projection': a query with tracking status True and
+    num_inliers >= projection_min_inliers goes to refine_by_projection, every other located query to refine_by_matching
+    (multimap3d.py:245-255); the two groups are the two functions' enable masks, built from what the localisation read back, and
+    a function whose group is empty is not called.  Any other value: NotImplementedError (singlemap3d.py:266).
+    -> per query localize_candidates' dict plus ``refinement``: the refining function's dict with ``method`` ('matching' or
+    'projection'), or None for a query that was not refined; the localisation's entries are left as they are (a failed refinement
+    changes nothing).  Host synchronisations: two for the localisation, two for the matching form, one for the projection form."""
+    if refinement_method not in ("matching", "projection"):
+        raise NotImplementedError(f"refinement_method {refinement_method!r}")
     out, state = _pose._localize(features, recognition, store, matcher, cameras, seg_k=seg_k, min_kpts=min_kpts, threshold=threshold,
                                  min_inliers=min_inliers, semantic_matching=semantic_matching, overlap_ratio=overlap_ratio, trials=trials,
                                  min_inlier_ratio=min_inlier_ratio, refine_iters=refine_iters, seed=seed)
-    ref = refine_by_matching(features, state, store, matcher, cameras, threshold=threshold, covisibility_frame=covisibility_frame, trials=trials,
-                             min_inlier_ratio=min_inlier_ratio, refine_iters=refine_iters, seed=seed, enable=enable)
+    kw = dict(threshold=threshold, covisibility_frame=covisibility_frame, trials=trials, min_inlier_ratio=min_inlier_ratio, refine_iters=refine_iters,
+              seed=seed)
+    if refinement_method == "matching":
+        ref = refine_by_matching(features, state, store, matcher, cameras, enable=enable, **kw)
+        for r, x in zip(out, ref):
+            if x is not None:
+                x["method"] = "matching"
+            r["refinement"] = x
+        return out
+    B = len(out)
+    on = np.ones(B, dtype=bool) if enable is None else np.asarray(enable.cpu() if torch.is_tensor(enable) else enable).astype(bool).reshape(-1)
+    if on.size != B:
+        raise ValueError("enable: expected one entry per query")
+    located = np.array([r["success"] for r in out], dtype=bool)
+    strong = np.array([bool(r["tracking_status"]) and r["num_inliers"] >= projection_min_inliers for r in out], dtype=bool)
+    by_proj, by_match = on & located & strong, on & located & ~strong
+    ref: List[Optional[dict]] = [None] * B
+    for mask, name, run in ((by_proj, "projection", lambda m: refine_by_projection(features, state, store, cameras, enable=m, image_sizes=image_sizes, **kw)),
+                            (by_match, "matching", lambda m: refine_by_matching(features, state, store, matcher, cameras, enable=m, **kw))):
+        if not mask.any():
+            continue
+        for b, x in enumerate(run(mask.astype(np.int32))):
+            if x is not None and mask[b]:
+                x["method"] = name
+                ref[b] = x
     for r, x in zip(out, ref):
         r["refinement"] = x
     return out

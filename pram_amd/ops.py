@@ -1747,3 +1747,109 @@ def refine_frame_vote(m_point3d_ids: torch.Tensor, m_count: torch.Tensor, inlier
                                         _p(s["pt_frames"]), int(s["n_points"]), int(s["n_pt_entries"]), _p(s["is_vrf"]), int(s["n_frames"]), k,
                                         _p(hist), _p(best_f), _p(best_c), _p(n_best), _st()), "pram_refine_frame_vote")
     return best_f, best_c, n_best
+
+
+# ---- pose refinement by projection over covisible frames (csrc/projref.hip; pram_amd/localization/refine.py drives these) ------
+def projref_mark(chosen: torch.Tensor, loc_plan: torch.Tensor, store, n_cov: int, enable: Optional[torch.Tensor] = None):
+    """chosen int32 [B, 3], loc_plan int32 [CAND_PLAN_COLS, B * seg_k], ``store``: the device tables of a ReferenceStore
+    -> (bitmap int32 [B, ceil(n_points / 32)] over the point table, ref_frame int32 [B])."""
+    L = _lib.load()
+    for t, nm in ((chosen, "chosen"), (loc_plan, "plan")) + (((enable, "enable"),) if enable is not None else ()):
+        _chk(t, nm, torch.int32)
+        assert t.is_contiguous(), nm
+    B, n_cov, s = chosen.shape[0], int(n_cov), store
+    assert tuple(chosen.shape) == (B, 3) and loc_plan.dim() == 2 and loc_plan.shape[0] == CAND_PLAN_COLS and (enable is None or enable.numel() == B)
+    seg_k = loc_plan.shape[1] // B if B else 1
+    assert seg_k >= 1 and loc_plan.shape[1] == B * seg_k
+    n_points, dev = int(s["n_points"]), chosen.device
+    bitmap = torch.empty(B, max((n_points + 31) // 32, 1), device=dev, dtype=torch.int32)      # zeroed by the entry
+    ref_frame = torch.empty(B, device=dev, dtype=torch.int32)
+    _lib.check(L.pram_projref_mark(_p(chosen), _p(loc_plan), _p(enable), _p(s["frame_off"]), _p(s["covis_off"]), _p(s["covis_frames"]),
+                                   _p(s["point3D_ids"]), _p(s["pt_ids"]), B, seg_k, n_cov, int(s["n_frames"]), int(s["n_covis"]), int(s["n_rows"]),
+                                   n_points, _p(bitmap), _p(ref_frame), _st()), "pram_projref_mark")
+    return bitmap, ref_frame
+
+
+def projref_project(bitmap: torch.Tensor, chosen: torch.Tensor, qvec: torch.Tensor, tvec: torch.Tensor, cam_model: torch.Tensor,
+                    cam_params: torch.Tensor, image_size: torch.Tensor, store, cap: int):
+    """bitmap: projref_mark's; qvec float64 [B * seg_k, 4], tvec [B * seg_k, 3]; cam_model int32 [B], cam_params float64 [B, 8],
+    image_size int32 [B, 2] (width, height); ``store``: ReferenceStore.point_tables
+    -> (cand_pt int32 [B, cap], cand_uv float64 [B, 2, cap], n_union int32 [B], n_cand int32 [B])."""
+    L = _lib.load()
+    for t, nm, dt in ((bitmap, "bitmap", torch.int32), (chosen, "chosen", torch.int32), (qvec, "qvec", torch.float64), (tvec, "tvec", torch.float64),
+                      (cam_model, "cam_model", torch.int32), (cam_params, "cam_params", torch.float64), (image_size, "image_size", torch.int32)):
+        _chk(t, nm, dt)
+        assert t.is_contiguous(), nm
+    B, cap, s = chosen.shape[0], int(cap), store
+    n_points = int(s["n_points"])
+    seg_k = qvec.shape[0] // B if B else 1
+    assert tuple(chosen.shape) == (B, 3) and seg_k >= 1 and tuple(qvec.shape) == (B * seg_k, 4) and tuple(tvec.shape) == (B * seg_k, 3)
+    assert tuple(bitmap.shape) == (B, max((n_points + 31) // 32, 1)) and cam_model.numel() == B and tuple(cam_params.shape) == (B, POSE_CAM_PARAMS)
+    assert tuple(image_size.shape) == (B, 2) and s["pt_xyz"].shape[0] >= n_points
+    dev = chosen.device
+    cand_pt = torch.empty(B, max(cap, 1), device=dev, dtype=torch.int32)
+    cand_uv = torch.empty(B, 2, max(cap, 1), device=dev, dtype=torch.float64)
+    n_union, n_cand = torch.empty(B, device=dev, dtype=torch.int32), torch.empty(B, device=dev, dtype=torch.int32)
+    _lib.check(L.pram_projref_project(_p(bitmap), n_points, _p(s["pt_xyz"]), _p(chosen), _p(qvec), _p(tvec), _p(cam_model), _p(cam_params),
+                                      _p(image_size), B, seg_k, cap, _p(cand_pt), _p(cand_uv), _p(n_union), _p(n_cand), _st()), "pram_projref_project")
+    return cand_pt, cand_uv, n_union, n_cand
+
+
+def projref_match(q_kpts: torch.Tensor, q_desc: torch.Tensor, counts: torch.Tensor, cand_pt: torch.Tensor, cand_uv: torch.Tensor,
+                  n_cand: torch.Tensor, store, threshold: float):
+    """q_kpts [B, N, 2], q_desc [B, N, 128], counts int32 [B]; cand_*: projref_project's; ``store``: ReferenceStore.point_tables
+    -> (best int32 [B, N] (candidate index, -1 none), d0, d1 float32 [B, N] (+inf: none), accept uint8 [B, N])."""
+    L = _lib.load()
+    for t, nm, dt in ((q_kpts, "keypoints", torch.float32), (q_desc, "descriptors", torch.float32), (counts, "counts", torch.int32),
+                      (cand_pt, "cand_pt", torch.int32), (cand_uv, "cand_uv", torch.float64), (n_cand, "n_cand", torch.int32)):
+        _chk(t, nm, dt)
+        assert t.is_contiguous(), nm
+    B, N, D = q_desc.shape
+    cap, s = cand_pt.shape[1], store
+    assert D == 128 and tuple(q_kpts.shape) == (B, N, 2) and counts.numel() == B and n_cand.numel() == B
+    assert tuple(cand_pt.shape) == (B, cap) and tuple(cand_uv.shape) == (B, 2, cap) and s["pt_desc"].shape[0] >= int(s["n_points"])
+    dev = q_desc.device
+    best = torch.empty(B, max(N, 1), device=dev, dtype=torch.int32)[:, :N]
+    d0, d1 = torch.empty(B, max(N, 1), device=dev)[:, :N], torch.empty(B, max(N, 1), device=dev)[:, :N]
+    accept = torch.empty(B, max(N, 1), device=dev, dtype=torch.uint8)[:, :N]
+    if N == 0:      # no keypoints: the empty inputs have no storage to hand to the entry
+        return best, d0, d1, accept
+    _lib.check(L.pram_projref_match(_p(q_kpts), _p(q_desc), _p(counts), B, N, _p(cand_pt), _p(cand_uv), _p(n_cand), cap, _p(s["pt_desc"]),
+                                    int(s["n_points"]), float(threshold), _p(best), _p(d0), _p(d1), _p(accept), _st()), "pram_projref_match")
+    return best, d0, d1, accept
+
+
+def projref_correspond(accept: torch.Tensor, best: torch.Tensor, counts: torch.Tensor, q_kpts: torch.Tensor, cand_pt: torch.Tensor,
+                       n_cand: torch.Tensor, store, out: Optional[dict] = None) -> dict:
+    """-> pram_cand_correspond's layout with N rows per query: matched_keypoint_ids int64 [B, N], matched_keypoints [B, N, 2],
+    matched_point3D_ids int64 [B, N], matched_xyzs float64 [B, N, 3], matched_sids int32 [B, N], count int32 [B].  ``out``: buffers
+    to write into (the tests pre-fill them)."""
+    L = _lib.load()
+    for t, nm, dt in ((accept, "accept", torch.uint8), (best, "best", torch.int32), (counts, "counts", torch.int32), (q_kpts, "keypoints", torch.float32),
+                      (cand_pt, "cand_pt", torch.int32), (n_cand, "n_cand", torch.int32)):
+        _chk(t, nm, dt)
+        assert t.is_contiguous(), nm
+    B, N = accept.shape
+    cap, s, dev = cand_pt.shape[1], store, accept.device
+    assert tuple(best.shape) == (B, N) and tuple(q_kpts.shape) == (B, N, 2) and counts.numel() == B and n_cand.numel() == B and cand_pt.shape[0] == B
+    n1 = max(N, 1)
+    if out is None:
+        out = {"matched_keypoint_ids": torch.empty(B, n1, device=dev, dtype=_INT64), "matched_keypoints": torch.empty(B, n1, 2, device=dev),
+               "matched_point3D_ids": torch.empty(B, n1, device=dev, dtype=_INT64), "matched_xyzs": torch.empty(B, n1, 3, device=dev, dtype=torch.float64),
+               "matched_sids": torch.empty(B, n1, device=dev, dtype=torch.int32), "count": torch.empty(B, device=dev, dtype=torch.int32)}
+    else:
+        for k, dt, tail in (("matched_keypoint_ids", _INT64, ()), ("matched_keypoints", torch.float32, (2,)), ("matched_point3D_ids", _INT64, ()),
+                            ("matched_xyzs", torch.float64, (3,)), ("matched_sids", torch.int32, ())):
+            _chk(out[k], f"out.{k}", dt)
+            assert out[k].is_contiguous() and tuple(out[k].shape) == (B, n1) + tail, k
+        _chk(out["count"], "out.count", torch.int32)
+        assert out["count"].is_contiguous() and out["count"].numel() == B
+    o = out
+    if N == 0:      # no keypoints: the empty inputs have no storage to hand to the entry
+        o["count"].zero_()
+        return out
+    _lib.check(L.pram_projref_correspond(_p(accept), _p(best), _p(counts), _p(q_kpts), B, N, _p(cand_pt), _p(n_cand), cap, _p(s["pt_ids"]),
+                                         _p(s["pt_xyz"]), _p(s["pt_sid"]), int(s["n_points"]), _p(o["matched_keypoint_ids"]), _p(o["matched_keypoints"]),
+                                         _p(o["matched_point3D_ids"]), _p(o["matched_xyzs"]), _p(o["matched_sids"]), _p(o["count"]), _st()),
+               "pram_projref_correspond")
+    return out
