@@ -850,6 +850,63 @@ int pram_projref_correspond(const unsigned char* accept, const int* best, const 
                             const int* pt_sid, int n_points, long long* m_kpt_ids, float* m_kpts, long long* m_point3d_ids,
                             double* m_xyz, int* m_sids, int* m_count, void* stream);
 
+/* ---------------------------------------------------------------- tracking the last frame, for a batch of streams
+ * Tracker.track_last_frame (localization/tracker.py:162-233), Frame.initialize_localization_variables / update_point3ds
+ * (frame.py:84-89, 191-195) and the hand-over mTracker.last_frame = curr_frame (loc_by_rec_online.py:193-197) for n_slots
+ * independent streams.  The state (pram_amd/localization/tracker.py::TrackState owns it) holds the last frame of every stream,
+ * slot s = rows s * n_max .. s * n_max + n_max of st_kpts [..][2], st_scores, st_desc [..][128] (16-byte aligned), st_xyz [..][3]
+ * float64, st_point3d_ids int64 (-1 = the row has no point), st_segs int32, with st_counts [n_slots] (rows in use), st_ref_frame
+ * [n_slots] (store index of the frame's reference frame) and st_frame_norm [n_slots][3] (normalize_keypoints' constants of the
+ * frame's camera).  slot [batch] names the state slot of query b (-1 = none; a value outside [0, n_slots) counts as none).  A
+ * tracking pair is a row of the plan table above with the slot in its frame column, so pram_cand_gather runs on
+ * pram_track_plan's table unchanged with the state's arrays as r_desc / r_kpts / r_scores / frame_norm and ref_rows = n_slots *
+ * n_max, and pram_pose_* (seg_k = 1) run on pram_track_correspond's lists.  float64 is moved as 64-bit words; every index read
+ * from a table is checked against the size given beside it before it is used.
+ *
+ * One thread per pair; counts [batch] keypoints per query (stride n).  plan [PRAM_CAND_PLAN_COLS][batch]: query b, sid -1, frame
+ * = slot[b], semantic 0, lens0 = counts[b], lens1 = st_counts[slot[b]], token offset -1, first row slot[b] * n_max, sel offset
+ * -1, order 0; a query without a slot: frame -1, lens0 = lens1 = 0.  loc_plan: the same table with frame = st_ref_frame[slot[b]]
+ * — the one-pair-per-query localisation plan pram_refine_plan and pram_projref_mark read (seg_k = 1).  The padded size of the
+ * grouped matcher call, max(64, round_up(max(n, n_max), 64)), is known on the host: no table is read back. */
+int pram_track_plan(const int* counts, const int* slot, const int* st_counts, const int* st_ref_frame, int batch, int n,
+                    int n_slots, int n_max, int* plan, int* loc_plan, void* stream);
+
+/* tracker.py:195-205.  One workgroup per pair (pairs = batch, pair p = query p).  matches0 [pairs][ldm] (-1 = none; the first
+ * min(lens0, t0) entries of a row are read) -> the query rows i with 0 <= j = matches0[p][i] < lens1 AND st_point3d_ids[slot][j]
+ * >= 0, in ascending i (ordered compaction by ballot and prefix), in pram_cand_correspond's layout [pairs][cap]...: m_kpt_ids
+ * int64 (= i), m_kpts (q_kpts [batch][n][2] rows), m_ref_kpts (the last frame's keypoints), m_point3d_ids, m_xyz (bit for
+ * bit), m_sids (st_segs), m_count [pairs].  Rows at and beyond cap are dropped; rows at and beyond m_count[p] are not written. */
+int pram_track_correspond(const long long* matches0, int ldm, const int* plan, const float* q_kpts, int n, const float* st_kpts,
+                          const double* st_xyz, const long long* st_point3d_ids, const int* st_segs, int n_slots, int n_max,
+                          int pairs, int t0, int cap, long long* m_kpt_ids, float* m_kpts, float* m_ref_kpts,
+                          long long* m_point3d_ids, double* m_xyz, int* m_sids, int* m_count, void* stream);
+
+/* tracker.py:154-160 (ret[...][inliers]).  One workgroup per query: of the first count[b] rows of the six lists [batch][cap]...
+ * those with mask [batch][cap] != 0 (bytes), in order, into lists of the same layout, with o_count [batch].  The outputs must
+ * not be the inputs; rows at and beyond o_count[b] are not written. */
+int pram_track_filter(const long long* kpt_ids, const float* kpts, const float* ref_kpts, const long long* point3d_ids,
+                      const double* xyz, const int* sids, const int* count, const unsigned char* mask, int batch, int cap,
+                      long long* o_kpt_ids, float* o_kpts, float* o_ref_kpts, long long* o_point3d_ids, double* o_xyz,
+                      int* o_sids, int* o_count, void* stream);
+
+/* The located frame becomes its stream's last frame.  For every query b with a slot: (one wave per row, 16-byte loads) the
+ * query's counts[b] keypoints, scores and descriptors (q_* [batch][n]..., n <= n_max) go to the slot's first rows; ALL n_max
+ * rows of the slot get xyz 0 and point id -1; st_segs = seg_ids [batch][n] on the first counts[b] rows (NULL: -1) and -1 beyond;
+ * st_counts = counts[b], st_ref_frame = ref_frame[b], st_frame_norm = (q_cx, q_cy, q_scale).  Then (one workgroup per query) the
+ * list rows r < m_count[b] of m_* [batch][cap]... — with mask [batch][cap] non-NULL only those with mask != 0 — are scattered
+ * to row m_kpt_ids[r] of the slot: xyz, point id and landmark.  A keypoint id outside [0, counts[b]) writes nothing.  Of the
+ * rows naming one keypoint the LAST in list order writes (numpy's fancy assignment, frame.py:87-89), whatever the scheduling:
+ * winner [batch][n] int32, a workspace of the caller which the entry sets to -1, takes an integer atomic max of r per keypoint
+ * id, and after a workgroup barrier the row that equals its keypoint's winner writes.  Slots no query names are not touched,
+ * rows at and beyond counts[b] keep their keypoints, scores and descriptors.  slot_host: a HOST copy of slot, checked here
+ * without touching the device: a slot >= n_slots, or two queries naming one slot -> PRAM_E_ARG. */
+int pram_track_commit(const float* q_kpts, const float* q_scores, const float* q_desc, const int* counts, const int* seg_ids,
+                      const int* slot, const int* slot_host, const int* ref_frame, int batch, int n, float q_cx, float q_cy,
+                      float q_scale, const long long* m_kpt_ids, const long long* m_point3d_ids, const double* m_xyz,
+                      const int* m_sids, const int* m_count, const unsigned char* mask, int cap, float* st_kpts, float* st_scores,
+                      float* st_desc, int* st_counts, double* st_xyz, long long* st_point3d_ids, int* st_segs, int* st_ref_frame,
+                      float* st_frame_norm, int n_slots, int n_max, int* winner, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

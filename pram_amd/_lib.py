@@ -118,6 +118,10 @@ _SIGS = {
     "pram_projref_project": (I, [P, I, P, P, P, P, P, P, P, I, I, I, P, P, P, P, P]),
     "pram_projref_match": (I, [P, P, P, I, I, P, P, P, I, P, I, C.c_double, P, P, P, P, P]),
     "pram_projref_correspond": (I, [P, P, P, P, I, I, P, P, I, P, P, P, I, P, P, P, P, P, P, P]),
+    "pram_track_plan": (I, [P, P, P, P, I, I, I, I, P, P, P]),
+    "pram_track_correspond": (I, [P, I, P, P, I, P, P, P, P, I, I, I, I, I, P, P, P, P, P, P, P, P]),
+    "pram_track_filter": (I, [P, P, P, P, P, P, P, P, I, I, P, P, P, P, P, P, P, P]),
+    "pram_track_commit": (I, [P, P, P, P, P, P, P, P, I, I, F, F, F, P, P, P, P, P, P, I, P, P, P, P, P, P, P, P, P, I, I, P, P]),
 }
 
 

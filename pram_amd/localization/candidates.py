@@ -379,7 +379,9 @@ def _match_planned(features: dict, planned: dict, store: ReferenceStore, matcher
     net = getattr(matcher, "net", matcher)
     m = net.produce_matches(data)      # its own precision / range-guard scopes (nets/_blocks.with_model_precision)
     plan = planned["plan"]
-    cor = ops.cand_correspond(m["matches0"][:, :t0], plan, planned["vote"]["tokens"], store.tables(plan.device),
+    # a batch without a single query keypoint (t0 = 0): an empty slice has no storage to hand over, so one column is passed — no
+    # pair reads it (every lens0 is 0) and the outputs keep their cap of t0 rows
+    cor = ops.cand_correspond(m["matches0"][:, :max(t0, 1)], plan, planned["vote"]["tokens"], store.tables(plan.device),
                               features["keypoints"].contiguous(), t0)
     return cor, host, m
 

@@ -732,7 +732,9 @@ def attention_h16t(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, batch: in
     assert vt.is_contiguous() and vt.dtype == torch.float16
     if out is None:
         out = torch.empty(batch * m_max, heads * 64, device=q.device, dtype=torch.float32)
-    lse = torch.empty(batch, heads, m_max, device=q.device, dtype=torch.float32) if want_lse else None
+    # ragged queries: the kernel writes lse for the rows below q_lens[b] only; the rows beyond are 0, not what the allocator held
+    lse = None if not want_lse else (torch.empty(batch, heads, m_max, device=q.device, dtype=torch.float32) if q_lens is None
+                                     else _filled((batch, heads, m_max), q.device))
     probe = attention_probe
     if probe is not None:
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -1853,3 +1855,124 @@ def projref_correspond(accept: torch.Tensor, best: torch.Tensor, counts: torch.T
                                          _p(o["matched_point3D_ids"]), _p(o["matched_xyzs"]), _p(o["matched_sids"]), _p(o["count"]), _st()),
                "pram_projref_correspond")
     return out
+
+
+# ---- tracking the last frame for a batch of streams (csrc/track.hip; pram_amd/localization/tracker.py drives these) ------------
+def _track_state_chk(st: dict):
+    """st: the arrays of a TrackState (dict: keypoints, scores, descriptors, counts, xyzs, point3D_ids, seg_ids, ref_frame,
+    frame_norm, n_slots, n_max) -> (n_slots, n_max)."""
+    S, n_max = int(st["n_slots"]), int(st["n_max"])
+    for k, dt, shape in (("keypoints", torch.float32, (S, n_max, 2)), ("scores", torch.float32, (S, n_max)), ("descriptors", torch.float32, (S, n_max, 128)),
+                         ("counts", torch.int32, (S,)), ("xyzs", torch.float64, (S, n_max, 3)), ("point3D_ids", _INT64, (S, n_max)),
+                         ("seg_ids", torch.int32, (S, n_max)), ("ref_frame", torch.int32, (S,)), ("frame_norm", torch.float32, (S, 3))):
+        _chk(st[k], f"state.{k}", dt)
+        assert st[k].is_contiguous() and tuple(st[k].shape) == shape, k
+    return S, n_max
+
+
+def track_plan(counts: torch.Tensor, slot: torch.Tensor, st: dict, n: int):
+    """counts, slot int32 [B] -> (plan, loc_plan) int32 [CAND_PLAN_COLS, B] (pram_track_plan)."""
+    L = _lib.load()
+    S, n_max = _track_state_chk(st)
+    _chk(counts, "counts", torch.int32)
+    _chk(slot, "slot", torch.int32)
+    B = counts.numel()
+    assert counts.is_contiguous() and slot.is_contiguous() and slot.numel() == B
+    plan = torch.empty(CAND_PLAN_COLS, B, device=counts.device, dtype=torch.int32)
+    loc_plan = torch.empty(CAND_PLAN_COLS, B, device=counts.device, dtype=torch.int32)
+    if B == 0:      # no queries: the empty tensors have no storage to hand to the entry
+        return plan, loc_plan
+    _lib.check(L.pram_track_plan(_p(counts), _p(slot), _p(st["counts"]), _p(st["ref_frame"]), B, int(n), S, n_max, _p(plan), _p(loc_plan), _st()),
+               "pram_track_plan")
+    return plan, loc_plan
+
+
+def track_gather_tables(st: dict, dummy: torch.Tensor) -> dict:
+    """The state's arrays under the names cand_gather reads from a ReferenceStore's tables (sel_rows: never read, sel offset -1)."""
+    return {"sel_rows": dummy, "descriptors": st["descriptors"], "keypoints": st["keypoints"], "scores": st["scores"], "frame_norm": st["frame_norm"],
+            "n_rows": int(st["n_slots"]) * int(st["n_max"])}
+
+
+def _cor_alloc(B: int, cap: int, dev) -> dict:
+    c1 = max(int(cap), 1)
+    return {"matched_keypoint_ids": torch.empty(B, c1, device=dev, dtype=_INT64), "matched_keypoints": torch.empty(B, c1, 2, device=dev),
+            "matched_ref_keypoints": torch.empty(B, c1, 2, device=dev), "matched_point3D_ids": torch.empty(B, c1, device=dev, dtype=_INT64),
+            "matched_xyzs": torch.empty(B, c1, 3, device=dev, dtype=torch.float64), "matched_sids": torch.empty(B, c1, device=dev, dtype=torch.int32),
+            "count": torch.empty(B, device=dev, dtype=torch.int32)}
+
+
+def track_correspond(matches0: torch.Tensor, plan: torch.Tensor, st: dict, q_kpts: torch.Tensor, cap: int, out: Optional[dict] = None) -> dict:
+    """matches0 int64 [B, >= t0] -> cand_correspond's dict, [B, cap, ...] and count int32 [B] (pram_track_correspond).  ``out``:
+    buffers to write into (the tests pre-fill them)."""
+    L = _lib.load()
+    S, n_max = _track_state_chk(st)
+    _chk(matches0, "matches0", _INT64)
+    _chk(q_kpts, "keypoints")
+    _chk(plan, "plan", torch.int32)
+    assert matches0.dim() == 2 and matches0.stride(1) == 1 and q_kpts.is_contiguous() and plan.is_contiguous()
+    P, t0 = matches0.shape
+    assert tuple(plan.shape) == (CAND_PLAN_COLS, P) and q_kpts.dim() == 3 and q_kpts.shape[0] == P
+    n, cap = q_kpts.shape[1], int(cap)
+    if out is None:
+        out = _cor_alloc(P, cap, matches0.device)
+    else:
+        _cor_chk(out, "out")
+        assert out["matched_sids"].shape[0] == P and out["matched_sids"].shape[1] >= cap
+        cap = out["matched_sids"].shape[1]
+    _lib.check(L.pram_track_correspond(_p(matches0), matches0.stride(0) if P else t0, _p(plan), _p(q_kpts), n, _p(st["keypoints"]), _p(st["xyzs"]),
+                                       _p(st["point3D_ids"]), _p(st["seg_ids"]), S, n_max, P, t0, cap, *[_p(out[k]) for k in _COR_KEYS],
+                                       _p(out["count"]), _st()), "pram_track_correspond")
+    return out
+
+
+def track_filter(cor: dict, mask: torch.Tensor, out: Optional[dict] = None) -> dict:
+    """cor: cand_correspond-shaped lists [B, cap, ...] with count; mask uint8 [B, cap] -> the rows r < count[b] with mask != 0, in
+    order, in new buffers of the same layout (pram_track_filter)."""
+    L = _lib.load()
+    B, cap = _cor_chk(cor, "lists")
+    _chk(mask, "mask", torch.uint8)
+    assert mask.is_contiguous() and tuple(mask.shape) == (B, cap)
+    if out is None:
+        out = _cor_alloc(B, cap, mask.device)
+    else:
+        assert _cor_chk(out, "out") == (B, cap)
+    _lib.check(L.pram_track_filter(*[_p(cor[k]) for k in _COR_KEYS], _p(cor["count"]), _p(mask), B, cap, *[_p(out[k]) for k in _COR_KEYS],
+                                   _p(out["count"]), _st()), "pram_track_filter")
+    return out
+
+
+def track_commit(st: dict, q_kpts: torch.Tensor, q_scores: torch.Tensor, q_desc: torch.Tensor, counts: torch.Tensor, seg_ids: Optional[torch.Tensor],
+                 slot: torch.Tensor, slot_host, ref_frame: torch.Tensor, q_norm, cor: dict, mask: Optional[torch.Tensor] = None,
+                 winner: Optional[torch.Tensor] = None) -> None:
+    """In place on the state (pram_track_commit): the queries with slot >= 0 become their slots' last frames and the list rows of
+    ``cor`` (with ``mask`` uint8 [B, cap]: those with mask != 0) give their keypoints a point.  slot_host: the slots on the host (a
+    sequence of ints), which is what the launcher validates; q_norm = (cx, cy, scale) of the queries' camera."""
+    import ctypes
+    L = _lib.load()
+    S, n_max = _track_state_chk(st)
+    for t, nm, dt in ((q_kpts, "keypoints", torch.float32), (q_scores, "scores", torch.float32), (q_desc, "descriptors", torch.float32),
+                      (counts, "counts", torch.int32), (slot, "slot", torch.int32), (ref_frame, "ref_frame", torch.int32)) + \
+            (((seg_ids, "seg_ids", torch.int32),) if seg_ids is not None else ()) + (((mask, "mask", torch.uint8),) if mask is not None else ()):
+        _chk(t, nm, dt)
+        assert t.is_contiguous(), nm
+    B, n, D = q_desc.shape
+    Bc, cap = cor["matched_keypoint_ids"].shape
+    for k, dt, tail in (("matched_keypoint_ids", _INT64, ()), ("matched_point3D_ids", _INT64, ()), ("matched_xyzs", torch.float64, (3,)),
+                        ("matched_sids", torch.int32, ())):      # the four lists update_point3ds reads
+        _chk(cor[k], f"lists.{k}", dt)
+        assert cor[k].is_contiguous() and tuple(cor[k].shape) == (Bc, cap) + tail, k
+    _chk(cor["count"], "lists.count", torch.int32)
+    assert cor["count"].is_contiguous() and cor["count"].numel() == Bc
+    assert D == 128 and tuple(q_kpts.shape) == (B, n, 2) and tuple(q_scores.shape) == (B, n) and counts.numel() == B and slot.numel() == B
+    assert ref_frame.numel() == B and len(slot_host) == B and Bc == B and (seg_ids is None or tuple(seg_ids.shape) == (B, n))
+    assert mask is None or tuple(mask.shape) == (B, cap)
+    if winner is None:
+        winner = torch.empty(B, max(n, 1), device=q_desc.device, dtype=torch.int32)
+    _chk(winner, "winner", torch.int32)
+    assert winner.is_contiguous() and winner.numel() >= B * n
+    host = (ctypes.c_int * max(B, 1))(*[int(s) for s in slot_host])
+    _lib.check(L.pram_track_commit(_p(q_kpts), _p(q_scores), _p(q_desc), _p(counts), _p(seg_ids), _p(slot), ctypes.addressof(host), _p(ref_frame), B, n,
+                                   float(q_norm[0]), float(q_norm[1]), float(q_norm[2]), _p(cor["matched_keypoint_ids"]), _p(cor["matched_point3D_ids"]),
+                                   _p(cor["matched_xyzs"]), _p(cor["matched_sids"]), _p(cor["count"]), _p(mask), cap, _p(st["keypoints"]),
+                                   _p(st["scores"]), _p(st["descriptors"]), _p(st["counts"]), _p(st["xyzs"]), _p(st["point3D_ids"]), _p(st["seg_ids"]),
+                                   _p(st["ref_frame"]), _p(st["frame_norm"]), S, n_max, _p(winner), _st()), "pram_track_commit")
