@@ -654,6 +654,18 @@ int pram_cand_plan(const int* win_sid, const int* win_count, const int* n_win, c
                    const int* hist_label, const int* hist_cnt, int n_frames, int min_kpts, double overlap_ratio,
                    int semantic_matching, int* plan, void* stream);
 
+/* pram_cand_plan over the tables of SEVERAL maps (pram_amd/localization/multimap.py::MultiMapStore; MultiMap3D.run picks the map
+ * by sid_scene_name[sid] and the in-map id by scene_name_start_sid, multimap3d.py:119-123): lm_frame / lm_sel_off / lm_sel_len
+ * [n_landmarks] are indexed by the GLOBAL landmark id g = vote id - 1 (frames and rows numbered over all maps), and lm_start[g] is
+ * the start_sid of the map that owns g, so in-map id = g - lm_start[g] and the frame's labels are compared as hist_label +
+ * lm_start[g].  g outside [0, n_landmarks), lm_frame[g] < 0 (no map owns g, or no reference frame) and lm_frame[g] >= n_frames
+ * give the empty pair.  Everything else, the checks and statuses included, as pram_cand_plan; the sid column stays g. */
+int pram_cand_plan_maps(const int* win_sid, const int* win_count, const int* n_win, const int* seg_ids, const int* counts,
+                        int batch, int n, int n_class, int seg_k, const int* lm_frame, const int* lm_sel_off,
+                        const int* lm_sel_len, int n_landmarks, const int* lm_start, const int* frame_off, const int* hist_off,
+                        const int* hist_label, const int* hist_cnt, int n_frames, int min_kpts, double overlap_ratio,
+                        int semantic_matching, int* plan, void* stream);
+
 /* The grouped matcher's inputs from the plan, one wave per row: desc0 / desc1 [pairs][t_pad][128], scores0 / scores1
  * [pairs][t_pad], nkpts0 / nkpts1 [pairs][t_pad][2] = keypoints already normalised per pair, (k - (cx, cy)) / scale in fp32 (the
  * operation order of pram_fourier_encoding_f32): the query side with (q_cx, q_cy, q_scale), the reference side with its frame's

@@ -104,6 +104,7 @@ _SIGS = {
     "pram_score_lookup_f32": (I, [P, LL, I, I, P, P, I, I, P, P]),
     "pram_cand_mask_ranks": (I, [P, P, I, I, I, P]),
     "pram_cand_plan": (I, [P, P, P, P, P, I, I, I, I, P, P, P, I, I, P, P, P, P, I, I, C.c_double, I, P, P]),
+    "pram_cand_plan_maps": (I, [P, P, P, P, P, I, I, I, I, P, P, P, I, P, P, P, P, P, I, I, C.c_double, I, P, P]),
     "pram_cand_gather": (I, [P, P, P, P, P, P, I, P, P, P, P, I, F, F, F, P, P, P, P, P, P, I, I, P]),
     "pram_cand_correspond": (I, [P, I, P, P, P, P, I, P, P, P, P, I, I, I, I, P, P, P, P, P, P, P, P]),
     "pram_pose_prepare": (I, [P, P, P, P, P, I, I, I, P, P]),

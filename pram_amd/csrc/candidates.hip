@@ -21,12 +21,17 @@ __global__ __launch_bounds__(256) void cand_mask_ranks_kernel(long long* __restr
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) p[i] = 0;
 }
 
-// one workgroup per (candidate w, query b)
+// one workgroup per (candidate w, query b).  MAPS = false: the tables of ONE map, indexed by the in-map id (global id - start_sid).
+// MAPS = true (a multi-map store): the landmark tables are indexed by the GLOBAL id and lm_start[gsid] is the start_sid of the map
+// that owns it (multimap3d.py:119-123: sid_scene_name picks the map, scene_name_start_sid the in-map id); a reference frame at or
+// beyond n_frames is an empty pair as well.
+template <bool MAPS>
 __global__ __launch_bounds__(256) void cand_plan_kernel(const int* __restrict__ win_sid, const int* __restrict__ win_cnt,
                                                         const int* __restrict__ n_win, const int* __restrict__ seg_ids,
                                                         const int* __restrict__ counts, int n, int seg_k,
                                                         const int* __restrict__ lm_frame, const int* __restrict__ lm_sel_off,
                                                         const int* __restrict__ lm_sel_len, int n_landmarks, int start_sid,
+                                                        const int* __restrict__ lm_start, int n_frames,
                                                         const int* __restrict__ frame_off, const int* __restrict__ hist_off,
                                                         const int* __restrict__ hist_label, const int* __restrict__ hist_cnt,
                                                         int min_kpts, double overlap_ratio, int semantic_on, int* __restrict__ plan) {
@@ -41,8 +46,17 @@ __global__ __launch_bounds__(256) void cand_plan_kernel(const int* __restrict__ 
     nw = nw > seg_k ? seg_k : nw;
     const bool live = w < nw;
     const int gsid = live ? win_sid[b * seg_k + w] - 1 : -1;      // multimap3d.py:119 "start from 0"
-    const int lsid = gsid - start_sid;                            // multimap3d.py:123
-    const int f = (live && lsid >= 0 && lsid < n_landmarks) ? lm_frame[lsid] : -1;
+    int lsid, lm, f;      // in-map id (multimap3d.py:123), the landmark's index in the tables, its reference frame
+    if constexpr (MAPS) {
+        lm = gsid;
+        f = (live && gsid >= 0 && gsid < n_landmarks) ? lm_frame[gsid] : -1;
+        if (f >= n_frames) f = -1;
+        start_sid = f >= 0 ? lm_start[gsid] : 0;
+        lsid = gsid - start_sid;
+    } else {
+        lsid = lm = gsid - start_sid;
+        f = (live && lsid >= 0 && lsid < n_landmarks) ? lm_frame[lsid] : -1;
+    }
     if (f < 0) {      // no such candidate (or a landmark the map has no reference frame for): an empty pair
         if (tid == 0) {
             col[PL_QUERY * pairs] = b; col[PL_SID * pairs] = gsid; col[PL_FRAME * pairs] = -1; col[PL_SEM * pairs] = 0; col[PL_LEN0 * pairs] = 0; col[PL_LEN1 * pairs] = 0;
@@ -83,10 +97,10 @@ __global__ __launch_bounds__(256) void cand_plan_kernel(const int* __restrict__ 
         const bool by_sid = sem && lsid > 0;        // singlemap3d.py:130
         col[PL_QUERY * pairs] = b; col[PL_SID * pairs] = gsid; col[PL_FRAME * pairs] = f; col[PL_SEM * pairs] = sem;
         col[PL_LEN0 * pairs] = sem ? ntok : nq;
-        col[PL_LEN1 * pairs] = by_sid ? lm_sel_len[lsid] : nref;
+        col[PL_LEN1 * pairs] = by_sid ? lm_sel_len[lm] : nref;
         col[PL_TOK_OFF * pairs] = sem ? (b * seg_k + w) * n : -1;
         col[PL_ROW0 * pairs] = row0;
-        col[PL_SEL_OFF * pairs] = by_sid ? lm_sel_off[lsid] : -1;
+        col[PL_SEL_OFF * pairs] = by_sid ? lm_sel_off[lm] : -1;
         col[PL_ORDER * pairs] = w;
     }
 }
@@ -209,25 +223,50 @@ extern "C" int pram_cand_mask_ranks(long long* sorted_ids, const int* counts, in
     return pram_launch_status("pram_cand_mask_ranks");
 }
 
+namespace {
+
+// the two plan entries: one set of checks and statuses (maps: lm_start is read and start_sid is not; else the other way round)
+int cand_plan_launch(const char* what, const int* win_sid, const int* win_count, const int* n_win, const int* seg_ids, const int* counts, int batch,
+                     int n, int n_class, int seg_k, const int* lm_frame, const int* lm_sel_off, const int* lm_sel_len, int n_landmarks,
+                     int start_sid, const int* lm_start, bool maps, const int* frame_off, const int* hist_off, const int* hist_label,
+                     const int* hist_cnt, int n_frames, int min_kpts, double overlap_ratio, int semantic_matching, int* plan, void* stream) {
+    PRAM_REQUIRE(win_sid && win_count && n_win && seg_ids && counts && lm_frame && lm_sel_off && lm_sel_len && (!maps || lm_start) && frame_off &&
+                 hist_off && hist_label && hist_cnt && plan, "%s: null pointer", what);
+    PRAM_REQUIRE(aligned(win_sid, 4) && aligned(win_count, 4) && aligned(n_win, 4) && aligned(seg_ids, 4) && aligned(counts, 4) &&
+                 aligned(lm_frame, 4) && aligned(lm_sel_off, 4) && aligned(lm_sel_len, 4) && aligned(lm_start, 4) && aligned(frame_off, 4) &&
+                 aligned(hist_off, 4) && aligned(hist_label, 4) && aligned(hist_cnt, 4) && aligned(plan, 4), "%s: misaligned pointer", what);
+    PRAM_REQUIRE(batch >= 0 && batch <= 65535 && n >= 0 && seg_k > 0 && n_class > 0 && n_class <= CAND_MAX_C && n_landmarks >= 0 && n_frames >= 0,
+                 "%s: needs 0 <= batch <= 65535, n >= 0, seg_k > 0, 0 < classes <= %d", what, CAND_MAX_C);
+    PRAM_REQUIRE((long long)batch * seg_k * (long long)(n > 0 ? n : 1) < 2147483647LL, "%s: batch * seg_k * n does not fit the plan's 32-bit offsets", what);
+    PRAM_REQUIRE(overlap_ratio == overlap_ratio && min_kpts >= 0, "%s: overlap_ratio is NaN or min_kpts < 0", what);
+    if (batch == 0) return PRAM_OK;
+    auto kernel = maps ? cand_plan_kernel<true> : cand_plan_kernel<false>;
+    hipLaunchKernelGGL(kernel, dim3(seg_k, batch), dim3(256), 0, (hipStream_t)stream, win_sid, win_count, n_win, seg_ids, counts, n, seg_k, lm_frame,
+                       lm_sel_off, lm_sel_len, n_landmarks, start_sid, lm_start, n_frames, frame_off, hist_off, hist_label, hist_cnt, min_kpts,
+                       overlap_ratio, semantic_matching != 0, plan);
+    return pram_launch_status(what);
+}
+
+}  // namespace
+
 extern "C" int pram_cand_plan(const int* win_sid, const int* win_count, const int* n_win, const int* seg_ids, const int* counts,
                               int batch, int n, int n_class, int seg_k, const int* lm_frame, const int* lm_sel_off,
                               const int* lm_sel_len, int n_landmarks, int start_sid, const int* frame_off, const int* hist_off,
                               const int* hist_label, const int* hist_cnt, int n_frames, int min_kpts, double overlap_ratio,
                               int semantic_matching, int* plan, void* stream) {
-    PRAM_REQUIRE(win_sid && win_count && n_win && seg_ids && counts && lm_frame && lm_sel_off && lm_sel_len && frame_off && hist_off &&
-                 hist_label && hist_cnt && plan, "pram_cand_plan: null pointer");
-    PRAM_REQUIRE(aligned(win_sid, 4) && aligned(win_count, 4) && aligned(n_win, 4) && aligned(seg_ids, 4) && aligned(counts, 4) &&
-                 aligned(lm_frame, 4) && aligned(lm_sel_off, 4) && aligned(lm_sel_len, 4) && aligned(frame_off, 4) && aligned(hist_off, 4) &&
-                 aligned(hist_label, 4) && aligned(hist_cnt, 4) && aligned(plan, 4), "pram_cand_plan: misaligned pointer");
-    PRAM_REQUIRE(batch >= 0 && batch <= 65535 && n >= 0 && seg_k > 0 && n_class > 0 && n_class <= CAND_MAX_C && n_landmarks >= 0 && n_frames >= 0,
-                 "pram_cand_plan: needs 0 <= batch <= 65535, n >= 0, seg_k > 0, 0 < classes <= %d", CAND_MAX_C);
-    PRAM_REQUIRE((long long)batch * seg_k * (long long)(n > 0 ? n : 1) < 2147483647LL, "pram_cand_plan: batch * seg_k * n does not fit the plan's 32-bit offsets");
-    PRAM_REQUIRE(overlap_ratio == overlap_ratio && min_kpts >= 0, "pram_cand_plan: overlap_ratio is NaN or min_kpts < 0");
-    if (batch == 0) return PRAM_OK;
-    hipLaunchKernelGGL(cand_plan_kernel, dim3(seg_k, batch), dim3(256), 0, (hipStream_t)stream, win_sid, win_count, n_win, seg_ids, counts, n,
-                       seg_k, lm_frame, lm_sel_off, lm_sel_len, n_landmarks, start_sid, frame_off, hist_off, hist_label, hist_cnt, min_kpts,
-                       overlap_ratio, semantic_matching != 0, plan);
-    return pram_launch_status("pram_cand_plan");
+    return cand_plan_launch("pram_cand_plan", win_sid, win_count, n_win, seg_ids, counts, batch, n, n_class, seg_k, lm_frame, lm_sel_off, lm_sel_len,
+                            n_landmarks, start_sid, nullptr, false, frame_off, hist_off, hist_label, hist_cnt, n_frames, min_kpts, overlap_ratio,
+                            semantic_matching, plan, stream);
+}
+
+extern "C" int pram_cand_plan_maps(const int* win_sid, const int* win_count, const int* n_win, const int* seg_ids, const int* counts,
+                                   int batch, int n, int n_class, int seg_k, const int* lm_frame, const int* lm_sel_off,
+                                   const int* lm_sel_len, int n_landmarks, const int* lm_start, const int* frame_off, const int* hist_off,
+                                   const int* hist_label, const int* hist_cnt, int n_frames, int min_kpts, double overlap_ratio,
+                                   int semantic_matching, int* plan, void* stream) {
+    return cand_plan_launch("pram_cand_plan_maps", win_sid, win_count, n_win, seg_ids, counts, batch, n, n_class, seg_k, lm_frame, lm_sel_off,
+                            lm_sel_len, n_landmarks, 0, lm_start, true, frame_off, hist_off, hist_label, hist_cnt, n_frames, min_kpts, overlap_ratio,
+                            semantic_matching, plan, stream);
 }
 
 extern "C" int pram_cand_gather(const int* plan, const int* tokens, const int* sel_rows, const float* q_desc, const float* q_kpts,

@@ -1479,7 +1479,7 @@ def cand_mask_ranks_(sorted_ids: torch.Tensor, counts: torch.Tensor) -> torch.Te
 def cand_plan(win_sid, win_count, n_win, seg_ids, counts, n_class: int, store, min_kpts: int, overlap_ratio: float,
               semantic_matching: bool) -> torch.Tensor:
     """-> plan int32 [CAND_PLAN_COLS, B * seg_k] (one contiguous column per CAND_PLAN_FIELDS entry).  ``store``: the device tables
-    of a ReferenceStore (dict of tensors)."""
+    of a ReferenceStore (dict of tensors: pram_cand_plan) or of a MultiMapStore (they carry lm_start: pram_cand_plan_maps)."""
     L = _lib.load()
     for t, nm in ((win_sid, "win_sid"), (win_count, "win_count"), (n_win, "n_win"), (seg_ids, "seg_ids"), (counts, "counts")):
         _chk(t, nm, torch.int32)
@@ -1489,6 +1489,12 @@ def cand_plan(win_sid, win_count, n_win, seg_ids, counts, n_class: int, store, m
     assert seg_ids.shape[0] == B and counts.numel() == B and n_win.numel() == B and win_count.shape == win_sid.shape
     plan = torch.empty(CAND_PLAN_COLS, B * seg_k, device=win_sid.device, dtype=torch.int32)
     s = store
+    if "lm_start" in s:      # a MultiMapStore's tables: the landmark tables are indexed by the global id
+        _lib.check(L.pram_cand_plan_maps(_p(win_sid), _p(win_count), _p(n_win), _p(seg_ids), _p(counts), B, n, int(n_class), seg_k, _p(s["lm_frame"]),
+                                         _p(s["lm_sel_off"]), _p(s["lm_sel_len"]), int(s["n_landmarks"]), _p(s["lm_start"]), _p(s["frame_off"]),
+                                         _p(s["hist_off"]), _p(s["hist_label"]), _p(s["hist_cnt"]), int(s["n_frames"]), int(min_kpts),
+                                         float(overlap_ratio), int(bool(semantic_matching)), _p(plan), _st()), "pram_cand_plan_maps")
+        return plan
     _lib.check(L.pram_cand_plan(_p(win_sid), _p(win_count), _p(n_win), _p(seg_ids), _p(counts), B, n, int(n_class), seg_k, _p(s["lm_frame"]),
                                 _p(s["lm_sel_off"]), _p(s["lm_sel_len"]), int(s["n_landmarks"]), int(s["start_sid"]), _p(s["frame_off"]),
                                 _p(s["hist_off"]), _p(s["hist_label"]), _p(s["hist_cnt"]), int(s["n_frames"]), int(min_kpts),
