@@ -2,13 +2,11 @@
 // singlemap3d.py:127-162, check_semantic_consistency singlemap3d.py:513-532, RefFrame.get_keypoints[_by_sid] refframe.py:34-75):
 // from the landmark vote of a batch of queries to the grouped matcher's inputs, and from its matches0 to 2D-3D correspondences,
 // without a host loop.  Bandwidth / latency kernels: coalesced 16-byte accesses on the descriptor rows, nothing tuned beyond that.
-#include "common.h"
+#include "glue.h"
 
 namespace {
 
 constexpr int CAND_MAX_C = 1024;          // classes of the recogniser (pram_seg_vote's own limit)
-enum { PL_QUERY = 0, PL_SID, PL_FRAME, PL_SEM, PL_LEN0, PL_LEN1, PL_TOK_OFF, PL_ROW0, PL_SEL_OFF, PL_ORDER };
-static_assert(PL_ORDER + 1 == PRAM_CAND_PLAN_COLS, "plan table layout");
 
 // sorted class ids of the padded tokens (t >= counts[b]) -> 0 at every rank: background is never a candidate of the vote and a
 // token that names it at every rank names no landmark, so pram_seg_vote over all n rows equals the vote over the first counts[b].
@@ -161,19 +159,14 @@ __global__ __launch_bounds__(256) void cand_correspond_kernel(const long long* _
                                                               const float* __restrict__ q_kpts, int n, const float* __restrict__ r_kpts,
                                                               const long long* __restrict__ r_xyz, const long long* __restrict__ r_p3d,
                                                               const int* __restrict__ r_segs, int ref_rows, int t0, int cap,
-                                                              long long* __restrict__ m_ids, float* __restrict__ m_kpts,
-                                                              float* __restrict__ m_ref_kpts, long long* __restrict__ m_p3d,
-                                                              long long* __restrict__ m_xyz, int* __restrict__ m_sids,
-                                                              int* __restrict__ m_count) {
+                                                              MatchList m, int* __restrict__ m_count) {
     __shared__ int wsum[4];
-    __shared__ int base;
-    const int p = blockIdx.x, P = gridDim.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int p = blockIdx.x, P = gridDim.x, tid = threadIdx.x;
     const int* pl = plan + p;
     int len0 = pl[PL_LEN0 * P];
     len0 = len0 > t0 ? t0 : len0;
     const int len1 = pl[PL_LEN1 * P], tok_off = pl[PL_TOK_OFF * P], sel_off = pl[PL_SEL_OFF * P], row0 = pl[PL_ROW0 * P], b = pl[PL_QUERY * P];
-    if (tid == 0) base = 0;
-    __syncthreads();
+    int base = 0;      // a running sum every thread carries
     for (int c0 = 0; c0 < len0; c0 += 256) {
         const int i = c0 + tid;
         long long j = -1;
@@ -185,32 +178,15 @@ __global__ __launch_bounds__(256) void cand_correspond_kernel(const long long* _
                 rr = sel_off < 0 ? row0 + (int)j : sel_rows[(size_t)sel_off + j];
             }
         }
-        const int f = qt >= 0 && qt < n && rr >= 0 && rr < ref_rows;
-        const unsigned long long bal = __ballot(f);
-        const int before = __popcll(bal & ((1ull << lane) - 1ull));
-        if (lane == 0) wsum[wave] = __popcll(bal);
-        __syncthreads();
-        int woff = 0, tot = 0;
-        for (int w = 0; w < 4; ++w) { if (w < wave) woff += wsum[w]; tot += wsum[w]; }
-        const int bs = base;
-        const int o = bs + woff + before;
-        if (f && o < cap) {
-            const size_t d = (size_t)p * cap + o, q = (size_t)b * n + qt;
-            m_ids[d] = qt;
-            m_kpts[d * 2] = q_kpts[q * 2]; m_kpts[d * 2 + 1] = q_kpts[q * 2 + 1];
-            m_ref_kpts[d * 2] = r_kpts[(size_t)rr * 2]; m_ref_kpts[d * 2 + 1] = r_kpts[(size_t)rr * 2 + 1];
-            m_p3d[d] = r_p3d[rr];
-            m_xyz[d * 3] = r_xyz[(size_t)rr * 3]; m_xyz[d * 3 + 1] = r_xyz[(size_t)rr * 3 + 1]; m_xyz[d * 3 + 2] = r_xyz[(size_t)rr * 3 + 2];
-            m_sids[d] = r_segs[rr];
-        }
-        __syncthreads();
-        if (tid == 0) base = bs + tot;
-        __syncthreads();
+        const bool f = qt >= 0 && qt < n && rr >= 0 && rr < ref_rows;
+        int tot;
+        const int o = base + chunk_offset<4>(f, wsum, tot);
+        if (f && o < cap)
+            match_emit_row(m, (size_t)p * cap + o, qt, q_kpts + ((size_t)b * n + qt) * 2, r_kpts, r_p3d, r_xyz, r_segs, (size_t)rr);
+        base += tot;
     }
     if (tid == 0) m_count[p] = base < cap ? base : cap;
 }
-
-inline bool aligned(const void* p, size_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
 
 }  // namespace
 
@@ -303,7 +279,7 @@ extern "C" int pram_cand_correspond(const long long* matches0, int ldm, const in
                  "pram_cand_correspond: needs pairs >= 0, 0 <= t0 <= ldm, cap >= 0, n >= 0, ref_rows >= 0");
     if (pairs == 0) return PRAM_OK;
     hipLaunchKernelGGL(cand_correspond_kernel, dim3(pairs), dim3(256), 0, (hipStream_t)stream, matches0, ldm, plan, tokens, sel_rows, q_kpts, n,
-                       r_kpts, reinterpret_cast<const long long*>(r_xyz), r_point3d_ids, r_segs, ref_rows, t0, cap, m_kpt_ids, m_kpts, m_ref_kpts,
-                       m_point3d_ids, reinterpret_cast<long long*>(m_xyz), m_sids, m_count);
+                       r_kpts, reinterpret_cast<const long long*>(r_xyz), r_point3d_ids, r_segs, ref_rows, t0, cap,
+                       match_list(m_kpt_ids, m_kpts, m_ref_kpts, m_point3d_ids, m_xyz, m_sids), m_count);
     return pram_launch_status("pram_cand_correspond");
 }

@@ -28,6 +28,9 @@ static inline int pram_launch_status(const char* what) {
 
 static inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 
+// a null pointer is aligned: the entries pass their optional arguments (enable, seg_ids, mask, lm_start) through the same test
+static inline bool aligned(const void* p, size_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
+
 // Behaviour-changing environment switches (tile / kernel-form overrides) exist in profiling builds only (-DPRAM_PROFILING, e.g.
 // profiles/tools/build_variants.py TAG:file.hip:-DPRAM_PROFILING).  The production library reads one: PRAM_CONV_HALO
 // (conv.hip), "0" forces the per-tap 3x3 kernel — tests/test_gpu_guard_chunks_mlp.py compares it against the halo kernel.

@@ -3,7 +3,7 @@
 // argmax, localization/frame.py:96-121), full descending row sort (torch.topk(k=C),
 // localization/multimap3d.py:348-350) and row top-2 (nearest-neighbour matching,
 // localization/matchers/nearest_neighbor.py:5-17; projection refinement singlemap3d.py:428-433).
-#include "common.h"
+#include "glue.h"
 #include <math.h>
 
 namespace {
@@ -322,29 +322,19 @@ __global__ __launch_bounds__(1024) void proj_compact_kernel(const int* __restric
                                                             int* __restrict__ keep_idx, double* __restrict__ uv_keep,
                                                             int* __restrict__ count) {
     __shared__ int wsum[16];
-    __shared__ int base;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    if (tid == 0) base = 0;
-    __syncthreads();
+    const int tid = threadIdx.x;
+    int base = 0;      // a running sum every thread carries
     for (int c0 = 0; c0 < n; c0 += 1024) {
         const int i = c0 + tid;
-        const int f = (i < n) ? (mask[i] != 0) : 0;
-        const unsigned long long bal = __ballot(f);
-        const int before = __popcll(bal & ((1ull << lane) - 1ull));
-        if (lane == 0) wsum[wave] = __popcll(bal);
-        __syncthreads();
-        int woff = 0, tot = 0;
-        for (int w = 0; w < 16; ++w) { if (w < wave) woff += wsum[w]; tot += wsum[w]; }
-        const int b = base;
+        const bool f = i < n && mask[i] != 0;
+        int tot;
+        const int o = base + chunk_offset<16>(f, wsum, tot);
         if (f) {
-            const int o = b + woff + before;
             keep_idx[o] = i;
             uv_keep[o] = uvd[i];
             uv_keep[n + o] = uvd[n + i];
         }
-        __syncthreads();
-        if (tid == 0) base = b + tot;
-        __syncthreads();
+        base += tot;
     }
     if (tid == 0) *count = base;
 }

@@ -636,8 +636,6 @@ __global__ __launch_bounds__(64) void pose_select_kernel(const int* __restrict__
     chosen[b * 3] = kept; chosen[b * 3 + 1] = status; chosen[b * 3 + 2] = kept;
 }
 
-inline bool aligned(const void* p, size_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
-
 }  // namespace
 
 extern "C" int pram_pose_prepare(const float* m_kpts, const int* count, const int* cam_model, const double* cam_params,

@@ -4,30 +4,9 @@
 // (no [M, N] matrix), and the compaction of the accepted keypoints into pram_cand_correspond's layout.  Plain vector loads and
 // stores, one idempotent integer atomic (the bitmap's OR), no float atomics; every loop is bounded by an argument and every index
 // read from a table is checked against the size given beside it before it is used.  Results do not depend on scheduling.
-#include "common.h"
+#include "glue.h"
 
 namespace {
-
-enum { PL_FRAME = 2 };      // the frame column of the plan table (PRAM_CAND_PLAN_COLS columns)
-
-// the frame the localisation kept for query b (-1: not located), and its covisible list cut to n_cov
-struct Slots { int f, c0, len; };
-
-__device__ __forceinline__ Slots query_slots(const int* __restrict__ chosen, const int* __restrict__ loc_plan, const int* __restrict__ enable,
-                                             const int* __restrict__ covis_off, int b, int batch, int seg_k, int n_cov, int n_frames,
-                                             int n_covis) {
-    Slots s = {-1, 0, 0};
-    const int kept = chosen[b * 3];
-    if (kept >= 0 && kept < seg_k) s.f = loc_plan[(size_t)PL_FRAME * batch * seg_k + b * seg_k + kept];
-    if (s.f >= n_frames || (enable != nullptr && enable[b] == 0)) s.f = -1;
-    if (s.f < 0) { s.f = -1; return s; }
-    s.c0 = covis_off[s.f];
-    s.len = covis_off[s.f + 1] - s.c0;
-    s.c0 = s.c0 < 0 ? 0 : s.c0;
-    s.len = s.len < 0 ? 0 : (s.len > n_cov ? n_cov : s.len);
-    if (s.c0 + s.len > n_covis) s.len = n_covis > s.c0 ? n_covis - s.c0 : 0;
-    return s;
-}
 
 // grid (n_cov + 1, batch): slot j < n_cov = entry j of the list, slot n_cov = the reference frame when the list does not hold it
 __global__ __launch_bounds__(256) void projref_mark_kernel(const int* __restrict__ chosen, const int* __restrict__ loc_plan,
@@ -56,35 +35,13 @@ __global__ __launch_bounds__(256) void projref_mark_kernel(const int* __restrict
     for (int r = r0 + tid; r < r1; r += 256) {
         const long long id = point3d_ids[r];
         if (id == -1) continue;
-        int lo = 0, hi = n_points;      // first index with pt_ids[i] >= id
-        for (int it = 0; it < 32 && lo < hi; ++it) {
-            const int mid = lo + ((hi - lo) >> 1);
-            if (pt_ids[mid] < id) lo = mid + 1; else hi = mid;
-        }
+        const int lo = lower_bound_i64(pt_ids, n_points, id);
         if (lo >= n_points || pt_ids[lo] != id) continue;      // a point the table does not hold marks nothing
         atomicOr(&bits[lo >> 5], 1u << (lo & 31));
     }
 }
 
 constexpr int PROJ_THREADS = 1024, PROJ_WAVES = PROJ_THREADS / 64;
-
-// block-wide exclusive offset of `n` items per thread (wave prefix + per-wave totals); returns the block's total through *tot
-__device__ __forceinline__ int block_offset(int n, int* wsum, int* tot) {
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    int incl = n;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const int v = __shfl_up(incl, o, 64);
-        if (lane >= o) incl += v;
-    }
-    if (lane == 63) wsum[wave] = incl;
-    __syncthreads();
-    int woff = 0, t = 0;
-    for (int w = 0; w < PROJ_WAVES; ++w) { if (w < wave) woff += wsum[w]; t += wsum[w]; }
-    __syncthreads();
-    *tot = t;
-    return woff + incl - n;
-}
 
 // one workgroup per query.  Phase 1: the marked points in ascending table index into cand_pt (one bitmap word per thread and
 // step).  Phase 2: project, frustum test, ordered compaction in place (a chunk is read, then a barrier, then written at or before
@@ -107,7 +64,7 @@ __global__ __launch_bounds__(PROJ_THREADS) void projref_project_kernel(const uns
         unsigned int word = w < words ? bits[w] : 0u;
         if (w == words - 1 && (n_points & 31)) word &= (1u << (n_points & 31)) - 1u;
         int tot;
-        int o = base + block_offset(__popc(word), wsum, &tot);
+        int o = base + chunk_offset_n<PROJ_WAVES>(__popc(word), wsum, tot);
         while (word) {
             const int bit = __ffs(word) - 1;
             word &= word - 1u;
@@ -158,7 +115,7 @@ __global__ __launch_bounds__(PROJ_THREADS) void projref_project_kernel(const uns
             keep = (p[2] > 0.0) && (p[2] < 100.0) && (u >= 0.0) && (u < imw) && (v >= 0.0) && (v < imh);
         }
         int tot;
-        const int o = base + block_offset(keep ? 1 : 0, wsum, &tot);      // its barriers stand between the chunk's reads and writes
+        const int o = base + chunk_offset<PROJ_WAVES>(keep, wsum, tot);      // its barriers stand between the chunk's reads and writes
         if (keep) {
             pts[o] = pt;
             uv[o] = u;
@@ -236,12 +193,10 @@ __global__ __launch_bounds__(256) void projref_correspond_kernel(const unsigned 
                                                                  const int* __restrict__ counts, const float* __restrict__ q_kpts, int n,
                                                                  const int* __restrict__ cand_pt, const int* __restrict__ n_cand, int cap,
                                                                  const long long* __restrict__ pt_ids, const long long* __restrict__ pt_xyz,
-                                                                 const int* __restrict__ pt_sid, int n_points, long long* __restrict__ m_ids,
-                                                                 float* __restrict__ m_kpts, long long* __restrict__ m_p3d,
-                                                                 long long* __restrict__ m_xyz, int* __restrict__ m_sids,
+                                                                 const int* __restrict__ pt_sid, int n_points, MatchList m,
                                                                  int* __restrict__ m_count) {
     __shared__ int wsum[4];
-    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int b = blockIdx.x, tid = threadIdx.x;
     int nq = counts[b], nc = n_cand[b];
     nq = nq < 0 ? 0 : (nq > n ? n : nq);
     nc = nc < 0 ? 0 : (nc > cap ? cap : nc);
@@ -255,26 +210,14 @@ __global__ __launch_bounds__(256) void projref_correspond_kernel(const unsigned 
             if (j >= 0 && j < nc) pt = cand_pt[(size_t)b * cap + j];
             if (pt >= n_points) pt = -1;
         }
-        const unsigned long long bal = __ballot(pt >= 0);
-        if (lane == 0) wsum[wave] = __popcll(bal);
-        __syncthreads();
-        int woff = 0, tot = 0;
-        for (int w = 0; w < 4; ++w) { if (w < wave) woff += wsum[w]; tot += wsum[w]; }
-        if (pt >= 0) {
-            const size_t d = (size_t)b * n + base + woff + __popcll(bal & ((1ull << lane) - 1ull));
-            m_ids[d] = i;
-            m_kpts[d * 2] = q_kpts[row * 2]; m_kpts[d * 2 + 1] = q_kpts[row * 2 + 1];
-            m_p3d[d] = pt_ids[pt];
-            m_xyz[d * 3] = pt_xyz[(size_t)pt * 3]; m_xyz[d * 3 + 1] = pt_xyz[(size_t)pt * 3 + 1]; m_xyz[d * 3 + 2] = pt_xyz[(size_t)pt * 3 + 2];
-            m_sids[d] = pt_sid[pt];
-        }
+        int tot;
+        const int o = base + chunk_offset<4>(pt >= 0, wsum, tot);
+        // the list has no ref_kpts (a point of the map has no keypoint of its own), so the helper reads no reference keypoints
+        if (pt >= 0) match_emit_row(m, (size_t)b * n + o, i, q_kpts + row * 2, nullptr, pt_ids, pt_xyz, pt_sid, (size_t)pt);
         base += tot;
-        __syncthreads();
     }
     if (tid == 0) m_count[b] = base;
 }
-
-inline bool aligned(const void* p, size_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
 
 }  // namespace
 
@@ -347,7 +290,7 @@ extern "C" int pram_projref_correspond(const unsigned char* accept, const int* b
     PRAM_REQUIRE(batch >= 0 && n >= 0 && n_points >= 1 && cap >= 1, "pram_projref_correspond: needs batch >= 0, n >= 0, n_points >= 1, cap >= 1");
     if (batch == 0) return PRAM_OK;
     hipLaunchKernelGGL(projref_correspond_kernel, dim3(batch), dim3(256), 0, (hipStream_t)stream, accept, best, counts, q_kpts, n, cand_pt, n_cand,
-                       cap, pt_ids, reinterpret_cast<const long long*>(pt_xyz), pt_sid, n_points, m_kpt_ids, m_kpts, m_point3d_ids,
-                       reinterpret_cast<long long*>(m_xyz), m_sids, m_count);
+                       cap, pt_ids, reinterpret_cast<const long long*>(pt_xyz), pt_sid, n_points,
+                       match_list(m_kpt_ids, m_kpts, nullptr, m_point3d_ids, m_xyz, m_sids), m_count);
     return pram_launch_status("pram_projref_correspond");
 }

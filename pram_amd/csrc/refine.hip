@@ -3,12 +3,9 @@
 // the candidate stage ("all keypoints of the query" against "the whole frame"), so pram_cand_gather / pram_cand_correspond run on
 // the plan written here unchanged.  Latency / bandwidth kernels: plain vector loads and stores, integer atomics only (the results
 // do not depend on the order the adds arrive in), every loop bounded by an argument, nothing allocated.
-#include "common.h"
+#include "glue.h"
 
 namespace {
-
-enum { PL_QUERY = 0, PL_SID, PL_FRAME, PL_SEM, PL_LEN0, PL_LEN1, PL_TOK_OFF, PL_ROW0, PL_SEL_OFF, PL_ORDER };
-static_assert(PL_ORDER + 1 == PRAM_CAND_PLAN_COLS, "plan table layout");
 
 // one thread per (query b, slot j < n_cov); the thread of slot 0 also writes the query's own row
 __global__ __launch_bounds__(256) void refine_plan_kernel(const int* __restrict__ chosen, const int* __restrict__ loc_plan,
@@ -20,25 +17,12 @@ __global__ __launch_bounds__(256) void refine_plan_kernel(const int* __restrict_
     const int p = blockIdx.x * 256 + threadIdx.x, pairs = batch * n_cov;
     if (p >= pairs) return;
     const int b = p / n_cov, j = p - b * n_cov;
-    const int loc_pairs = batch * seg_k;
     const int kept = chosen[b * 3], status = chosen[b * 3 + 1];
-    int f = -1, sid = -1;
-    if (kept >= 0 && kept < seg_k) {
-        const int lp = b * seg_k + kept;
-        f = loc_plan[PL_FRAME * loc_pairs + lp];
-        sid = loc_plan[PL_SID * loc_pairs + lp];
-    }
-    if (f >= n_frames) f = -1;
-    const bool live = f >= 0 && (enable == nullptr || enable[b] != 0);
-    int c0 = 0, len = 0;
-    if (live) {      // the covisible list of the localisation's reference frame, cut to n_cov (the canonical order makes it a prefix)
-        c0 = covis_off[f];
-        len = covis_off[f + 1] - c0;
-        c0 = c0 < 0 ? 0 : c0;
-        len = len < 0 ? 0 : (len > n_cov ? n_cov : len);
-        if (c0 + len > n_covis) len = n_covis > c0 ? n_covis - c0 : 0;
-    }
-    int g = (live && j < len) ? covis_frames[c0 + j] : -1;
+    const int sid = (kept >= 0 && kept < seg_k) ? loc_plan[PL_SID * batch * seg_k + b * seg_k + kept] : -1;
+    // the covisible list of the localisation's reference frame, cut to n_cov (the canonical order makes it a prefix)
+    const Slots s = query_slots(chosen, loc_plan, enable, covis_off, b, batch, seg_k, n_cov, n_frames, n_covis);
+    const int f = s.f, c0 = s.c0, len = s.len;      // not live: f = -1 and an empty list
+    int g = j < len ? covis_frames[c0 + j] : -1;
     if (g >= n_frames) g = -1;
     int nq = counts[b];
     nq = nq < 0 ? 0 : nq;
@@ -51,24 +35,17 @@ __global__ __launch_bounds__(256) void refine_plan_kernel(const int* __restrict_
     if (j == 0) {
         int in_list = 0;
         for (int i = 0; i < len; ++i) in_list |= covis_frames[c0 + i] == f;      // singlemap3d.py:273 "ref_frame_id in db_ids"
-        ref_frame[b] = live ? f : -1;
+        ref_frame[b] = f;
         n_cov_used[b] = len;
-        init_on[b] = live && status == 1 && in_list;
+        init_on[b] = f >= 0 && status == 1 && in_list;
     }
 }
 
-struct MergeBufs {
-    const long long* ids; const float* kpts; const float* ref_kpts; const long long* p3d; const long long* xyz; const int* sids;
-};
-
 // one workgroup per query: the slots in ascending order, then the localisation's matches (singlemap3d.py:288-315)
-__global__ __launch_bounds__(256) void refine_merge_kernel(MergeBufs r, const int* __restrict__ r_count, int t0, MergeBufs a,
+__global__ __launch_bounds__(256) void refine_merge_kernel(ConstMatchList r, const int* __restrict__ r_count, int t0, ConstMatchList a,
                                                            const int* __restrict__ a_count, int t0a, const int* __restrict__ chosen,
-                                                           const int* __restrict__ init_on, int seg_k, int n_cov, int cap,
-                                                           long long* __restrict__ m_ids, float* __restrict__ m_kpts,
-                                                           float* __restrict__ m_ref_kpts, long long* __restrict__ m_p3d,
-                                                           long long* __restrict__ m_xyz, int* __restrict__ m_sids, int* __restrict__ m_src,
-                                                           int* __restrict__ m_count) {
+                                                           const int* __restrict__ init_on, int seg_k, int n_cov, int cap, MatchList m,
+                                                           int* __restrict__ m_src, int* __restrict__ m_count) {
     const int b = blockIdx.x, tid = threadIdx.x;
     const int kept = chosen[b * 3];
     const bool with_init = init_on[b] != 0 && kept >= 0 && kept < seg_k;
@@ -78,7 +55,7 @@ __global__ __launch_bounds__(256) void refine_merge_kernel(MergeBufs r, const in
     for (int s = 0; s <= n_cov; ++s) {
         const bool init = s == n_cov;
         if (init && !with_init) break;
-        const MergeBufs& src = init ? a : r;
+        const ConstMatchList& src = init ? a : r;
         const int ld = init ? t0a : t0;
         const size_t seg = init ? (size_t)(b * seg_k + kept) : (size_t)b * n_cov + s;
         int cnt = init ? a_count[seg] : r_count[seg];
@@ -86,12 +63,7 @@ __global__ __launch_bounds__(256) void refine_merge_kernel(MergeBufs r, const in
         if (base + cnt > cap) cnt = cap - base;
         for (int i = tid; i < cnt; i += 256) {
             const size_t q = seg * ld + i, d = (size_t)b * cap + base + i;
-            m_ids[d] = src.ids[q];
-            m_kpts[d * 2] = src.kpts[q * 2]; m_kpts[d * 2 + 1] = src.kpts[q * 2 + 1];
-            m_ref_kpts[d * 2] = src.ref_kpts[q * 2]; m_ref_kpts[d * 2 + 1] = src.ref_kpts[q * 2 + 1];
-            m_p3d[d] = src.p3d[q];
-            m_xyz[d * 3] = src.xyz[q * 3]; m_xyz[d * 3 + 1] = src.xyz[q * 3 + 1]; m_xyz[d * 3 + 2] = src.xyz[q * 3 + 2];
-            m_sids[d] = src.sids[q];
+            match_copy_row(m, d, src, q);
             m_src[d] = s;
         }
         base += cnt;
@@ -117,11 +89,7 @@ __global__ __launch_bounds__(256) void refine_frame_vote_kernel(const long long*
         const size_t row = (size_t)b * cap + r;
         if (only_inliers && !inliers[row]) continue;
         const long long id = m_p3d[row];
-        int lo = 0, hi = n_points;      // first index with pt_ids[i] >= id
-        for (int it = 0; it < 32 && lo < hi; ++it) {
-            const int mid = lo + ((hi - lo) >> 1);
-            if (pt_ids[mid] < id) lo = mid + 1; else hi = mid;
-        }
+        const int lo = lower_bound_i64(pt_ids, n_points, id);
         if (lo >= n_points || pt_ids[lo] != id) continue;      // a point the map does not know votes for nothing
         int e0 = pt_off[lo], e1 = pt_off[lo + 1];
         e0 = e0 < 0 ? 0 : e0;
@@ -164,8 +132,6 @@ __global__ __launch_bounds__(256) void refine_frame_vote_kernel(const long long*
     if (tid == 0) n_best[b] = found;
 }
 
-inline bool aligned(const void* p, size_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
-
 }  // namespace
 
 extern "C" int pram_refine_plan(const int* chosen, const int* loc_plan, const int* counts, const int* enable, const int* frame_off,
@@ -207,11 +173,10 @@ extern "C" int pram_refine_merge(const long long* r_kpt_ids, const float* r_kpts
     PRAM_REQUIRE((long long)n_cov * t0 + t0a <= (long long)cap && cap < 2147483647, "pram_refine_merge: cap is smaller than n_cov * t0 + t0a");
     PRAM_REQUIRE((long long)batch * n_cov < 2147483647LL && (long long)batch * seg_k < 2147483647LL, "pram_refine_merge: batch * n_cov or batch * seg_k overflows");
     if (batch == 0) return PRAM_OK;
-    const MergeBufs r = {r_kpt_ids, r_kpts, r_ref_kpts, r_point3d_ids, reinterpret_cast<const long long*>(r_xyz), r_sids};
-    const MergeBufs a = {a_kpt_ids, a_kpts, a_ref_kpts, a_point3d_ids, reinterpret_cast<const long long*>(a_xyz), a_sids};
-    hipLaunchKernelGGL(refine_merge_kernel, dim3(batch), dim3(256), 0, (hipStream_t)stream, r, r_count, t0, a, a_count, t0a, chosen, init_on,
-                       seg_k, n_cov, cap, m_kpt_ids, m_kpts, m_ref_kpts, m_point3d_ids, reinterpret_cast<long long*>(m_xyz), m_sids, m_src,
-                       m_count);
+    hipLaunchKernelGGL(refine_merge_kernel, dim3(batch), dim3(256), 0, (hipStream_t)stream,
+                       match_list(r_kpt_ids, r_kpts, r_ref_kpts, r_point3d_ids, r_xyz, r_sids), r_count, t0,
+                       match_list(a_kpt_ids, a_kpts, a_ref_kpts, a_point3d_ids, a_xyz, a_sids), a_count, t0a, chosen, init_on, seg_k, n_cov, cap,
+                       match_list(m_kpt_ids, m_kpts, m_ref_kpts, m_point3d_ids, m_xyz, m_sids), m_src, m_count);
     return pram_launch_status("pram_refine_merge");
 }
 

@@ -5,12 +5,9 @@
 // "the rows of the slot"), so pram_cand_gather runs on pram_track_plan's table unchanged with the state's arrays as its
 // reference side.  Latency / bandwidth kernels: 16-byte accesses on the descriptor rows, plain vector loads and stores
 // elsewhere, one integer atomic max (its result does not depend on the order the rows arrive in), nothing allocated.
-#include "common.h"
+#include "glue.h"
 
 namespace {
-
-enum { PL_QUERY = 0, PL_SID, PL_FRAME, PL_SEM, PL_LEN0, PL_LEN1, PL_TOK_OFF, PL_ROW0, PL_SEL_OFF, PL_ORDER };
-static_assert(PL_ORDER + 1 == PRAM_CAND_PLAN_COLS, "plan table layout");
 
 // one thread per pair
 __global__ __launch_bounds__(256) void track_plan_kernel(const int* __restrict__ counts, const int* __restrict__ slot,
@@ -35,30 +32,12 @@ __global__ __launch_bounds__(256) void track_plan_kernel(const int* __restrict__
     lcol[PL_ROW0 * batch] = live ? s * n_max : 0; lcol[PL_SEL_OFF * batch] = -1; lcol[PL_ORDER * batch] = 0;
 }
 
-// ordered compaction inside a workgroup of 256: the offset of this thread's row among the flagged rows of the chunk and the
-// chunk's total (every thread of the workgroup calls it; two barriers)
-__device__ __forceinline__ int chunk_offset(bool f, int* wsum, int& total) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const unsigned long long bal = __ballot(f);
-    const int before = __popcll(bal & ((1ull << lane) - 1ull));
-    __syncthreads();      // the previous chunk's readers of wsum are done
-    if (lane == 0) wsum[wave] = __popcll(bal);
-    __syncthreads();
-    int woff = 0, tot = 0;
-    for (int w = 0; w < 4; ++w) { if (w < wave) woff += wsum[w]; tot += wsum[w]; }
-    total = tot;
-    return woff + before;
-}
-
 // one workgroup per pair: the matched query rows whose row of the last frame carries a point (tracker.py:195-205)
 __global__ __launch_bounds__(256) void track_correspond_kernel(const long long* __restrict__ matches0, int ldm, const int* __restrict__ plan,
                                                                const float* __restrict__ q_kpts, int n, const float* __restrict__ st_kpts,
                                                                const long long* __restrict__ st_xyz, const long long* __restrict__ st_p3d,
                                                                const int* __restrict__ st_segs, int n_slots, int n_max, int t0, int cap,
-                                                               long long* __restrict__ m_ids, float* __restrict__ m_kpts,
-                                                               float* __restrict__ m_ref_kpts, long long* __restrict__ m_p3d,
-                                                               long long* __restrict__ m_xyz, int* __restrict__ m_sids,
-                                                               int* __restrict__ m_count) {
+                                                               MatchList m, int* __restrict__ m_count) {
     __shared__ int wsum[4];
     const int p = blockIdx.x, P = gridDim.x, tid = threadIdx.x;
     const int* pl = plan + p;
@@ -82,30 +61,16 @@ __global__ __launch_bounds__(256) void track_correspond_kernel(const long long* 
             }
         }
         int tot;
-        const int o = base + chunk_offset(f, wsum, tot);
-        if (f && o < cap) {
-            const size_t d = (size_t)p * cap + o, q = (size_t)b * n + i;
-            m_ids[d] = i;
-            m_kpts[d * 2] = q_kpts[q * 2]; m_kpts[d * 2 + 1] = q_kpts[q * 2 + 1];
-            m_ref_kpts[d * 2] = st_kpts[rr * 2]; m_ref_kpts[d * 2 + 1] = st_kpts[rr * 2 + 1];
-            m_p3d[d] = st_p3d[rr];
-            m_xyz[d * 3] = st_xyz[rr * 3]; m_xyz[d * 3 + 1] = st_xyz[rr * 3 + 1]; m_xyz[d * 3 + 2] = st_xyz[rr * 3 + 2];
-            m_sids[d] = st_segs[rr];
-        }
+        const int o = base + chunk_offset<4>(f, wsum, tot);
+        if (f && o < cap) match_emit_row(m, (size_t)p * cap + o, i, q_kpts + ((size_t)b * n + i) * 2, st_kpts, st_p3d, st_xyz, st_segs, rr);
         base += tot;
     }
     if (tid == 0) m_count[p] = base < cap ? base : cap;
 }
 
-struct ListBufs {
-    const long long* ids; const float* kpts; const float* ref_kpts; const long long* p3d; const long long* xyz; const int* sids;
-};
-
 // one workgroup per query: the rows r < count[b] with mask != 0, in order (tracker.py:154-160)
-__global__ __launch_bounds__(256) void track_filter_kernel(ListBufs in, const int* __restrict__ count, const unsigned char* __restrict__ mask,
-                                                           int cap, long long* __restrict__ o_ids, float* __restrict__ o_kpts,
-                                                           float* __restrict__ o_ref_kpts, long long* __restrict__ o_p3d,
-                                                           long long* __restrict__ o_xyz, int* __restrict__ o_sids, int* __restrict__ o_count) {
+__global__ __launch_bounds__(256) void track_filter_kernel(ConstMatchList in, const int* __restrict__ count, const unsigned char* __restrict__ mask,
+                                                           int cap, MatchList out, int* __restrict__ o_count) {
     __shared__ int wsum[4];
     const int b = blockIdx.x, tid = threadIdx.x;
     int cnt = count[b];
@@ -116,16 +81,8 @@ __global__ __launch_bounds__(256) void track_filter_kernel(ListBufs in, const in
         const size_t q = (size_t)b * cap + r;
         const bool f = r < cnt && mask[q] != 0;
         int tot;
-        const int o = base + chunk_offset(f, wsum, tot);
-        if (f) {      // o <= r < cap
-            const size_t d = (size_t)b * cap + o;
-            o_ids[d] = in.ids[q];
-            o_kpts[d * 2] = in.kpts[q * 2]; o_kpts[d * 2 + 1] = in.kpts[q * 2 + 1];
-            o_ref_kpts[d * 2] = in.ref_kpts[q * 2]; o_ref_kpts[d * 2 + 1] = in.ref_kpts[q * 2 + 1];
-            o_p3d[d] = in.p3d[q];
-            o_xyz[d * 3] = in.xyz[q * 3]; o_xyz[d * 3 + 1] = in.xyz[q * 3 + 1]; o_xyz[d * 3 + 2] = in.xyz[q * 3 + 2];
-            o_sids[d] = in.sids[q];
-        }
+        const int o = base + chunk_offset<4>(f, wsum, tot);
+        if (f) match_copy_row(out, (size_t)b * cap + o, in, q);      // o <= r < cap
         base += tot;
     }
     if (tid == 0) o_count[b] = base;
@@ -206,8 +163,6 @@ __global__ __launch_bounds__(256) void track_commit_scatter_kernel(const int* __
     }
 }
 
-inline bool aligned(const void* p, size_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
-
 }  // namespace
 
 extern "C" int pram_track_plan(const int* counts, const int* slot, const int* st_counts, const int* st_ref_frame, int batch, int n,
@@ -238,8 +193,8 @@ extern "C" int pram_track_correspond(const long long* matches0, int ldm, const i
                  "pram_track_correspond: needs pairs >= 0, 0 <= t0 <= ldm, cap >= 0, n >= 0, n_slots >= 0, n_max >= 0");
     if (pairs == 0) return PRAM_OK;
     hipLaunchKernelGGL(track_correspond_kernel, dim3(pairs), dim3(256), 0, (hipStream_t)stream, matches0, ldm, plan, q_kpts, n, st_kpts,
-                       reinterpret_cast<const long long*>(st_xyz), st_point3d_ids, st_segs, n_slots, n_max, t0, cap, m_kpt_ids, m_kpts, m_ref_kpts,
-                       m_point3d_ids, reinterpret_cast<long long*>(m_xyz), m_sids, m_count);
+                       reinterpret_cast<const long long*>(st_xyz), st_point3d_ids, st_segs, n_slots, n_max, t0, cap,
+                       match_list(m_kpt_ids, m_kpts, m_ref_kpts, m_point3d_ids, m_xyz, m_sids), m_count);
     return pram_launch_status("pram_track_correspond");
 }
 
@@ -258,9 +213,8 @@ extern "C" int pram_track_filter(const long long* kpt_ids, const float* kpts, co
                  (const void*)point3d_ids != (const void*)o_point3d_ids && (const void*)xyz != (const void*)o_xyz && (const void*)sids != (const void*)o_sids,
                  "pram_track_filter: the output lists must not be the input lists");
     if (batch == 0) return PRAM_OK;
-    const ListBufs in = {kpt_ids, kpts, ref_kpts, point3d_ids, reinterpret_cast<const long long*>(xyz), sids};
-    hipLaunchKernelGGL(track_filter_kernel, dim3(batch), dim3(256), 0, (hipStream_t)stream, in, count, mask, cap, o_kpt_ids, o_kpts, o_ref_kpts,
-                       o_point3d_ids, reinterpret_cast<long long*>(o_xyz), o_sids, o_count);
+    hipLaunchKernelGGL(track_filter_kernel, dim3(batch), dim3(256), 0, (hipStream_t)stream, match_list(kpt_ids, kpts, ref_kpts, point3d_ids, xyz, sids),
+                       count, mask, cap, match_list(o_kpt_ids, o_kpts, o_ref_kpts, o_point3d_ids, o_xyz, o_sids), o_count);
     return pram_launch_status("pram_track_filter");
 }
 

@@ -395,8 +395,7 @@ def _candidate_lists(cor: dict, host, m: dict, store: ReferenceStore, B: int, se
         for w in range(seg_k):
             p = b * seg_k + w
             l0, fr = int(col("lens0")[p]), int(col("frame")[p])
-            c = {k: cor[k][p, :l0] for k in ("matched_keypoints", "matched_keypoint_ids", "matched_xyzs", "matched_point3D_ids", "matched_sids",
-                                             "matched_ref_keypoints")}
+            c = {k: cor[k][p, :l0] for k in ops.MATCH_RESULT_KEYS}
             c.update(reference_frame_id=store.frame_ids[fr] if fr >= 0 else None, sid=int(col("sid")[p]),
                      semantic_matching=bool(col("semantic")[p]), n_query_kpts=l0, n_ref_kpts=int(col("lens1")[p]), order=w,
                      n_matches=cor["count"][p], matches0=m["matches0"][p, :l0], matching_scores0=m["matching_scores0"][p, :l0])

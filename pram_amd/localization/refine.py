@@ -30,8 +30,7 @@ from pram_amd import ops
 from pram_amd.localization import candidates as _cand
 from pram_amd.localization import pose as _pose
 
-_MATCHED = ("matched_keypoints", "matched_keypoint_ids", "matched_xyzs", "matched_point3D_ids", "matched_sids", "matched_ref_keypoints",
-            "matched_src")
+_MATCHED = ops.MATCH_RESULT_KEYS + (ops.MATCH_SRC,)
 
 
 @torch.no_grad()
@@ -103,7 +102,7 @@ def image_size_table(cameras) -> np.ndarray:
     return np.array([[int(c[1]), int(c[2])] for c in cameras], dtype=np.int32).reshape(-1, 2)
 
 
-_PROJ_MATCHED = ("matched_keypoints", "matched_keypoint_ids", "matched_xyzs", "matched_point3D_ids", "matched_sids")
+_PROJ_MATCHED = tuple(k for k in ops.MATCH_RESULT_KEYS if k != ops.MATCH_REF_KPTS)
 
 
 @torch.no_grad()

@@ -38,8 +38,7 @@ from pram_amd.localization import candidates as _cand
 from pram_amd.localization import pose as _pose
 from pram_amd.localization import refine as _refine
 
-_LISTS = ("matched_keypoints", "matched_keypoint_ids", "matched_xyzs", "matched_point3D_ids", "matched_sids", "matched_ref_keypoints")
-_COMMIT_KEYS = ("matched_keypoint_ids", "matched_point3D_ids", "matched_xyzs", "matched_sids")
+_LISTS, _COMMIT_KEYS = ops.MATCH_RESULT_KEYS, ops.MATCH_POINT_KEYS
 
 
 class TrackState:
@@ -167,8 +166,7 @@ class Tracker:
         counts, kp, sc, de = self._features(features)
         B, dev = counts.numel(), counts.device
         cap = max([int(v[1]["matched_keypoint_ids"].shape[0]) for v in members.values()] + [1])
-        cor = {"matched_keypoint_ids": torch.empty(B, cap, device=dev, dtype=torch.int64), "matched_point3D_ids": torch.empty(B, cap, device=dev, dtype=torch.int64),
-               "matched_xyzs": torch.empty(B, cap, 3, device=dev, dtype=torch.float64), "matched_sids": torch.empty(B, cap, device=dev, dtype=torch.int32)}
+        cor = ops._cor_alloc(B, cap, dev, _COMMIT_KEYS)
         mask = torch.zeros(B, cap, device=dev, dtype=torch.uint8)
         cnt, slot, ref = np.zeros(B, np.int32), np.full(B, -1, np.int32), np.full(B, -1, np.int32)
         for b, (s, lists, inl, fid) in members.items():

@@ -1523,6 +1523,40 @@ def cand_gather(plan: torch.Tensor, tokens: torch.Tensor, store, q_desc, q_kpts,
     return {"descriptors0": d[:P], "descriptors1": d[P:], "norm_keypoints0": k[:P], "norm_keypoints1": k[P:], "scores0": sc[:P], "scores1": sc[P:]}
 
 
+# The match list every stage hands on: parallel tensors [P, cap] + tail with count int32 [P].  Key -> (dtype, tail), in the order
+# the entries of pram_hip.h take the pointers.
+MATCH_LIST = {"matched_keypoint_ids": (_INT64, ()), "matched_keypoints": (torch.float32, (2,)), "matched_ref_keypoints": (torch.float32, (2,)),
+              "matched_point3D_ids": (_INT64, ()), "matched_xyzs": (torch.float64, (3,)), "matched_sids": (torch.int32, ())}
+MATCH_KEYS = tuple(MATCH_LIST)
+MATCH_REF_KPTS, MATCH_SRC = "matched_ref_keypoints", "matched_src"      # the list projref_correspond leaves out, the one refine_merge adds
+MATCH_NOREF_KEYS = tuple(k for k in MATCH_KEYS if k != MATCH_REF_KPTS)
+MATCH_POINT_KEYS = tuple(k for k in MATCH_NOREF_KEYS if k != "matched_keypoints")      # the four lists update_point3ds reads
+# the order the result dicts of localization/ list them in (the reference's)
+MATCH_RESULT_KEYS = tuple(MATCH_KEYS[i] for i in (1, 0, 4, 3, 5, 2))
+
+
+def _cor_chk(cor: dict, name: str, keys=MATCH_KEYS, src: bool = False):
+    """dtypes, contiguity and shapes of the lists ``keys`` of cor (src: and of matched_src) and of its count -> (P, cap)."""
+    P, t = cor["matched_keypoint_ids"].shape
+    for k in keys + ((MATCH_SRC,) if src else ()):
+        dt, tail = MATCH_LIST.get(k, (torch.int32, ()))
+        _chk(cor[k], f"{name}.{k}", dt)
+        assert cor[k].is_contiguous() and tuple(cor[k].shape) == (P, t) + tail, (name, k)
+    _chk(cor["count"], f"{name}.count", torch.int32)
+    assert cor["count"].is_contiguous() and cor["count"].numel() == P
+    return P, t
+
+
+def _cor_alloc(B: int, cap: int, dev, keys=MATCH_KEYS, src: bool = False) -> dict:
+    """Uninitialised lists ``keys`` [B, max(cap, 1)] (src: and matched_src), then count."""
+    c1 = max(int(cap), 1)
+    out = {k: torch.empty((B, c1) + MATCH_LIST[k][1], device=dev, dtype=MATCH_LIST[k][0]) for k in keys}
+    if src:
+        out[MATCH_SRC] = torch.empty(B, c1, device=dev, dtype=torch.int32)
+    out["count"] = torch.empty(B, device=dev, dtype=torch.int32)
+    return out
+
+
 def cand_correspond(matches0: torch.Tensor, plan: torch.Tensor, tokens: torch.Tensor, store, q_kpts: torch.Tensor, cap: int):
     """matches0 int64 [P, >= T0] -> dict of padded per-pair outputs [P, cap, ...] and count int32 [P] (pram_cand_correspond)."""
     L = _lib.load()
@@ -1531,18 +1565,12 @@ def cand_correspond(matches0: torch.Tensor, plan: torch.Tensor, tokens: torch.Te
     assert matches0.dim() == 2 and matches0.stride(1) == 1 and q_kpts.is_contiguous()
     P, t0 = matches0.shape
     assert plan.shape[1] == P
-    n, dev, cap = q_kpts.shape[1], matches0.device, int(cap)
-    c1 = max(cap, 1)
-    out = {"matched_keypoint_ids": torch.empty(P, c1, device=dev, dtype=_INT64), "matched_keypoints": torch.empty(P, c1, 2, device=dev),
-           "matched_ref_keypoints": torch.empty(P, c1, 2, device=dev), "matched_point3D_ids": torch.empty(P, c1, device=dev, dtype=_INT64),
-           "matched_xyzs": torch.empty(P, c1, 3, device=dev, dtype=torch.float64), "matched_sids": torch.empty(P, c1, device=dev, dtype=torch.int32),
-           "count": torch.empty(P, device=dev, dtype=torch.int32)}
+    n, cap = q_kpts.shape[1], int(cap)
+    out = _cor_alloc(P, cap, matches0.device)
     s = store
     _lib.check(L.pram_cand_correspond(_p(matches0), matches0.stride(0), _p(plan), _p(tokens), _p(s["sel_rows"]), _p(q_kpts), n, _p(s["keypoints"]),
                                       _p(s["xyzs"]), _p(s["point3D_ids"]), _p(s["keypoint_segs"]), int(s["n_rows"]), P, t0, cap,
-                                      _p(out["matched_keypoint_ids"]), _p(out["matched_keypoints"]), _p(out["matched_ref_keypoints"]),
-                                      _p(out["matched_point3D_ids"]), _p(out["matched_xyzs"]), _p(out["matched_sids"]), _p(out["count"]), _st()),
-               "pram_cand_correspond")
+                                      *[_p(out[k]) for k in MATCH_KEYS], _p(out["count"]), _st()), "pram_cand_correspond")
     return out
 
 
@@ -1689,21 +1717,6 @@ def refine_plan(chosen: torch.Tensor, loc_plan: torch.Tensor, counts: torch.Tens
     return plan, ref_frame, used, init_on
 
 
-_COR_KEYS = ("matched_keypoint_ids", "matched_keypoints", "matched_ref_keypoints", "matched_point3D_ids", "matched_xyzs", "matched_sids")
-
-
-def _cor_chk(cor: dict, name: str):
-    dts = (_INT64, torch.float32, torch.float32, _INT64, torch.float64, torch.int32)
-    P, t = cor["matched_keypoint_ids"].shape
-    tails = ((), (2,), (2,), (), (3,), ())
-    for k, dt, tail in zip(_COR_KEYS, dts, tails):
-        _chk(cor[k], f"{name}.{k}", dt)
-        assert cor[k].is_contiguous() and tuple(cor[k].shape) == (P, t) + tail, (name, k)
-    _chk(cor["count"], f"{name}.count", torch.int32)
-    assert cor["count"].is_contiguous() and cor["count"].numel() == P
-    return P, t
-
-
 def refine_merge(cor_ref: dict, cor_loc: dict, chosen: torch.Tensor, init_on: torch.Tensor, n_cov: int, out: Optional[dict] = None) -> dict:
     """cor_ref / cor_loc: cand_correspond's dicts for the B * n_cov refinement pairs and the B * seg_k localisation pairs
     -> one list per query, dict of [B, cap, ...] tensors (cap = n_cov * t0 + t0a) with the keys of cand_correspond plus
@@ -1717,21 +1730,14 @@ def refine_merge(cor_ref: dict, cor_loc: dict, chosen: torch.Tensor, init_on: to
     assert chosen.is_contiguous() and init_on.is_contiguous() and tuple(chosen.shape) == (B, 3) and Pr == B * n_cov
     seg_k = Pa // B if B else 1
     assert seg_k >= 1 and Pa == B * seg_k
-    dev = init_on.device
     if out is None:
-        cap = max(n_cov * t0 + t0a, 1)
-        out = {"matched_keypoint_ids": torch.empty(B, cap, device=dev, dtype=_INT64), "matched_keypoints": torch.empty(B, cap, 2, device=dev),
-               "matched_ref_keypoints": torch.empty(B, cap, 2, device=dev), "matched_point3D_ids": torch.empty(B, cap, device=dev, dtype=_INT64),
-               "matched_xyzs": torch.empty(B, cap, 3, device=dev, dtype=torch.float64), "matched_sids": torch.empty(B, cap, device=dev, dtype=torch.int32),
-               "matched_src": torch.empty(B, cap, device=dev, dtype=torch.int32), "count": torch.empty(B, device=dev, dtype=torch.int32)}
+        out = _cor_alloc(B, n_cov * t0 + t0a, init_on.device, src=True)
     else:
-        _cor_chk(out, "out")
-        _chk(out["matched_src"], "out.matched_src", torch.int32)
-        assert out["matched_src"].is_contiguous() and tuple(out["matched_src"].shape) == tuple(out["matched_sids"].shape) and out["count"].numel() == B
+        assert _cor_chk(out, "out", src=True)[0] == B
     cap = out["matched_sids"].shape[1]
     r, a, o = cor_ref, cor_loc, out
-    _lib.check(L.pram_refine_merge(*[_p(r[k]) for k in _COR_KEYS], _p(r["count"]), t0, *[_p(a[k]) for k in _COR_KEYS], _p(a["count"]), t0a,
-                                   _p(chosen), _p(init_on), B, seg_k, n_cov, cap, *[_p(o[k]) for k in _COR_KEYS], _p(o["matched_src"]),
+    _lib.check(L.pram_refine_merge(*[_p(r[k]) for k in MATCH_KEYS], _p(r["count"]), t0, *[_p(a[k]) for k in MATCH_KEYS], _p(a["count"]), t0a,
+                                   _p(chosen), _p(init_on), B, seg_k, n_cov, cap, *[_p(o[k]) for k in MATCH_KEYS], _p(o[MATCH_SRC]),
                                    _p(o["count"]), _st()), "pram_refine_merge")
     return out
 
@@ -1838,28 +1844,18 @@ def projref_correspond(accept: torch.Tensor, best: torch.Tensor, counts: torch.T
         _chk(t, nm, dt)
         assert t.is_contiguous(), nm
     B, N = accept.shape
-    cap, s, dev = cand_pt.shape[1], store, accept.device
+    cap, s = cand_pt.shape[1], store
     assert tuple(best.shape) == (B, N) and tuple(q_kpts.shape) == (B, N, 2) and counts.numel() == B and n_cand.numel() == B and cand_pt.shape[0] == B
-    n1 = max(N, 1)
     if out is None:
-        out = {"matched_keypoint_ids": torch.empty(B, n1, device=dev, dtype=_INT64), "matched_keypoints": torch.empty(B, n1, 2, device=dev),
-               "matched_point3D_ids": torch.empty(B, n1, device=dev, dtype=_INT64), "matched_xyzs": torch.empty(B, n1, 3, device=dev, dtype=torch.float64),
-               "matched_sids": torch.empty(B, n1, device=dev, dtype=torch.int32), "count": torch.empty(B, device=dev, dtype=torch.int32)}
+        out = _cor_alloc(B, N, accept.device, MATCH_NOREF_KEYS)
     else:
-        for k, dt, tail in (("matched_keypoint_ids", _INT64, ()), ("matched_keypoints", torch.float32, (2,)), ("matched_point3D_ids", _INT64, ()),
-                            ("matched_xyzs", torch.float64, (3,)), ("matched_sids", torch.int32, ())):
-            _chk(out[k], f"out.{k}", dt)
-            assert out[k].is_contiguous() and tuple(out[k].shape) == (B, n1) + tail, k
-        _chk(out["count"], "out.count", torch.int32)
-        assert out["count"].is_contiguous() and out["count"].numel() == B
-    o = out
+        assert _cor_chk(out, "out", MATCH_NOREF_KEYS) == (B, max(N, 1))
     if N == 0:      # no keypoints: the empty inputs have no storage to hand to the entry
-        o["count"].zero_()
+        out["count"].zero_()
         return out
     _lib.check(L.pram_projref_correspond(_p(accept), _p(best), _p(counts), _p(q_kpts), B, N, _p(cand_pt), _p(n_cand), cap, _p(s["pt_ids"]),
-                                         _p(s["pt_xyz"]), _p(s["pt_sid"]), int(s["n_points"]), _p(o["matched_keypoint_ids"]), _p(o["matched_keypoints"]),
-                                         _p(o["matched_point3D_ids"]), _p(o["matched_xyzs"]), _p(o["matched_sids"]), _p(o["count"]), _st()),
-               "pram_projref_correspond")
+                                         _p(s["pt_xyz"]), _p(s["pt_sid"]), int(s["n_points"]), *[_p(out[k]) for k in MATCH_NOREF_KEYS],
+                                         _p(out["count"]), _st()), "pram_projref_correspond")
     return out
 
 
@@ -1899,14 +1895,6 @@ def track_gather_tables(st: dict, dummy: torch.Tensor) -> dict:
             "n_rows": int(st["n_slots"]) * int(st["n_max"])}
 
 
-def _cor_alloc(B: int, cap: int, dev) -> dict:
-    c1 = max(int(cap), 1)
-    return {"matched_keypoint_ids": torch.empty(B, c1, device=dev, dtype=_INT64), "matched_keypoints": torch.empty(B, c1, 2, device=dev),
-            "matched_ref_keypoints": torch.empty(B, c1, 2, device=dev), "matched_point3D_ids": torch.empty(B, c1, device=dev, dtype=_INT64),
-            "matched_xyzs": torch.empty(B, c1, 3, device=dev, dtype=torch.float64), "matched_sids": torch.empty(B, c1, device=dev, dtype=torch.int32),
-            "count": torch.empty(B, device=dev, dtype=torch.int32)}
-
-
 def track_correspond(matches0: torch.Tensor, plan: torch.Tensor, st: dict, q_kpts: torch.Tensor, cap: int, out: Optional[dict] = None) -> dict:
     """matches0 int64 [B, >= t0] -> cand_correspond's dict, [B, cap, ...] and count int32 [B] (pram_track_correspond).  ``out``:
     buffers to write into (the tests pre-fill them)."""
@@ -1926,7 +1914,7 @@ def track_correspond(matches0: torch.Tensor, plan: torch.Tensor, st: dict, q_kpt
         assert out["matched_sids"].shape[0] == P and out["matched_sids"].shape[1] >= cap
         cap = out["matched_sids"].shape[1]
     _lib.check(L.pram_track_correspond(_p(matches0), matches0.stride(0) if P else t0, _p(plan), _p(q_kpts), n, _p(st["keypoints"]), _p(st["xyzs"]),
-                                       _p(st["point3D_ids"]), _p(st["seg_ids"]), S, n_max, P, t0, cap, *[_p(out[k]) for k in _COR_KEYS],
+                                       _p(st["point3D_ids"]), _p(st["seg_ids"]), S, n_max, P, t0, cap, *[_p(out[k]) for k in MATCH_KEYS],
                                        _p(out["count"]), _st()), "pram_track_correspond")
     return out
 
@@ -1942,7 +1930,7 @@ def track_filter(cor: dict, mask: torch.Tensor, out: Optional[dict] = None) -> d
         out = _cor_alloc(B, cap, mask.device)
     else:
         assert _cor_chk(out, "out") == (B, cap)
-    _lib.check(L.pram_track_filter(*[_p(cor[k]) for k in _COR_KEYS], _p(cor["count"]), _p(mask), B, cap, *[_p(out[k]) for k in _COR_KEYS],
+    _lib.check(L.pram_track_filter(*[_p(cor[k]) for k in MATCH_KEYS], _p(cor["count"]), _p(mask), B, cap, *[_p(out[k]) for k in MATCH_KEYS],
                                    _p(out["count"]), _st()), "pram_track_filter")
     return out
 
@@ -1962,13 +1950,7 @@ def track_commit(st: dict, q_kpts: torch.Tensor, q_scores: torch.Tensor, q_desc:
         _chk(t, nm, dt)
         assert t.is_contiguous(), nm
     B, n, D = q_desc.shape
-    Bc, cap = cor["matched_keypoint_ids"].shape
-    for k, dt, tail in (("matched_keypoint_ids", _INT64, ()), ("matched_point3D_ids", _INT64, ()), ("matched_xyzs", torch.float64, (3,)),
-                        ("matched_sids", torch.int32, ())):      # the four lists update_point3ds reads
-        _chk(cor[k], f"lists.{k}", dt)
-        assert cor[k].is_contiguous() and tuple(cor[k].shape) == (Bc, cap) + tail, k
-    _chk(cor["count"], "lists.count", torch.int32)
-    assert cor["count"].is_contiguous() and cor["count"].numel() == Bc
+    Bc, cap = _cor_chk(cor, "lists", MATCH_POINT_KEYS)
     assert D == 128 and tuple(q_kpts.shape) == (B, n, 2) and tuple(q_scores.shape) == (B, n) and counts.numel() == B and slot.numel() == B
     assert ref_frame.numel() == B and len(slot_host) == B and Bc == B and (seg_ids is None or tuple(seg_ids.shape) == (B, n))
     assert mask is None or tuple(mask.shape) == (B, cap)
@@ -1978,7 +1960,7 @@ def track_commit(st: dict, q_kpts: torch.Tensor, q_scores: torch.Tensor, q_desc:
     assert winner.is_contiguous() and winner.numel() >= B * n
     host = (ctypes.c_int * max(B, 1))(*[int(s) for s in slot_host])
     _lib.check(L.pram_track_commit(_p(q_kpts), _p(q_scores), _p(q_desc), _p(counts), _p(seg_ids), _p(slot), ctypes.addressof(host), _p(ref_frame), B, n,
-                                   float(q_norm[0]), float(q_norm[1]), float(q_norm[2]), _p(cor["matched_keypoint_ids"]), _p(cor["matched_point3D_ids"]),
-                                   _p(cor["matched_xyzs"]), _p(cor["matched_sids"]), _p(cor["count"]), _p(mask), cap, _p(st["keypoints"]),
+                                   float(q_norm[0]), float(q_norm[1]), float(q_norm[2]), *[_p(cor[k]) for k in MATCH_POINT_KEYS], _p(cor["count"]),
+                                   _p(mask), cap, _p(st["keypoints"]),
                                    _p(st["scores"]), _p(st["descriptors"]), _p(st["counts"]), _p(st["xyzs"]), _p(st["point3D_ids"]), _p(st["seg_ids"]),
                                    _p(st["ref_frame"]), _p(st["frame_norm"]), S, n_max, _p(winner), _st()), "pram_track_commit")

@@ -395,3 +395,54 @@ def test_ctypes_entries_on_a_hand_written_store(hip_lib, dev):
     assert run_cor(ldm=2) == E_ARG
     assert L.pram_cand_mask_ranks(p(idx), p(counts), 1, n, 0, st) == E_ARG
     assert L.pram_cand_mask_ranks(None, p(counts), 1, n, 8, st) == E_ARG
+
+
+@pytest.mark.parametrize("cap", [513, 100])
+def test_correspond_chunk_and_wave_boundaries(hip_lib, dev, cap):
+    """pram_cand_correspond alone on a hand-written plan, against cand_ref.correspondences: pair lengths at and around the wave's
+    64 and the workgroup's chunk of 256 (63, 64, 65, 256, 257, 513), seeded matches with a share of -1, a pair where every
+    keypoint matches and one where none does, pairs read through the token and the selected-row tables; cap 100 cuts the list
+    inside the first chunk.  Every field bit-equal, rows beyond the count keep the sentinel they were filled with."""
+    L = hip_lib
+    rng = np.random.default_rng(41)
+    p = lambda t: C.c_void_p(t.data_ptr())
+    to = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+    lens0 = [63, 64, 65, 256, 257, 513, 513, 513, 513]
+    P, B, n, R = len(lens0), 2, 513, 600
+    frame = {"keypoints": rng.uniform(0, 640, (R, 3)).astype(np.float32), "xyzs": rng.standard_normal((R, 3)),
+             "point3D_ids": rng.integers(0, 2 ** 40, R), "keypoint_segs": rng.integers(-1, 50, R).astype(np.int32)}
+    qk = rng.uniform(0, 640, (B, n, 2)).astype(np.float32)
+    tokens, sel_rows = rng.permutation(n).astype(np.int32), rng.permutation(R).astype(np.int32)
+    m0 = rng.integers(0, R, (P, n))
+    m0[rng.uniform(0, 1, (P, n)) < 0.4] = -1
+    m0[6], m0[7] = rng.integers(0, R, n), -1      # every keypoint matched; none
+    plan = np.zeros((10, P), np.int32)
+    cands = []
+    for i, l0 in enumerate(lens0):
+        with_tokens, with_sel = i == 8, i % 2 == 1
+        plan[:, i] = [i % B, 0, 0, with_tokens, l0, R, 0 if with_tokens else -1, 0, 0 if with_sel else -1, 0]
+        cands.append({"matches0": m0[i, :l0], "q_kpt_ids": (tokens[:l0] if with_tokens else np.arange(l0)).astype(np.int64),
+                      "ref_rows": sel_rows if with_sel else np.arange(R)})
+    keys = (("matched_keypoint_ids", torch.int64, ()), ("matched_keypoints", torch.float32, (2,)), ("matched_ref_keypoints", torch.float32, (2,)),
+            ("matched_point3D_ids", torch.int64, ()), ("matched_xyzs", torch.float64, (3,)), ("matched_sids", torch.int32, ()))
+    out = {k: torch.full((P, cap) + tail, -7, dtype=dt, device=dev) for k, dt, tail in keys}
+    cnt = torch.full((P,), -7, dtype=torch.int32, device=dev)
+    dm0, dplan, dtok, dsel, dqk = to(m0), to(plan), to(tokens), to(sel_rows), to(qk)
+    r_kpts, r_xyz, r_p3d, r_segs = to(frame["keypoints"][:, :2]), to(frame["xyzs"]), to(frame["point3D_ids"]), to(frame["keypoint_segs"])
+    st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    assert L.pram_cand_correspond(p(dm0), n, p(dplan), p(dtok), p(dsel), p(dqk), n, p(r_kpts), p(r_xyz), p(r_p3d), p(r_segs), R, P, n, cap,
+                                  *[p(out[k]) for k, _, _ in keys], p(cnt), st) == 0
+    got_counts = cnt.cpu().tolist()
+    bits = lambda a: np.ascontiguousarray(a).reshape(-1).view(np.uint8)
+    capped = 0
+    for i, c in enumerate(cands):
+        want = CR.correspondences(c, {"keypoints": qk[i % B]}, frame)
+        full = len(want["matched_keypoint_ids"])
+        m = min(full, cap)
+        capped += full > cap
+        assert got_counts[i] == m, (i, got_counts[i], m)
+        for k, dt, tail in keys:
+            g = out[k][i].cpu().numpy()
+            assert np.array_equal(bits(g[:m]), bits(np.asarray(want[k])[:m].astype(g.dtype))), (i, k)
+            assert (g[m:] == -7).all(), (i, k, "rows beyond the count were written")
+    assert got_counts[6] == min(513, cap) and got_counts[7] == 0 and (capped >= 4) == (cap == 100)

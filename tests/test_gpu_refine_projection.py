@@ -119,6 +119,48 @@ def test_mark_project_exact(dev, n_points):
     assert want[2] is None and want[3] is None      # not located; disabled
 
 
+def test_project_two_sweeps_and_three_chunks(dev):
+    """pram_projref_project alone on hand-made bitmaps over 32 * 1024 + 33 points: the bitmap is two sweeps of 1024 words long and
+    its last word holds one point (the bits beyond it are set and must not count).  Query 0 marks 300 points, among them the
+    first and last of a word, of a wave's 64 words and of each sweep; query 1 marks 2500, so the projection compacts in place over
+    three chunks of 1024 candidates; query 2 is not located.  n_union, n_cand and cand_pt exact against projref_ref.project, cand_uv
+    1e-9 (test_mark_project_exact's bar)."""
+    from pram_amd import ops
+    rng = np.random.default_rng(61)
+    n_points = 32 * 1024 + 33
+    words = (n_points + 31) // 32
+    edge = np.array([0, 31, 32, 2047, 2048, 32767, 32768, 32799, 32800])
+    pool = np.setdiff1d(np.arange(n_points), edge)
+    marks = [np.sort(np.concatenate([edge, rng.choice(pool, k - len(edge), replace=False)])) for k in (300, 2500)]
+    bits = np.zeros((3, words * 32), bool)
+    bits[0, marks[0]], bits[1, marks[1]] = True, True
+    bits[:, n_points:] = True
+    bitmap = _t(np.packbits(bits, axis=1, bitorder="little").view(np.int32), torch.int32, dev)
+    xyz = np.stack([rng.uniform(-40, 40, n_points), rng.uniform(-30, 30, n_points), rng.uniform(-30, 160, n_points)], 1)
+    tables = {"pt_xyz": _t(xyz, torch.float64, dev), "n_points": n_points}
+    cams = [PJ.MARK_CAMERAS[0], PJ.MARK_CAMERAS[1], PJ.MARK_CAMERAS[4]]
+    (cam_model, cam_params, _), sizes = _cams(cams, dev)
+    B, seg_k, cap = 3, 2, 2500
+    chosen = np.array([[0, 1, 0], [1, 1, 1], [-1, 0, -1]], np.int32)
+    qvec, tvec = np.full((B * seg_k, 4), np.nan), np.full((B * seg_k, 3), np.nan)
+    for b in range(2):
+        qvec[b * seg_k + chosen[b, 0]] = PR.rot_to_qvec(PR.rodrigues(rng.standard_normal(3) * 0.05))
+        tvec[b * seg_k + chosen[b, 0]] = rng.standard_normal(3) * 0.5
+    cand_pt, cand_uv, n_union, n_cand = (x.cpu().numpy() for x in ops.projref_project(
+        bitmap, _t(chosen, torch.int32, dev), _t(qvec, torch.float64, dev), _t(tvec, torch.float64, dev), cam_model, cam_params, sizes, tables, cap))
+    assert n_union[2] == 0 and n_cand[2] == 0
+    for b in range(2):
+        row, cam = b * seg_k + chosen[b, 0], cams[b]
+        u, v, _, mask = PJ.project(xyz[marks[b]], PJ.intrinsics(cam), PJ.qvec2rotmat(qvec[row]), tvec[row], cam[1], cam[2])
+        n = int(mask.sum())
+        assert n_union[b] == len(marks[b]) and n_cand[b] == n, (b, n_union[b], n_cand[b], n)
+        assert np.array_equal(cand_pt[b, :n], marks[b][mask]), b
+        assert np.abs(cand_uv[b, :, :n] - np.stack([u[mask], v[mask]])).max() <= 1e-9, b
+        # survivors and drop-outs in every chunk of 1024 candidates, so every chunk moves rows
+        for c0 in range(0, len(marks[b]), 1024):
+            assert mask[c0:c0 + 1024].any() and not mask[c0:c0 + 1024].all(), (b, c0)
+
+
 @pytest.fixture(scope="module")
 def match_cases():
     """The crafted inputs and their dense expectation, computed once."""

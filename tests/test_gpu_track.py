@@ -553,3 +553,24 @@ def test_ctypes_entries(hip_lib, dev):
     assert run_commit(n_=n_max + 1) == E_ARG and b"n <= n_max" in L.pram_last_error()
     assert run_commit(winner_=None) == E_ARG and b"null" in L.pram_last_error()
     assert s_cnt.tolist() == [2, 0, 3]
+
+
+@pytest.mark.parametrize("mask_kind", ["seeded", "all", "none"])
+def test_track_filter_chunk_and_wave_boundaries(dev, mask_kind):
+    """List lengths at and around the wave's 64 and the workgroup's chunk of 256, and two chunks and one row (513); a seeded mask
+    puts survivors on both sides of every boundary.  Bit-equal to numpy's boolean indexing, rows beyond the count untouched."""
+    from pram_amd import ops
+    rng = np.random.default_rng(29)
+    counts = [63, 64, 65, 256, 257, 513]
+    B, cap = len(counts), 513
+    cor = {k: _random_bytes(rng, (B, cap) + tail, dt, dev) for k, dt, tail in zip(COR_KEYS, COR_DTYPES, COR_TAILS)}
+    cor["count"] = torch.tensor(counts, dtype=torch.int32, device=dev)
+    mask = {"seeded": (rng.uniform(0, 1, (B, cap)) < 0.5).astype(np.uint8), "all": np.ones((B, cap), np.uint8), "none": np.zeros((B, cap), np.uint8)}[mask_kind]
+    out = ops.track_filter(cor, torch.from_numpy(mask).to(dev), out=_sentinel_cor(B, cap, dev))
+    sentinel = _sentinel_cor(B, cap, dev)
+    for b in range(B):
+        keep = np.nonzero(mask[b, :counts[b]])[0]
+        assert int(out["count"][b]) == len(keep), (b, mask_kind)
+        for k in COR_KEYS:
+            assert np.array_equal(_bits(out[k][b, :len(keep)]), _bits(cor[k][b].cpu().numpy()[keep])), (b, k)
+            assert np.array_equal(_bits(out[k][b, len(keep):]), _bits(sentinel[k][b, len(keep):])), (b, k)
