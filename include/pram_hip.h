@@ -919,6 +919,49 @@ int pram_track_commit(const float* q_kpts, const float* q_scores, const float* q
                       float* st_desc, int* st_counts, double* st_xyz, long long* st_point3d_ids, int* st_segs, int* st_ref_frame,
                       float* st_frame_norm, int n_slots, int n_max, int* winner, void* stream);
 
+/* ---- Map building (csrc/mapbuild.hip; pram_amd/localization/mapbuild.py drives these): the two inputs of a ReferenceStore that
+ * the reference computes offline on the CPU (recognition/recmap.py).  Both take tables of the store as they lie on the device.
+ * An offset table also comes as a HOST copy: the workspace size and the table's shape are checked from it without touching the
+ * device, and nothing is read back. */
+#define PRAM_MAPBUILD_SHORT_TRACK 32   /* tracks up to this many entries: Gram matrix and rank selection in LDS */
+#define PRAM_MAPBUILD_ROW_LDS 512      /* longer tracks up to this many entries keep the current Gram row in LDS, beyond: workspace */
+#define PRAM_MAPBUILD_MAX_VRF 64
+#define PRAM_MAPBUILD_CAM_COLS 13      /* qw qx qy qz tx ty tz fx fy cx cy width height */
+
+/* RecMap.assign_point3D_descriptor (recmap.py:124-194).  One workgroup per point p, whose track is the entries trk_off[p] ..
+ * trk_off[p + 1] of trk_frame (store frame index; -1: an image the map does not hold) and trk_kpt (keypoint index inside the
+ * frame).  An entry with frame -1, a frame outside [0, n_frames) or a keypoint outside its frame is dropped.  Over the kept
+ * entries i: d_ij = 2 - 2 <a_i, a_j> in float64 (the products of the fp32 rows are exact and are added in one fixed order for
+ * every pair — four dimensions to a lane in ascending order, then a butterfly over 32 lanes: d_ij == d_ji bit for bit), m_i = numpy's median of row i, and the FIRST i with the smallest
+ * m_i is chosen.  pt_choice [n_points]: its position in the track, -1 when nothing was kept; pt_desc [n_points][128]: a bit copy
+ * of its row of descriptors [n_rows][128] (16-byte aligned), zeros for -1.  Descriptors are finite.  workspace: 12 bytes per
+ * entry up to the end of the last track longer than PRAM_MAPBUILD_SHORT_TRACK, as the size function says. */
+size_t pram_mapbuild_desc_workspace_bytes(const int* trk_off_host, int n_points);
+int pram_mapbuild_assign_descriptors(const float* descriptors, const int* frame_off, int n_frames, int n_rows, const int* trk_off,
+                                     const int* trk_off_host, const int* trk_frame, const int* trk_kpt, int n_points, void* workspace,
+                                     size_t workspace_bytes, float* pt_desc, int* pt_choice, void* stream);
+
+/* find_best_vrf_by_covisibility with the filter of RecMap.create_virtual_frame_3 around it (recmap.py:263-355, 369-403).  One
+ * workgroup per landmark l, whose points are lm_points[lm_off[l] .. lm_off[l + 1]) in the label file's order (ids the point
+ * table lacks and repeated ids allowed).  point3d_ids [n_rows] / frame_off: the store's rows; pt_ids (ascending) / pt_off /
+ * pt_frames / pt_xyz [n_points][3]: its point table; frame_ignored [n_frames]; frame_cams [n_frames][PRAM_MAPBUILD_CAM_COLS]
+ * float64.  A frame's observation count is the number of its rows with id > 0.  Candidates: the frames listed by the landmark's
+ * points that the table holds, minus ignored ones; those with count >= min_obs by count descending, then by first encounter in
+ * the double loop over the points and each point's frame list, cut at topk_imgs; when no frame reaches min_obs every
+ * encountered frame by first encounter.  A candidate's mask has a bit per list position whose id (> 0; a repeated id: its first
+ * position) a row of the frame carries.  Greedy cover: the first candidate with the largest popcount(mask & unobserved), a gain
+ * of 0 allowed; stop at coverage >= min_cover_ratio, after a pick with gain / len < gain_floor, at n_vrf picks or when no
+ * candidate is left.  A picked frame is dropped unless a point of the list with id >= 0 that the table holds is a row of the
+ * frame and K (R x + t) / z lies inside [0, width) x [0, height) (float64, no depth test).  lm_vrf [n_landmarks][n_vrf]: store
+ * frame indices in pick order, padded with -1; lm_vrf_n [n_landmarks]. */
+size_t pram_mapbuild_vrf_workspace_bytes(int n_landmarks, int n_lm_points, int n_frames);
+int pram_mapbuild_select_frames(const long long* point3d_ids, const int* frame_off, int n_frames, int n_rows, const long long* pt_ids,
+                                const int* pt_off, const int* pt_frames, int n_points, int n_entries, const double* pt_xyz,
+                                const int* lm_off, const int* lm_off_host, const long long* lm_points, int n_landmarks,
+                                const int* frame_ignored, const double* frame_cams, int min_obs, int topk_imgs, int n_vrf,
+                                double min_cover_ratio, double gain_floor, void* workspace, size_t workspace_bytes, int* lm_vrf,
+                                int* lm_vrf_n, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

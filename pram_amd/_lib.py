@@ -123,6 +123,10 @@ _SIGS = {
     "pram_track_correspond": (I, [P, I, P, P, I, P, P, P, P, I, I, I, I, I, P, P, P, P, P, P, P, P]),
     "pram_track_filter": (I, [P, P, P, P, P, P, P, P, I, I, P, P, P, P, P, P, P, P]),
     "pram_track_commit": (I, [P, P, P, P, P, P, P, P, I, I, F, F, F, P, P, P, P, P, P, I, P, P, P, P, P, P, P, P, P, I, I, P, P]),
+    "pram_mapbuild_desc_workspace_bytes": (SZ, [P, I]),
+    "pram_mapbuild_assign_descriptors": (I, [P, P, I, I, P, P, P, P, I, P, SZ, P, P, P]),
+    "pram_mapbuild_vrf_workspace_bytes": (SZ, [I, I, I]),
+    "pram_mapbuild_select_frames": (I, [P, P, I, I, P, P, P, I, I, P, P, P, P, I, P, P, I, I, I, C.c_double, C.c_double, P, SZ, P, P, P]),
 }
 
 

@@ -1964,3 +1964,80 @@ def track_commit(st: dict, q_kpts: torch.Tensor, q_scores: torch.Tensor, q_desc:
                                    _p(mask), cap, _p(st["keypoints"]),
                                    _p(st["scores"]), _p(st["descriptors"]), _p(st["counts"]), _p(st["xyzs"]), _p(st["point3D_ids"]), _p(st["seg_ids"]),
                                    _p(st["ref_frame"]), _p(st["frame_norm"]), S, n_max, _p(winner), _st()), "pram_track_commit")
+
+
+# ---- map building (csrc/mapbuild.hip; pram_amd/localization/mapbuild.py drives these) ------------------------------------------
+MAPBUILD_SHORT_TRACK, MAPBUILD_ROW_LDS, MAPBUILD_MAX_VRF, MAPBUILD_CAM_COLS = 32, 512, 64, 13      # include/pram_hip.h
+
+
+def _host_offsets(off_host, name: str):
+    """A CSR offset table on the host as a ctypes int array (what the entries validate) and its length - 1."""
+    import ctypes
+    import numpy as np
+    a = np.ascontiguousarray(np.asarray(off_host).reshape(-1), dtype=np.int32)
+    if a.size < 1:
+        raise _lib.PramHipError(f"{name}: an offset table has at least one entry")
+    return (ctypes.c_int * a.size).from_buffer_copy(a.tobytes()), a.size - 1
+
+
+def mapbuild_assign_descriptors(store, trk_off: torch.Tensor, trk_off_host, trk_frame: torch.Tensor, trk_kpt: torch.Tensor,
+                                workspace: Optional[torch.Tensor] = None):
+    """``store``: the device tables of a ReferenceStore; the tracks as CSR, trk_off int32 [P + 1] with its host copy, trk_frame /
+    trk_kpt int32 [E] (store frame index or -1, keypoint index inside the frame) -> (pt_desc float32 [P, 128], pt_choice int32 [P]:
+    the position of the chosen entry in the track, -1 for a track with nothing kept).  ``workspace``: uint8, at least
+    pram_mapbuild_desc_workspace_bytes; None allocates it."""
+    import ctypes
+    L = _lib.load()
+    for t, nm in ((trk_off, "trk_off"), (trk_frame, "trk_frame"), (trk_kpt, "trk_kpt")):
+        _chk(t, nm, torch.int32)
+        assert t.is_contiguous(), nm
+    s = store
+    _chk(s["descriptors"], "descriptors")
+    host, P = _host_offsets(trk_off_host, "trk_off")
+    E = int(host[P])
+    assert trk_off.numel() >= P + 1 and trk_frame.numel() >= E and trk_kpt.numel() >= E and s["descriptors"].is_contiguous() and s["descriptors"].shape[-1] == 128
+    dev = trk_off.device
+    need = int(L.pram_mapbuild_desc_workspace_bytes(ctypes.addressof(host), P))
+    if workspace is None:
+        workspace = torch.empty(max(need, 8), device=dev, dtype=torch.uint8)
+    _chk(workspace, "workspace", torch.uint8)
+    pt_desc = torch.empty(max(P, 1), 128, device=dev, dtype=torch.float32)
+    pt_choice = torch.empty(max(P, 1), device=dev, dtype=torch.int32)
+    _lib.check(L.pram_mapbuild_assign_descriptors(_p(s["descriptors"]), _p(s["frame_off"]), int(s["n_frames"]), int(s["n_rows"]), _p(trk_off),
+                                                  ctypes.addressof(host), _p(trk_frame), _p(trk_kpt), P, _p(workspace), workspace.numel(),
+                                                  _p(pt_desc), _p(pt_choice), _st()), "pram_mapbuild_assign_descriptors")
+    return pt_desc[:P], pt_choice[:P]
+
+
+def mapbuild_select_frames(store, pt_xyz: torch.Tensor, lm_off: torch.Tensor, lm_off_host, lm_points: torch.Tensor, frame_ignored: torch.Tensor,
+                           frame_cams: torch.Tensor, min_obs: int = 120, topk_imgs: int = 500, n_vrf: int = 10, min_cover_ratio: float = 0.9,
+                           gain_floor: float = 0.01, workspace: Optional[torch.Tensor] = None):
+    """``store``: the device tables of a ReferenceStore (rows and point table); pt_xyz float64 [n_points, 3] aligned with pt_ids; the
+    landmarks as CSR, lm_off int32 [L + 1] with its host copy and lm_points int64 [sum]; frame_ignored int32 [F]; frame_cams float64
+    [F, MAPBUILD_CAM_COLS] (qvec, tvec, fx, fy, cx, cy, width, height) -> (lm_vrf int32 [L, n_vrf] store frame indices padded with
+    -1, lm_vrf_n int32 [L]).  ``workspace``: uint8, at least pram_mapbuild_vrf_workspace_bytes; None allocates it."""
+    import ctypes
+    L = _lib.load()
+    s = store
+    for t, nm, dt in ((pt_xyz, "pt_xyz", torch.float64), (lm_off, "lm_off", torch.int32), (lm_points, "lm_points", _INT64),
+                      (frame_ignored, "frame_ignored", torch.int32), (frame_cams, "frame_cams", torch.float64)):
+        _chk(t, nm, dt)
+        assert t.is_contiguous(), nm
+    host, n_lm = _host_offsets(lm_off_host, "lm_off")
+    total = int(host[n_lm])
+    F, n_points, n_vrf = int(s["n_frames"]), int(s["n_points"]), int(n_vrf)
+    assert lm_off.numel() >= n_lm + 1 and lm_points.numel() >= total and frame_ignored.numel() >= F and frame_cams.numel() >= F * MAPBUILD_CAM_COLS
+    assert pt_xyz.numel() >= 3 * n_points
+    dev = lm_off.device
+    need = int(L.pram_mapbuild_vrf_workspace_bytes(n_lm, max(total, 0), F))
+    if workspace is None:
+        workspace = torch.empty(max(need, 8), device=dev, dtype=torch.uint8)
+    _chk(workspace, "workspace", torch.uint8)
+    lm_vrf = torch.empty(max(n_lm, 1), max(n_vrf, 1), device=dev, dtype=torch.int32)
+    lm_vrf_n = torch.empty(max(n_lm, 1), device=dev, dtype=torch.int32)
+    _lib.check(L.pram_mapbuild_select_frames(_p(s["point3D_ids"]), _p(s["frame_off"]), F, int(s["n_rows"]), _p(s["pt_ids"]), _p(s["pt_off"]),
+                                             _p(s["pt_frames"]), n_points, int(s["n_pt_entries"]), _p(pt_xyz), _p(lm_off), ctypes.addressof(host),
+                                             _p(lm_points), n_lm, _p(frame_ignored), _p(frame_cams), int(min_obs), int(topk_imgs), n_vrf,
+                                             float(min_cover_ratio), float(gain_floor), _p(workspace), workspace.numel(), _p(lm_vrf), _p(lm_vrf_n),
+                                             _st()), "pram_mapbuild_select_frames")
+    return lm_vrf[:n_lm], lm_vrf_n[:n_lm]
