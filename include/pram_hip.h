@@ -962,6 +962,50 @@ int pram_mapbuild_select_frames(const long long* point3d_ids, const int* frame_o
                                 double min_cover_ratio, double gain_floor, void* workspace, size_t workspace_bytes, int* lm_vrf,
                                 int* lm_vrf_n, void* stream);
 
+/* ---- Map compression (csrc/compress.hip; pram_amd/localization/compress.py drives these): RecMap.compress_map_by_projection_v2
+ * (recmap.py:668-922) and the rows RefFrame.associate_keypoints_with_point3Ds (refframe.py:99-147) gives a compressed frame.
+ * Frames, rows and the point table are a ReferenceStore's, as they lie on the device; frame_cams as for map building.  Tables
+ * the host walks to enqueue the steps come as HOST arrays; nothing is read back. */
+#define PRAM_COMPRESS_ROW_TILE 256     /* candidate rows per workgroup of the test step */
+#define PRAM_COMPRESS_KPT_TILE 256     /* kept keypoints of a chain frame per LDS tile */
+
+/* One workspace serves the selection and the sparsification: 24 bytes per row, 4 (covisibility_frame + 1) + 16 besides. */
+size_t pram_compress_workspace_bytes(int n_rows, int covisibility_frame);
+
+/* Selection (recmap.py:695-828).  A row is valid when its id is not -1 and pt_ids (ascending) holds it.  vrf_host [n_vrf]: the
+ * reference frames in order (a repeated one is taken again); covis_off_host [n_frames + 1] / covis_frames_host: every frame's
+ * candidates in order, at most covisibility_frame each, at least one for every frame of vrf_host.  For each v of vrf_host: v is
+ * retained with all its valid rows kept (over an earlier partial retention; its place in the retained order stays) and starts
+ * the chain; then each candidate c != v in order: a retained c joins the chain; otherwise a valid row of c with xyz x is
+ * discarded when for some chain frame k, p = R_k x + t_k, u = (fx p_x + cx p_z) / p_z, v likewise, 0 <= u < width,
+ * 0 <= v < height, p_z > 0 and sqrt(dx * dx + dy * dy) <= radius for a KEPT row of k with keypoint xys [n_rows][2] (float64);
+ * with a row left c is retained with the rows left and joins the chain, with none nothing happens.  A chain frame without kept
+ * rows discards nothing; a candidate without valid rows is never retained.  Launches: one begin per v, a test (row tiles x
+ * covisibility_frame + 1 chain slots) and a commit per candidate; the kernels read the state to decide what a step does; no
+ * workgroup waits for another.  ret_order [n_frames]: the frame's place in the retained order, -1 when not retained; list_cnt
+ * [n_frames] and list_pt [n_rows]: frame f's kept rows as indices into pt_ids, in row order, at list_pt[frame_off[f] ..]. */
+int pram_compress_select(const long long* point3d_ids, const int* frame_off, const int* frame_off_host, int n_frames, int n_rows,
+                         const long long* pt_ids, int n_points, const double* pt_xyz, const double* xys, const double* frame_cams,
+                         const int* covis_off_host, const int* covis_frames_host, int covisibility_frame, const int* vrf_host,
+                         int n_vrf, double radius, void* workspace, size_t workspace_bytes, int* ret_order, int* list_cnt,
+                         int* list_pt, void* stream);
+
+/* sparsify_by_grid (recmap.py:670-693, 852-860) in place on the lists of pram_compress_select, for every frame listing more
+ * than nkpts points; one workgroup per frame.  A listed point projects with the frame's own pose (no in-image or depth test)
+ * into cell iw = rint(u // radius), ih likewise (numpy's float floor division), key ih * ceil(width / radius) + iw in 64 bits.
+ * Per key the highest pt_score [n_points] wins, the earlier position on a tie; the winners leave in the order in which their
+ * keys first appear.  A point whose projection is not finite is dropped. */
+int pram_compress_sparsify(const int* frame_off, int n_frames, int n_rows, const double* frame_cams, const double* pt_xyz,
+                           const int* pt_score, int n_points, double radius, int nkpts, void* workspace, size_t workspace_bytes,
+                           int* list_pt, int* list_cnt, void* stream);
+
+/* The rows of the compressed frames: row i is point row_point[i] (an index into the point table) seen from frame row_frame[i].
+ * out_kpts [n_out][3] float64: the projection and the score 1 / clip(5 pt_err, 1, 20); out_xyz, out_desc [n_out][128], out_sid,
+ * out_ids: the point's values.  An index out of range gives zeros and id -1. */
+int pram_compress_rows(const int* row_frame, const int* row_point, int n_out, int n_frames, int n_points, const double* frame_cams,
+                       const long long* pt_ids, const double* pt_xyz, const float* pt_desc, const int* pt_sid, const double* pt_err,
+                       double* out_kpts, double* out_xyz, float* out_desc, int* out_sid, long long* out_ids, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -127,6 +127,10 @@ _SIGS = {
     "pram_mapbuild_assign_descriptors": (I, [P, P, I, I, P, P, P, P, I, P, SZ, P, P, P]),
     "pram_mapbuild_vrf_workspace_bytes": (SZ, [I, I, I]),
     "pram_mapbuild_select_frames": (I, [P, P, I, I, P, P, P, I, I, P, P, P, P, I, P, P, I, I, I, C.c_double, C.c_double, P, SZ, P, P, P]),
+    "pram_compress_workspace_bytes": (SZ, [I, I]),
+    "pram_compress_select": (I, [P, P, P, I, I, P, I, P, P, P, P, P, I, P, I, C.c_double, P, SZ, P, P, P, P]),
+    "pram_compress_sparsify": (I, [P, I, I, P, P, P, I, C.c_double, I, P, SZ, P, P, P]),
+    "pram_compress_rows": (I, [P, P, I, I, I, P, P, P, P, P, P, P, P, P, P, P, P]),
 }
 
 

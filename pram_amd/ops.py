@@ -2041,3 +2041,98 @@ def mapbuild_select_frames(store, pt_xyz: torch.Tensor, lm_off: torch.Tensor, lm
                                              float(min_cover_ratio), float(gain_floor), _p(workspace), workspace.numel(), _p(lm_vrf), _p(lm_vrf_n),
                                              _st()), "pram_mapbuild_select_frames")
     return lm_vrf[:n_lm], lm_vrf_n[:n_lm]
+
+
+# ---- map compression (csrc/compress.hip; pram_amd/localization/compress.py drives these) --------------------------------------
+COMPRESS_ROW_TILE, COMPRESS_KPT_TILE = 256, 256      # include/pram_hip.h
+
+
+def _host_ints(a, name: str):
+    """A host table as a ctypes int array (never empty behind its pointer) and its length."""
+    import ctypes
+    import numpy as np
+    a = np.ascontiguousarray(np.asarray(a).reshape(-1), dtype=np.int32)
+    return (ctypes.c_int * max(a.size, 1)).from_buffer_copy(a.tobytes() if a.size else b"\0\0\0\0"), a.size
+
+
+def compress_workspace(store, device) -> torch.Tensor:
+    need = int(_lib.load().pram_compress_workspace_bytes(int(store["n_rows"]), int(store["covisibility_frame"])))
+    return torch.empty(max(need, 8), device=device, dtype=torch.uint8)
+
+
+def compress_select(store, frame_off_host, covis_off_host, covis_frames_host, vrf_host, pt_xyz: torch.Tensor, xys: torch.Tensor,
+                    frame_cams: torch.Tensor, radius: float, workspace: Optional[torch.Tensor] = None):
+    """``store``: the device tables of a ReferenceStore (rows and point ids); the host copies of frame_off and of the covisibility
+    graph, and the reference frames in order, as int arrays; pt_xyz float64 [n_points, 3]; xys float64 [n_rows, 2]; frame_cams
+    float64 [F, MAPBUILD_CAM_COLS] -> (ret_order int32 [F]: place in the retained order or -1, list_cnt int32 [F], list_pt int32
+    [n_rows]: frame f's kept rows as point table indices at frame_off[f] ..).  Nothing is read back."""
+    import ctypes
+    L = _lib.load()
+    s = store
+    for t, nm in ((pt_xyz, "pt_xyz"), (xys, "xys"), (frame_cams, "frame_cams")):
+        _chk(t, nm, torch.float64)
+        assert t.is_contiguous(), nm
+    F, n_rows, n_points, cov = int(s["n_frames"]), int(s["n_rows"]), int(s["n_points"]), int(s["covisibility_frame"])
+    fo, n_fo = _host_ints(frame_off_host, "frame_off")
+    co, n_co = _host_ints(covis_off_host, "covis_off")
+    cf, n_cf = _host_ints(covis_frames_host, "covis_frames")
+    vh, n_vrf = _host_ints(vrf_host, "vrf")
+    if n_fo != F + 1 or n_co != F + 1 or n_cf < int(co[F]) or F < 1:
+        raise _lib.PramHipError(f"compress_select: frame_off and covis_off need {F + 1} entries (at least one frame), covis_frames {int(co[F]) if n_co == F + 1 else '?'}")
+    assert pt_xyz.numel() >= 3 * n_points and xys.numel() >= 2 * n_rows and frame_cams.numel() >= F * MAPBUILD_CAM_COLS
+    dev = pt_xyz.device
+    if workspace is None:
+        workspace = compress_workspace(s, dev)
+    _chk(workspace, "workspace", torch.uint8)
+    ret_order = torch.empty(F, device=dev, dtype=torch.int32)
+    list_cnt = torch.empty(F, device=dev, dtype=torch.int32)
+    list_pt = torch.empty(max(n_rows, 1), device=dev, dtype=torch.int32)
+    _lib.check(L.pram_compress_select(_p(s["point3D_ids"]), _p(s["frame_off"]), ctypes.addressof(fo), F, n_rows, _p(s["pt_ids"]), n_points, _p(pt_xyz),
+                                      _p(xys), _p(frame_cams), ctypes.addressof(co), ctypes.addressof(cf), cov, ctypes.addressof(vh), n_vrf,
+                                      float(radius), _p(workspace), workspace.numel(), _p(ret_order), _p(list_cnt), _p(list_pt), _st()),
+               "pram_compress_select")
+    return ret_order, list_cnt, list_pt
+
+
+def compress_sparsify(store, frame_cams: torch.Tensor, pt_xyz: torch.Tensor, pt_score: torch.Tensor, radius: float, nkpts: int,
+                      list_pt: torch.Tensor, list_cnt: torch.Tensor, workspace: Optional[torch.Tensor] = None) -> None:
+    """In place on (list_pt, list_cnt) of :func:`compress_select`: every frame listing more than ``nkpts`` points keeps the best
+    point (pt_score int32 [n_points], the earlier on a tie) of every cell of ``radius`` pixels, in the order the cells appear."""
+    L = _lib.load()
+    s = store
+    for t, nm, dt in ((frame_cams, "frame_cams", torch.float64), (pt_xyz, "pt_xyz", torch.float64), (pt_score, "pt_score", torch.int32),
+                      (list_pt, "list_pt", torch.int32), (list_cnt, "list_cnt", torch.int32)):
+        _chk(t, nm, dt)
+        assert t.is_contiguous(), nm
+    F, n_rows, n_points = int(s["n_frames"]), int(s["n_rows"]), int(s["n_points"])
+    assert pt_xyz.numel() >= 3 * n_points and pt_score.numel() >= n_points and frame_cams.numel() >= F * MAPBUILD_CAM_COLS
+    assert list_pt.numel() >= n_rows and list_cnt.numel() >= F
+    if workspace is None:
+        workspace = compress_workspace(s, pt_xyz.device)
+    _chk(workspace, "workspace", torch.uint8)
+    _lib.check(L.pram_compress_sparsify(_p(s["frame_off"]), F, n_rows, _p(frame_cams), _p(pt_xyz), _p(pt_score), n_points, float(radius), int(nkpts),
+                                        _p(workspace), workspace.numel(), _p(list_pt), _p(list_cnt), _st()), "pram_compress_sparsify")
+
+
+def compress_rows(row_frame: torch.Tensor, row_point: torch.Tensor, n_frames: int, frame_cams: torch.Tensor, pt_ids: torch.Tensor,
+                  pt_xyz: torch.Tensor, pt_desc: torch.Tensor, pt_sid: torch.Tensor, pt_err: torch.Tensor, n_points: int) -> dict:
+    """Row i of a compressed map: point row_point[i] (index into the point table) seen from frame row_frame[i] -> dict(keypoints
+    float64 [n, 3] (u, v, score), xyzs float64 [n, 3], descriptors float32 [n, 128], keypoint_segs int32 [n], point3D_ids int64 [n])."""
+    L = _lib.load()
+    for t, nm, dt in ((row_frame, "row_frame", torch.int32), (row_point, "row_point", torch.int32), (frame_cams, "frame_cams", torch.float64),
+                      (pt_ids, "pt_ids", _INT64), (pt_xyz, "pt_xyz", torch.float64), (pt_desc, "pt_desc", torch.float32),
+                      (pt_sid, "pt_sid", torch.int32), (pt_err, "pt_err", torch.float64)):
+        _chk(t, nm, dt)
+        assert t.is_contiguous(), nm
+    n = int(row_frame.numel())
+    assert row_point.numel() == n and frame_cams.numel() >= int(n_frames) * MAPBUILD_CAM_COLS and pt_ids.numel() >= n_points
+    assert pt_xyz.numel() >= 3 * n_points and pt_desc.numel() >= 128 * n_points and pt_sid.numel() >= n_points and pt_err.numel() >= n_points
+    dev = row_frame.device
+    m = max(n, 1)
+    out = {"keypoints": torch.empty(m, 3, device=dev, dtype=torch.float64), "xyzs": torch.empty(m, 3, device=dev, dtype=torch.float64),
+           "descriptors": torch.empty(m, 128, device=dev, dtype=torch.float32), "keypoint_segs": torch.empty(m, device=dev, dtype=torch.int32),
+           "point3D_ids": torch.empty(m, device=dev, dtype=_INT64)}
+    _lib.check(L.pram_compress_rows(_p(row_frame), _p(row_point), n, int(n_frames), int(n_points), _p(frame_cams), _p(pt_ids), _p(pt_xyz), _p(pt_desc),
+                                    _p(pt_sid), _p(pt_err), _p(out["keypoints"]), _p(out["xyzs"]), _p(out["descriptors"]), _p(out["keypoint_segs"]),
+                                    _p(out["point3D_ids"]), _st()), "pram_compress_rows")
+    return {k: v[:n] for k, v in out.items()}
