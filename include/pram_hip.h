@@ -25,6 +25,7 @@
  *   - AdaGML pruning handles token sets of at most 8192 tokens (pram_adagml_prune_f32);
  *   - Sinkhorn / dual-softmax matching handles at most 8191 rows (m_max) and 4351 columns (n_max) per pair, the dust-bin row
  *     and column excluded (pram_sinkhorn_match_f32, pram_dual_softmax_match_f32);
+ *   - k-means labelling takes at most PRAM_KMEANS_MAX_K = 4096 clusters and fewer than 2^31 points (the pram_kmeans entries);
  *   - LayerNorm rows are at most 1024 wide; the split-fp16 GEMMs need K % 32 == 0 (other shapes: the exact-fp32 entry);
  *   - the split-fp16 operands carry value * s in fp16 (s = 16 by default, pram_x3_set_act_scale): a finite |x| >= 65520 / s
  *     (4094.97) does not fit.  This one is NOT a silent limit
@@ -1005,6 +1006,57 @@ int pram_compress_sparsify(const int* frame_off, int n_frames, int n_rows, const
 int pram_compress_rows(const int* row_frame, const int* row_point, int n_out, int n_frames, int n_points, const double* frame_cams,
                        const long long* pt_ids, const double* pt_xyz, const float* pt_desc, const int* pt_sid, const double* pt_err,
                        double* out_kpts, double* out_xyz, float* out_desc, int* out_sid, long long* out_ids, void* stream);
+
+/* ---- K-means labelling of a map's points (csrc/kmeans.hip; pram_amd/localization/labelling.py drives these): the labels that
+ * RecMap.cluster(method='kmeans') (recmap.py:85-122) takes from sklearn's KMeans(n_clusters=k, random_state=0): k-means++
+ * seeding, Lloyd iterations, sklearn's stopping rules and its relocation of empty clusters.  x [n][3] float64: the points as the
+ * host centred them (sklearn subtracts the mean); centers [k][3] float64 in the same coordinates.  Every floating-point sum has
+ * one fixed order, so a result is the same bits on every run and equals the numpy restatement tests/kmeans_ref.py:
+ *   - distance ((x0 - c0)^2 + (x1 - c1)^2) + (x2 - c2)^2, products and sums written out; the lowest centre index wins a tie;
+ *   - a sum over points cuts them into blocks of PRAM_KMEANS_BLOCK consecutive indices: inside a block the terms are added to 0.0
+ *     in ascending index (cluster sums: per cluster), the block partials are added to 0.0 in ascending block index.  Results
+ *     depend on PRAM_KMEANS_BLOCK.  No floating-point atomics; counts are integers.
+ * Every entry refuses (PRAM_E_ARG) n < 1, k < 1, k > n, k > PRAM_KMEANS_MAX_K, a null or misaligned pointer (float64 buffers 8
+ * bytes, the others 4), a workspace that is too small and n >= 2^31 (n travels as long long so that this is a refusal and not a
+ * wrapped int).  Coordinates are finite.  No workgroup waits for another: every step is a launch of its own and
+ * every loop is bounded by an argument. */
+#define PRAM_KMEANS_BLOCK 1024         /* points per block of every reduction over points; the results depend on it */
+#define PRAM_KMEANS_MAX_K 4096         /* the per-block histogram and cursors of the cluster sums are LDS tables of this size */
+#define PRAM_KMEANS_MAX_TRIALS 10      /* candidates per k-means++ step: sklearn's 2 + int(ln k) is 10 at k = 4096 */
+#define PRAM_KMEANS_STATE_WORDS 8      /* done, n_iter, strict, relocations, changed, three spare */
+
+/* One workspace serves seeding and iterations.  0 for arguments the entries refuse. */
+size_t pram_kmeans_workspace_bytes(long long n, int k);
+
+/* sklearn's k-means++ (_kmeans_plusplus) with the host's random numbers: first: the first seed's index; rand [k - 1][n_trials]
+ * float64 (device): the uniform numbers of every step, n_trials in [1, PRAM_KMEANS_MAX_TRIALS].  closest[i] is the squared
+ * distance of point i to its nearest seed, pot its blocked sum.  A step's candidate t is the first i with
+ * run[b] + within[i] >= rand[t] * pot, clipped to n - 1, where within is the running sum of closest inside block b and run the
+ * running sum of the block totals; its potential is the blocked sum of min(closest[i], d2(x_i, x_cand)); the smallest potential
+ * wins, the lowest t on a tie.  Three launches per step (pick the winner and the next targets' blocks: one workgroup; update
+ * closest and walk the targets' blocks; the candidates' potentials per block), nothing is read back.  seeds [k] int32: the chosen
+ * points; centers [k][3]: their coordinates. */
+int pram_kmeans_init_pp(const double* x, long long n, int k, int first, const double* rand, int n_trials, void* workspace,
+                        size_t workspace_bytes, int* seeds, double* centers, void* stream);
+
+/* Lloyd iterations first_iter .. first_iter + n_iters - 1 on `centers` (in place), four launches each: assign every point (one
+ * thread per point, the centres through LDS); the cluster sums and counts of every block (the block's points ordered by label in
+ * LDS, stably, every run added in index order); the block partials added in block order; and one workgroup that relocates empty
+ * clusters (ascending cluster index; each takes the next of the points farthest from their own centre, in descending distance,
+ * lowest index on ties, which leaves its old cluster's sum and count), divides the sums by the counts (a cluster left without a
+ * point keeps its sum), adds the squared centre moves in ascending index and decides: the labels equal the previous iteration's
+ * (strict) -> done; else shift <= tol_abs -> done; else iteration max_iter - 1 -> done.  state [PRAM_KMEANS_STATE_WORDS] int32
+ * (device) carries this between calls: state[0] done, [1] iterations run, [2] strict, [3] relocations so far; first_iter == 0
+ * resets it.  Once done, the launches of later iterations return at once, so a caller enqueues iterations in groups and reads
+ * state[0] once per group.  finish != 0 (after the iterations, valid once done is set): without strict convergence one more
+ * assignment; labels [n] int32, dist [n] float64 (squared distance to the point's own centre; also the iterations' scratch) and
+ * inertia [2] float64: the blocked sum of dist, and the last iteration's shift.  Nothing waits for the stream. */
+int pram_kmeans_lloyd(const double* x, long long n, int k, double* centers, double tol_abs, int max_iter, int first_iter, int n_iters,
+                      int finish, void* workspace, size_t workspace_bytes, int* labels, double* dist, int* state, double* inertia,
+                      void* stream);
+
+/* One assignment step: labels [n] int32 and dist [n] float64 of x against centers [k][3].  Needs no workspace. */
+int pram_kmeans_assign(const double* x, long long n, const double* centers, int k, int* labels, double* dist, void* stream);
 
 #ifdef __cplusplus
 }

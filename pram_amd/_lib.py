@@ -131,6 +131,10 @@ _SIGS = {
     "pram_compress_select": (I, [P, P, P, I, I, P, I, P, P, P, P, P, I, P, I, C.c_double, P, SZ, P, P, P, P]),
     "pram_compress_sparsify": (I, [P, I, I, P, P, P, I, C.c_double, I, P, SZ, P, P, P]),
     "pram_compress_rows": (I, [P, P, I, I, I, P, P, P, P, P, P, P, P, P, P, P, P]),
+    "pram_kmeans_workspace_bytes": (SZ, [LL, I]),
+    "pram_kmeans_init_pp": (I, [P, LL, I, I, P, I, P, SZ, P, P, P]),
+    "pram_kmeans_lloyd": (I, [P, LL, I, P, C.c_double, I, I, I, I, P, SZ, P, P, P, P, P]),
+    "pram_kmeans_assign": (I, [P, LL, P, I, P, P, P]),
 }
 
 

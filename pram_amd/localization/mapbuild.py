@@ -20,8 +20,9 @@ Where this differs from the reference, on purpose:
     build_store_inputs reports the choices beside the descriptors, so that a caller can tell such a point.
   * cameras: fx, fy, cx, cy as get_intrinsics_from_camera extracts them, no distortion (the reference's projection has none).
   * ``covisible_frame_ids`` and ``original_points3d`` of the reference's file are not produced: the store derives its own graph.
-k-means / Birch labelling, Open3D outlier removal and everything cv2 draws stay outside this repository; map compression, the
-next step of the reference's pipeline, is localization/compress.py."""
+The k-means labelling that produces ``landmarks`` is localization/labelling.py; Birch labelling, Open3D outlier removal and
+everything cv2 draws stay outside this repository; map compression, the next step of the reference's pipeline, is
+localization/compress.py."""
 from __future__ import annotations
 
 from typing import Dict, Optional, Sequence

@@ -2136,3 +2136,76 @@ def compress_rows(row_frame: torch.Tensor, row_point: torch.Tensor, n_frames: in
                                     _p(pt_sid), _p(pt_err), _p(out["keypoints"]), _p(out["xyzs"]), _p(out["descriptors"]), _p(out["keypoint_segs"]),
                                     _p(out["point3D_ids"]), _st()), "pram_compress_rows")
     return {k: v[:n] for k, v in out.items()}
+
+
+# ---- k-means labelling (csrc/kmeans.hip; pram_amd/localization/labelling.py drives these) --------------------------------------
+KMEANS_BLOCK, KMEANS_MAX_K, KMEANS_MAX_TRIALS, KMEANS_STATE_WORDS = 1024, 4096, 10, 8      # include/pram_hip.h
+KMEANS_DONE, KMEANS_ITER, KMEANS_STRICT, KMEANS_RELOC = 0, 1, 2, 3      # words of the state
+
+
+def _kmeans_x(x: torch.Tensor, name: str = "x") -> int:
+    _chk(x, name, torch.float64)
+    if x.dim() != 2 or x.shape[1] != 3 or not x.is_contiguous():
+        raise _lib.PramHipError(f"{name}: expected a contiguous float64 [n, 3] tensor, got {tuple(x.shape)}")
+    return int(x.shape[0])
+
+
+def kmeans_workspace(n: int, k: int, device) -> torch.Tensor:
+    need = int(_lib.load().pram_kmeans_workspace_bytes(int(n), int(k)))
+    if need == 0:
+        raise _lib.PramHipError(f"kmeans: needs 1 <= n < 2^31 and 1 <= k <= min(n, {KMEANS_MAX_K}), got n = {n}, k = {k}")
+    return torch.empty(need, device=device, dtype=torch.uint8)
+
+
+def kmeans_init_pp(x: torch.Tensor, k: int, first: int, rand: torch.Tensor, workspace: Optional[torch.Tensor] = None):
+    """sklearn's k-means++ on the centred points x float64 [n, 3] with the host's random numbers: ``first`` the first seed, rand
+    float64 [k - 1, T] the uniform numbers of every step -> (seeds int32 [k]: the chosen points, centers float64 [k, 3])."""
+    L = _lib.load()
+    n, k = _kmeans_x(x), int(k)
+    _chk(rand, "rand", torch.float64)
+    T = int(rand.shape[1]) if rand.dim() == 2 else 0
+    if rand.dim() != 2 or not rand.is_contiguous() or rand.shape[0] < k - 1 or T < 1:
+        raise _lib.PramHipError(f"rand: expected a contiguous float64 [k - 1, T] tensor with T >= 1, got {tuple(rand.shape)}")
+    if workspace is None:
+        workspace = kmeans_workspace(n, k, x.device)
+    _chk(workspace, "workspace", torch.uint8)
+    seeds = torch.empty(max(k, 1), device=x.device, dtype=torch.int32)
+    centers = torch.empty(max(k, 1), 3, device=x.device, dtype=torch.float64)
+    _lib.check(L.pram_kmeans_init_pp(_p(x), n, k, int(first), _p(rand), T, _p(workspace), workspace.numel(), _p(seeds), _p(centers), _st()),
+               "pram_kmeans_init_pp")
+    return seeds, centers
+
+
+def kmeans_buffers(n: int, device) -> dict:
+    """The outputs and the state of :func:`kmeans_lloyd`, which carries them from one group of iterations to the next."""
+    return {"labels": torch.empty(n, device=device, dtype=torch.int32), "dist": torch.empty(n, device=device, dtype=torch.float64),
+            "state": torch.zeros(KMEANS_STATE_WORDS, device=device, dtype=torch.int32), "inertia": torch.zeros(2, device=device, dtype=torch.float64)}
+
+
+def kmeans_lloyd(x: torch.Tensor, centers: torch.Tensor, tol_abs: float, max_iter: int, first_iter: int, n_iters: int, finish: bool,
+                 buffers: dict, workspace: torch.Tensor) -> None:
+    """Enqueues Lloyd iterations first_iter .. first_iter + n_iters - 1 on ``centers`` float64 [k, 3] (in place) and, with
+    ``finish``, the final labels, distances and inertia into ``buffers`` (:func:`kmeans_buffers`).  buffers["state"] says when the
+    iterations are done (word KMEANS_DONE); later iterations then return at once.  Nothing is read back here."""
+    L = _lib.load()
+    n = _kmeans_x(x)
+    k = _kmeans_x(centers, "centers")
+    _chk(workspace, "workspace", torch.uint8)
+    for nm, dt, cnt in (("labels", torch.int32, n), ("dist", torch.float64, n), ("state", torch.int32, KMEANS_STATE_WORDS), ("inertia", torch.float64, 2)):
+        _chk(buffers[nm], nm, dt)
+        assert buffers[nm].is_contiguous() and buffers[nm].numel() >= cnt, nm
+    _lib.check(L.pram_kmeans_lloyd(_p(x), n, k, _p(centers), float(tol_abs), int(max_iter), int(first_iter), int(n_iters), int(bool(finish)),
+                                   _p(workspace), workspace.numel(), _p(buffers["labels"]), _p(buffers["dist"]), _p(buffers["state"]),
+                                   _p(buffers["inertia"]), _st()), "pram_kmeans_lloyd")
+
+
+def kmeans_assign(x: torch.Tensor, centers: torch.Tensor):
+    """One assignment step: x float64 [n, 3], centers float64 [k, 3] (k <= n) -> (labels int32 [n], squared distance float64 [n]);
+    the lowest centre index wins a tie."""
+    L = _lib.load()
+    n = _kmeans_x(x)
+    k = _kmeans_x(centers, "centers")
+    labels = torch.empty(max(n, 1), device=x.device, dtype=torch.int32)
+    dist = torch.empty(max(n, 1), device=x.device, dtype=torch.float64)
+    _lib.check(L.pram_kmeans_assign(_p(x), n, _p(centers), k, _p(labels), _p(dist), _st()), "pram_kmeans_assign")
+    return labels[:n], dist[:n]
