@@ -920,6 +920,25 @@ int pram_track_commit(const float* q_kpts, const float* q_scores, const float* q
                       float* st_desc, int* st_counts, double* st_xyz, long long* st_point3d_ids, int* st_segs, int* st_ref_frame,
                       float* st_frame_norm, int n_slots, int n_max, int* winner, void* stream);
 
+/* ---- The query pre-filter (csrc/prefilter.hip; pram_amd/localization/localizer.py drives it): Frame.add_segmentations' optional
+ * filtering of the query (frame.py:102-116) for a padded batch.  keypoints [batch][n][2], scores [batch][n], descriptors
+ * [batch][n][desc_dim], logits [batch][n][n_class], and pram_seg_epilogue_f32's outputs at the filtering threshold: seg_ids,
+ * non_bg_mask [batch][n], n_non_bg [batch]; counts [batch] real rows per query (clamped to [0, n]); enable = the threshold is
+ * > 0.  Query b FIRES when enable != 0 and 5 * n_non_bg[b] >= 2 * counts[b] — frame.py:106's `>= 0.4 * n` in float64, which
+ * this integer form equals for every n an int holds (csrc/prefilter.hip) — and then keeps the rows i < counts[b] with
+ * non_bg_mask != 0, in their order; otherwise it keeps all counts[b] rows.  counts[b] == 0 fires (0 >= 0.0).  Outputs, out of
+ * place, same shapes: the five row arrays compacted (kept rows bit for bit, NaN payloads and negative zeros included; rows j >=
+ * o_counts[b] zero, o_seg_ids -2 there), o_counts [batch], kept [batch][n] = the input row of output row j (-1 for j >=
+ * o_counts[b]), filtered [batch] = 1 where the query fired.  Every element of every output is written whatever the inputs hold
+ * beyond counts[b].  One workgroup per query plans (ordered compaction by ballot and prefix), one wave per output row moves
+ * (descriptors as 16-byte vectors: desc_dim % 4 == 0 and 16-byte aligned descriptor buffers; a logits row as 32-bit words, since
+ * an odd n_class leaves it 4-byte aligned only).  No atomics, no host synchronisation.  batch == 0 or n == 0: PRAM_OK, nothing
+ * is launched and nothing written (with n == 0 the caller owns o_counts = 0 and filtered = enable != 0). */
+int pram_query_prefilter(const float* keypoints, const float* scores, const float* descriptors, const float* logits,
+                         const int* seg_ids, const int* non_bg_mask, const int* n_non_bg, const int* counts, int enable, int batch,
+                         int n, int n_class, int desc_dim, float* o_keypoints, float* o_scores, float* o_descriptors,
+                         float* o_logits, int* o_seg_ids, int* o_counts, int* kept, int* filtered, void* stream);
+
 /* ---- Map building (csrc/mapbuild.hip; pram_amd/localization/mapbuild.py drives these): the two inputs of a ReferenceStore that
  * the reference computes offline on the CPU (recognition/recmap.py).  Both take tables of the store as they lie on the device.
  * An offset table also comes as a HOST copy: the workspace size and the table's shape are checked from it without touching the

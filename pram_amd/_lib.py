@@ -123,6 +123,7 @@ _SIGS = {
     "pram_track_correspond": (I, [P, I, P, P, I, P, P, P, P, I, I, I, I, I, P, P, P, P, P, P, P, P]),
     "pram_track_filter": (I, [P, P, P, P, P, P, P, P, I, I, P, P, P, P, P, P, P, P]),
     "pram_track_commit": (I, [P, P, P, P, P, P, P, P, I, I, F, F, F, P, P, P, P, P, P, I, P, P, P, P, P, P, P, P, P, I, I, P, P]),
+    "pram_query_prefilter": (I, [P, P, P, P, P, P, P, P, I, I, I, I, I, P, P, P, P, P, P, P, P, P]),
     "pram_mapbuild_desc_workspace_bytes": (SZ, [P, I]),
     "pram_mapbuild_assign_descriptors": (I, [P, P, I, I, P, P, P, P, I, P, SZ, P, P, P]),
     "pram_mapbuild_vrf_workspace_bytes": (SZ, [I, I, I]),

@@ -1966,6 +1966,37 @@ def track_commit(st: dict, q_kpts: torch.Tensor, q_scores: torch.Tensor, q_desc:
                                    _p(st["ref_frame"]), _p(st["frame_norm"]), S, n_max, _p(winner), _st()), "pram_track_commit")
 
 
+# ---- the query pre-filter (csrc/prefilter.hip; pram_amd/localization/localizer.py drives it) -------------------------------------
+def query_prefilter(keypoints: torch.Tensor, scores: torch.Tensor, descriptors: torch.Tensor, logits: torch.Tensor, seg_ids: torch.Tensor,
+                    non_bg_mask: torch.Tensor, n_non_bg: torch.Tensor, counts: torch.Tensor, enable: bool) -> dict:
+    """Frame.add_segmentations' filtering of the query for a padded batch (pram_query_prefilter).  keypoints [B, N, 2], scores
+    [B, N], descriptors [B, N, D], logits [B, N, C] float32; seg_ids, non_bg_mask [B, N], n_non_bg [B] int32 = seg_epilogue's
+    outputs at the filtering threshold; counts [B] int32; enable = the threshold is > 0.  -> dict(keypoints, scores, descriptors,
+    logits, seg_ids: new buffers of the same shapes, compacted; counts [B]; kept int32 [B, N]; filtered int32 [B]).  No read-back."""
+    L = _lib.load()
+    for t, nm, dt in ((keypoints, "keypoints", torch.float32), (scores, "scores", torch.float32), (descriptors, "descriptors", torch.float32),
+                      (logits, "logits", torch.float32), (seg_ids, "seg_ids", torch.int32), (non_bg_mask, "non_bg_mask", torch.int32),
+                      (n_non_bg, "n_non_bg", torch.int32), (counts, "counts", torch.int32)):
+        _chk(t, nm, dt)
+        assert t.is_contiguous(), nm
+    assert descriptors.dim() == 3 and logits.dim() == 3
+    B, N, D = descriptors.shape
+    Cc = logits.shape[2]
+    assert tuple(keypoints.shape) == (B, N, 2) and tuple(scores.shape) == (B, N) and tuple(logits.shape[:2]) == (B, N)
+    assert tuple(seg_ids.shape) == (B, N) and tuple(non_bg_mask.shape) == (B, N) and n_non_bg.numel() == B and counts.numel() == B
+    dev = descriptors.device
+    out = {"keypoints": torch.empty_like(keypoints), "scores": torch.empty_like(scores), "descriptors": torch.empty_like(descriptors),
+           "logits": torch.empty_like(logits), "seg_ids": torch.empty_like(seg_ids), "kept": torch.empty((B, N), device=dev, dtype=torch.int32)}
+    if B == 0 or N == 0:      # the empty tensors have no storage to hand to the entry; an empty query keeps nothing, and fires
+        out["counts"], out["filtered"] = _filled((B,), dev, torch.int32), _filled((B,), dev, torch.int32, 1 if enable else 0)      # (0 >= 0.4 * 0)
+        return out
+    out["counts"], out["filtered"] = torch.empty(B, device=dev, dtype=torch.int32), torch.empty(B, device=dev, dtype=torch.int32)
+    _lib.check(L.pram_query_prefilter(_p(keypoints), _p(scores), _p(descriptors), _p(logits), _p(seg_ids), _p(non_bg_mask), _p(n_non_bg), _p(counts),
+                                      1 if enable else 0, B, N, Cc, D, _p(out["keypoints"]), _p(out["scores"]), _p(out["descriptors"]), _p(out["logits"]),
+                                      _p(out["seg_ids"]), _p(out["counts"]), _p(out["kept"]), _p(out["filtered"]), _st()), "pram_query_prefilter")
+    return out
+
+
 # ---- map building (csrc/mapbuild.hip; pram_amd/localization/mapbuild.py drives these) ------------------------------------------
 MAPBUILD_SHORT_TRACK, MAPBUILD_ROW_LDS, MAPBUILD_MAX_VRF, MAPBUILD_CAM_COLS = 32, 512, 64, 13      # include/pram_hip.h
 
