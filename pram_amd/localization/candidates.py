@@ -20,7 +20,91 @@ from pram_amd.nets.utils import keypoint_norm_constants
 _FRAME_KEYS = ("keypoints", "descriptors", "xyzs", "point3D_ids", "keypoint_segs", "width", "height")
 
 
-class ReferenceStore:
+class StoreBase:
+    """What ReferenceStore and MultiMapStore share: the host views over the concatenated arrays, the per-point values (checked on
+    first use) and the resident device tables.  A subclass fills the arrays named in _TABLES / _PADDED (and in the hooks below)
+    in its constructor, ends it with _ready(device), and says in _point_values where pt_xyz / pt_desc / pt_sid come from."""
+
+    _TABLES = ("descriptors", "keypoints", "scores", "xyzs", "point3D_ids", "keypoint_segs", "frame_norm")
+    _PADDED = ("sel_rows", "hist_label", "hist_cnt", "lm_frame", "lm_sel_off", "lm_sel_len", "frame_off", "hist_off",
+               "pt_ids", "pt_off", "pt_frames", "is_vrf", "covis_off", "covis_frames", "covis_count")
+    _POINT_TABLES = ("pt_xyz", "pt_desc", "pt_sid")
+    _EXTRA_PADDED: tuple = ()      # the hooks: further arrays uploaded like _PADDED, further attributes handed over as they are
+    _EXTRA_COUNTS: tuple = ()
+    _pt_values: Optional[dict] = None
+
+    def _ready(self, device) -> None:
+        self._dev: Dict[str, dict] = {}
+        self._dev_points: Dict[str, dict] = {}
+        if device is not None:
+            self.tables(device)
+
+    pt_xyz = property(lambda self: self._point_values()["pt_xyz"])
+    pt_desc = property(lambda self: self._point_values()["pt_desc"])
+    pt_sid = property(lambda self: self._point_values()["pt_sid"])
+
+    def covisible(self, frame: int) -> np.ndarray:
+        """covisible_graph[frame]: the store indices of the frames covisible with store frame `frame`, best first (empty for a
+        frame that is no landmark's reference frame)."""
+        return self.covis_frames[self.covis_off[frame]:self.covis_off[frame + 1]].astype(np.int64)
+
+    # ---- host views (what the two RefFrame accessors select; used by the tests and by anyone who wants to look)
+    @property
+    def n_frames(self) -> int:
+        return len(self.frame_ids)
+
+    @property
+    def n_rows(self) -> int:
+        return int(self.frame_off[-1])
+
+    @property
+    def max_frame_rows(self) -> int:
+        return int(np.diff(self.frame_off).max()) if self.n_frames else 0
+
+    def rows(self, frame: int) -> np.ndarray:
+        """RefFrame.get_keypoints: the frame's rows (indices into the concatenated arrays), original order."""
+        return np.arange(self.frame_off[frame], self.frame_off[frame + 1], dtype=np.int64)
+
+    def rows_by_sid(self, frame: int, sid: int) -> np.ndarray:
+        """RefFrame.get_keypoints_by_sid(sid): the frame's rows with keypoint_segs == sid (an IN-MAP landmark id), original order."""
+        off, n = self._slices[frame].get(int(sid), (0, 0))
+        return self.sel_rows[off:off + n].astype(np.int64)
+
+    @staticmethod
+    def _upload(a: np.ndarray, device, pad: bool) -> torch.Tensor:
+        """The pad-and-upload rule: never an empty allocation behind a pointer.  pad: one zero row more; otherwise one zero row
+        only where the array has none."""
+        zero = np.zeros((1,) + a.shape[1:], dtype=a.dtype)
+        a = np.concatenate([a, zero]) if pad else (a if a.size else zero)
+        return torch.from_numpy(np.ascontiguousarray(a)).to(device)
+
+    def tables(self, device) -> dict:
+        """The device-side tables (uploaded on first use, then resident)."""
+        device = torch.device(device)
+        if device.type != "cuda":
+            from pram_amd._lib import PramHipError
+            raise PramHipError("ReferenceStore.tables: expected a CUDA device (pram_amd has no CPU path)")
+        key = str(device)
+        if key not in self._dev:
+            t = {name: self._upload(getattr(self, name), device, False) for name in self._TABLES}
+            t.update({name: self._upload(getattr(self, name), device, True) for name in self._PADDED + self._EXTRA_PADDED})
+            t.update(n_rows=self.n_rows, n_frames=self.n_frames, n_landmarks=len(self.lm_frame), start_sid=self.start_sid,
+                     n_points=len(self.pt_ids), n_pt_entries=len(self.pt_frames), n_covis=len(self.covis_frames),
+                     covisibility_frame=self.covisibility_frame, **{name: getattr(self, name) for name in self._EXTRA_COUNTS})
+            self._dev[key] = t
+        return self._dev[key]
+
+    def point_tables(self, device) -> dict:
+        """tables() plus the per-point values pt_xyz, pt_desc, pt_sid (uploaded on first use, then resident, padded like the
+        others): what the refinement by projection reads."""
+        t = self.tables(device)
+        key = str(torch.device(device))
+        if key not in self._dev_points:
+            self._dev_points[key] = {**t, **{name: self._upload(getattr(self, name), t["pt_ids"].device, True) for name in self._POINT_TABLES}}
+        return self._dev_points[key]
+
+
+class ReferenceStore(StoreBase):
     """The reference frames of ONE map, built once from plain numpy and uploaded once.
 
     frames: a sequence of dicts with ``keypoints`` [n, 3] (x, y, score), ``descriptors`` [n, 128], ``xyzs`` [n, 3] float64,
@@ -128,13 +212,9 @@ class ReferenceStore:
         # a store whose point table names points without rows (a vote-only table) stays valid as long as nobody asks for the
         # per-point values: without the three arguments they are derived, and checked, on first use
         self._pt_given = (point3D_xyzs, point3D_descriptors, point3D_sids)
-        self._pt_values: Optional[dict] = None
         if any(g is not None for g in self._pt_given):
             self._point_values()
-        self._dev: Dict[str, dict] = {}
-        self._dev_points: Dict[str, dict] = {}
-        if device is not None:
-            self.tables(device)
+        self._ready(device)
 
     def _build_point_table(self, point3D_frame_ids, index_of) -> None:
         F = len(self.frame_ids)
@@ -170,10 +250,6 @@ class ReferenceStore:
         self.pt_ids = np.ascontiguousarray(self.pt_ids, dtype=np.int64)
         self.pt_off = np.zeros(len(self.pt_ids) + 1, dtype=np.int32)
         self.pt_off[1:] = np.cumsum(lens)
-
-    pt_xyz = property(lambda self: self._point_values()["pt_xyz"])
-    pt_desc = property(lambda self: self._point_values()["pt_desc"])
-    pt_sid = property(lambda self: self._point_values()["pt_sid"])
 
     def _point_values(self) -> dict:
         if self._pt_values is not None:
@@ -229,65 +305,6 @@ class ReferenceStore:
         self.covis_off[1:] = np.cumsum(np.bincount(f, minlength=F))
         self.covis_frames, self.covis_count = g.astype(np.int32), cnt.astype(np.int32)
 
-    def covisible(self, frame: int) -> np.ndarray:
-        """covisible_graph[frame]: the store indices of the frames covisible with store frame `frame`, best first (empty for a
-        frame that is no landmark's reference frame)."""
-        return self.covis_frames[self.covis_off[frame]:self.covis_off[frame + 1]].astype(np.int64)
-
-    # ---- host views (what the two RefFrame accessors select; used by the tests and by anyone who wants to look)
-    @property
-    def n_frames(self) -> int:
-        return len(self.frame_ids)
-
-    @property
-    def n_rows(self) -> int:
-        return int(self.frame_off[-1])
-
-    @property
-    def max_frame_rows(self) -> int:
-        return int(np.diff(self.frame_off).max()) if self.n_frames else 0
-
-    def rows(self, frame: int) -> np.ndarray:
-        """RefFrame.get_keypoints: the frame's rows (indices into the concatenated arrays), original order."""
-        return np.arange(self.frame_off[frame], self.frame_off[frame + 1], dtype=np.int64)
-
-    def rows_by_sid(self, frame: int, sid: int) -> np.ndarray:
-        """RefFrame.get_keypoints_by_sid(sid): the frame's rows with keypoint_segs == sid, original order."""
-        off, n = self._slices[frame].get(int(sid), (0, 0))
-        return self.sel_rows[off:off + n].astype(np.int64)
-
-    def tables(self, device) -> dict:
-        """The device-side tables (uploaded on first use, then resident)."""
-        device = torch.device(device)
-        if device.type != "cuda":
-            from pram_amd._lib import PramHipError
-            raise PramHipError("ReferenceStore.tables: expected a CUDA device (pram_amd has no CPU path)")
-        key = str(device)
-        if key not in self._dev:
-            up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(device)
-            pad = lambda a: np.concatenate([a, np.zeros(1, dtype=a.dtype)])      # never an empty allocation behind a pointer
-            t = {name: up(getattr(self, name)) if getattr(self, name).size else up(np.zeros((1,) + getattr(self, name).shape[1:], dtype=getattr(self, name).dtype))
-                 for name in ("descriptors", "keypoints", "scores", "xyzs", "point3D_ids", "keypoint_segs", "frame_norm")}
-            for name in ("sel_rows", "hist_label", "hist_cnt", "lm_frame", "lm_sel_off", "lm_sel_len", "frame_off", "hist_off",
-                         "pt_ids", "pt_off", "pt_frames", "is_vrf", "covis_off", "covis_frames", "covis_count"):
-                t[name] = up(pad(getattr(self, name)))
-            t.update(n_rows=self.n_rows, n_frames=self.n_frames, n_landmarks=len(self.lm_frame), start_sid=self.start_sid,
-                     n_points=len(self.pt_ids), n_pt_entries=len(self.pt_frames), n_covis=len(self.covis_frames),
-                     covisibility_frame=self.covisibility_frame)
-            self._dev[key] = t
-        return self._dev[key]
-
-    def point_tables(self, device) -> dict:
-        """tables() plus the per-point values pt_xyz, pt_desc, pt_sid (uploaded on first use, then resident, padded like the
-        others): what the refinement by projection reads."""
-        t = self.tables(device)
-        key = str(torch.device(device))
-        if key not in self._dev_points:
-            pad = lambda a: np.concatenate([a, np.zeros((1,) + a.shape[1:], dtype=a.dtype)])
-            self._dev_points[key] = {**t, **{name: torch.from_numpy(np.ascontiguousarray(pad(getattr(self, name)))).to(t["pt_ids"].device)
-                                             for name in ("pt_xyz", "pt_desc", "pt_sid")}}
-        return self._dev_points[key]
-
 
 def _query_norm(features: dict):
     if "image_size" in features:
@@ -325,7 +342,7 @@ def vote_candidates(features: dict, recognition, seg_k: int) -> dict:
 
 
 @torch.no_grad()
-def plan_candidates(features: dict, recognition, store: ReferenceStore, *, seg_k: int, min_kpts: int, semantic_matching: bool = True,
+def plan_candidates(features: dict, recognition, store: StoreBase, *, seg_k: int, min_kpts: int, semantic_matching: bool = True,
                     overlap_ratio: float = 0.5) -> dict:
     """Vote + pram_cand_plan.  -> dict(plan int32 [10, B * seg_k] on the device (ops.CAND_PLAN_FIELDS), vote)."""
     counts = features["counts"]
@@ -340,8 +357,30 @@ def _round_up(x: int, m: int) -> int:
     return (x + m - 1) // m * m
 
 
+def padded_size(n0: int, n1: int) -> int:
+    """The padded size T of a grouped matcher call whose longest sides have n0 and n1 rows: rounded up to 64, at least 64."""
+    return max(64, _round_up(max(n0, n1), 64))
+
+
+def grouped_inputs(data: dict, plan: torch.Tensor) -> dict:
+    """pram_cand_gather's filled dict -> the matcher's data dict, in place: the normalised keypoints under the names the matcher
+    reads and the lens0 / lens1 columns of the plan table."""
+    f = ops.CAND_PLAN_FIELDS
+    data["keypoints0"], data["keypoints1"] = data["norm_keypoints0"], data["norm_keypoints1"]
+    data["lens0"], data["lens1"] = plan[f.index("lens0")], plan[f.index("lens1")]
+    return data
+
+
 @torch.no_grad()
-def gather_candidates(features: dict, planned: dict, store: ReferenceStore) -> dict:
+def match_grouped(data: dict, plan: torch.Tensor, matcher) -> dict:
+    """ONE grouped produce_matches call for all pairs of a plan table (the candidates', the refinement's, the tracker's) on
+    pram_cand_gather's filled dict.  matcher: the nn.Module or its localization.matchers wrapper.  -> the matcher's outputs."""
+    net = getattr(matcher, "net", matcher)
+    return net.produce_matches(grouped_inputs(data, plan))      # its own precision / range-guard scopes (nets/_blocks.with_model_precision)
+
+
+@torch.no_grad()
+def gather_candidates(features: dict, planned: dict, store: StoreBase) -> dict:
     """The ONE host synchronisation of the call: the plan table (40 bytes per pair) is read back to fix the padded size of the
     grouped call — T = max(lens0, lens1) over the pairs, rounded up to 64 — then pram_cand_gather fills the matcher's inputs.
     -> the matcher's data dict plus 'plan_host' (numpy [10, P]) and 't0' (largest query side)."""
@@ -349,18 +388,15 @@ def gather_candidates(features: dict, planned: dict, store: ReferenceStore) -> d
     host = plan.cpu().numpy()
     f = ops.CAND_PLAN_FIELDS
     t0, t1 = int(host[f.index("lens0")].max(initial=0)), int(host[f.index("lens1")].max(initial=0))
-    T = max(64, _round_up(max(t0, t1), 64))
-    dev = plan.device
-    data = ops.cand_gather(plan, planned["vote"]["tokens"], store.tables(dev), features["descriptors"], features["keypoints"], features["scores"],
-                           _query_norm(features), T)
-    data["keypoints0"], data["keypoints1"] = data["norm_keypoints0"], data["norm_keypoints1"]
-    data["lens0"], data["lens1"] = plan[f.index("lens0")], plan[f.index("lens1")]
+    data = ops.cand_gather(plan, planned["vote"]["tokens"], store.tables(plan.device), features["descriptors"], features["keypoints"], features["scores"],
+                           _query_norm(features), padded_size(t0, t1))
+    grouped_inputs(data, plan)
     data["plan_host"], data["t0"] = host, t0
     return data
 
 
 @torch.no_grad()
-def _match_pairs(features: dict, recognition, store: ReferenceStore, matcher, *, seg_k: int, min_kpts: int, semantic_matching: bool,
+def _match_pairs(features: dict, recognition, store: StoreBase, matcher, *, seg_k: int, min_kpts: int, semantic_matching: bool,
                  overlap_ratio: float):
     """The stages of match_candidates up to the compacted correspondences (ONE host synchronisation, the plan read-back).
     -> (cor: pram_cand_correspond's padded outputs [P, t0, ...] and count [P], host: the plan table as numpy [10, P],
@@ -371,14 +407,13 @@ def _match_pairs(features: dict, recognition, store: ReferenceStore, matcher, *,
 
 
 @torch.no_grad()
-def _match_planned(features: dict, planned: dict, store: ReferenceStore, matcher):
+def _match_planned(features: dict, planned: dict, store: StoreBase, matcher):
     """_match_pairs from a plan table on: gather, ONE grouped matcher call, correspondences.  The refinement hands its own plan
     over (localization/refine.py); planned = dict(plan, vote = dict(tokens))."""
     data = gather_candidates(features, planned, store)
     host, t0 = data.pop("plan_host"), data.pop("t0")
-    net = getattr(matcher, "net", matcher)
-    m = net.produce_matches(data)      # its own precision / range-guard scopes (nets/_blocks.with_model_precision)
     plan = planned["plan"]
+    m = match_grouped(data, plan, matcher)
     # a batch without a single query keypoint (t0 = 0): an empty slice has no storage to hand over, so one column is passed — no
     # pair reads it (every lens0 is 0) and the outputs keep their cap of t0 rows
     cor = ops.cand_correspond(m["matches0"][:, :max(t0, 1)], plan, planned["vote"]["tokens"], store.tables(plan.device),
@@ -386,7 +421,7 @@ def _match_planned(features: dict, planned: dict, store: ReferenceStore, matcher
     return cor, host, m
 
 
-def _candidate_lists(cor: dict, host, m: dict, store: ReferenceStore, B: int, seg_k: int) -> List[List[dict]]:
+def _candidate_lists(cor: dict, host, m: dict, store: StoreBase, B: int, seg_k: int) -> List[List[dict]]:
     f = ops.CAND_PLAN_FIELDS
     col = lambda name: host[f.index(name)]
     out: List[List[dict]] = []
@@ -405,7 +440,7 @@ def _candidate_lists(cor: dict, host, m: dict, store: ReferenceStore, B: int, se
 
 
 @torch.no_grad()
-def match_candidates(features: dict, recognition, store: ReferenceStore, matcher, *, seg_k: int, min_kpts: int,
+def match_candidates(features: dict, recognition, store: StoreBase, matcher, *, seg_k: int, min_kpts: int,
                      semantic_matching: bool = True, overlap_ratio: float = 0.5) -> List[List[dict]]:
     """features: the batched extractor output (``keypoints`` [B, N, 2], ``scores`` [B, N], ``descriptors`` [B, N, 128], ``counts``
     int32 [B], all on the GPU, plus ``image_size`` = (width, height) of the query camera or the ``image`` batch); recognition: see

@@ -24,10 +24,8 @@ import torch
 from pram_amd import ops
 from pram_amd.localization import pose as _pose
 from pram_amd.localization import refine as _refine
-from pram_amd.localization.tracker import Tracker
+from pram_amd.localization.tracker import TRACKER_KEYS, Tracker, split_options  # noqa: F401  (TRACKER_KEYS: the names loc_kw may carry)
 
-TRACKER_KEYS = ("seg_k", "min_kpts", "threshold", "min_inliers", "do_refinement", "refinement_method", "refine_below", "projection_min_inliers",
-                "covisibility_frame", "trials", "semantic_matching", "overlap_ratio", "min_inlier_ratio", "refine_iters", "seed")
 _EPILOGUE_KEYS = ("landmark", "non_bg", "n_non_bg")
 
 
@@ -87,9 +85,7 @@ class Localizer:
 
     def __init__(self, pipeline, store, *, pre_filtering_th: float, tracking: bool = False, n_streams: Optional[int] = None,
                  n_max: Optional[int] = None, **loc_kw):
-        unknown = sorted(set(loc_kw) - set(TRACKER_KEYS))
-        if unknown:
-            raise TypeError(f"Localizer: unknown arguments {unknown} (expected Tracker's: {', '.join(TRACKER_KEYS)})")
+        self._groups = split_options(loc_kw, "Localizer")
         self.pipeline, self.store, self.matcher = pipeline, store, pipeline.matcher
         self.pre_filtering_th, self.tracking = float(pre_filtering_th), bool(tracking)
         self.n_streams, self.n_max = n_streams, n_max
@@ -130,19 +126,18 @@ class Localizer:
         copied.record(torch.cuda.current_stream(dev))
         # cameras already on the device carry no image size for the projection refinement: the batch has one (QueryPipeline's rule)
         sizes = None
-        if isinstance(cameras, tuple) and len(cameras) == 3 and torch.is_tensor(cameras[0]):
+        if _pose.camera_form(cameras) == "resident":
             w, h = feats["image_size"] if "image_size" in feats else (feats["image"].shape[-1], feats["image"].shape[-2])
             sizes = np.tile(np.array([[int(w), int(h)]], dtype=np.int32), (B, 1))
         with ops.guard_scope(self.pipeline.guard):
             if self.tracking:
                 res = self._the_tracker(B, N, dev).run(feats, rec, cameras, streams, image_sizes=sizes)
             else:
-                kw = {k: v for k, v in self._loc_kw.items() if k not in ("do_refinement", "refine_below")}
+                g = self._groups
                 if self.do_refinement:
-                    res = _refine.localize_and_refine(feats, rec, self.store, self.matcher, cameras, image_sizes=sizes, **kw)
+                    res = _refine.localize_and_refine(feats, rec, self.store, self.matcher, cameras, image_sizes=sizes, **g["localize"], **g["pose"], **g["refine"])
                 else:
-                    kw = {k: v for k, v in kw.items() if k not in ("refinement_method", "projection_min_inliers", "covisibility_frame")}
-                    res = _pose.localize_candidates(feats, rec, self.store, self.matcher, cameras, **kw)
+                    res = _pose.localize_candidates(feats, rec, self.store, self.matcher, cameras, **g["localize"], **g["pose"])
         copied.synchronize()      # returns at once after any read-back of the stage; waits only when the stage made none
         n = host.numpy()
         for b, r in enumerate(res):

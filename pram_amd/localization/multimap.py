@@ -8,18 +8,18 @@ landmark tables are laid out by the GLOBAL landmark id with lm_start naming the 
 them), and point ids are scoped per map."""
 from __future__ import annotations
 
-from typing import Dict, Optional, Sequence
+from typing import Sequence
 
 import numpy as np
 import torch
 
-from pram_amd.localization.candidates import ReferenceStore
+from pram_amd.localization.candidates import ReferenceStore, StoreBase
 
 POINT_ID_BITS = 40      # a store point id = map index << 40 | raw id (COLMAP numbers the points of every model from 1)
 _RAW_MASK = (1 << POINT_ID_BITS) - 1
 
 
-class MultiMapStore:
+class MultiMapStore(StoreBase):
     """maps: ReferenceStores, each built with the start_sid it has in the recogniser's numbering (the reference passes the running
     class count, multimap3d.py:84-90); names: one scene name per map (the reference's matched_scene_name).
 
@@ -91,11 +91,7 @@ class MultiMapStore:
         self.frame_map = np.repeat(np.arange(self.n_maps, dtype=np.int32), [m.n_frames for m in maps])
         self.frame_ids = [(n, fid) for m, n in zip(maps, names) for fid in m.frame_ids]
         self._slices = [{l: (o + int(self.map_row_off[i]), c) for l, (o, c) in sl.items()} for i, m in enumerate(maps) for sl in m._slices]
-        self._dev: Dict[str, dict] = {}
-        self._dev_points: Dict[str, dict] = {}
-        self._pt_values: Optional[dict] = None
-        if device is not None:
-            self.tables(device)
+        self._ready(device)
 
     # ---- point ids
     @staticmethod
@@ -117,54 +113,15 @@ class MultiMapStore:
         ids = np.asarray(ids, dtype=np.int64)
         return np.where(ids < 0, ids, ids >> POINT_ID_BITS), np.where(ids < 0, ids, ids & _RAW_MASK)
 
-    # ---- per-point values: concatenated on first use, each map checking its own then (ReferenceStore's rule)
-    pt_xyz = property(lambda self: self._point_values()["pt_xyz"])
-    pt_desc = property(lambda self: self._point_values()["pt_desc"])
-    pt_sid = property(lambda self: self._point_values()["pt_sid"])
+    # ---- what the base asks for: lm_start (uploaded and padded like the other landmark tables) and n_maps join tables(); the
+    # per-point values are concatenated on first use, each map checking its own then (ReferenceStore's rule)
+    _EXTRA_PADDED, _EXTRA_COUNTS = ("lm_start",), ("n_maps",)
 
     def _point_values(self) -> dict:
         if self._pt_values is None:
-            self._pt_values = {name: np.concatenate([getattr(m, name) for m in self.maps]) for name in ("pt_xyz", "pt_desc", "pt_sid")}
+            self._pt_values = {name: np.concatenate([getattr(m, name) for m in self.maps]) for name in self._POINT_TABLES}
         return self._pt_values
-
-    # ---- host views
-    @property
-    def n_frames(self) -> int:
-        return len(self.frame_ids)
-
-    @property
-    def n_rows(self) -> int:
-        return int(self.frame_off[-1])
-
-    @property
-    def max_frame_rows(self) -> int:
-        return max(m.max_frame_rows for m in self.maps)
 
     def scene_of(self, frame: int) -> str:
         """The name of the map that holds store frame `frame` (the reference's matched_scene_name)."""
         return self.names[int(self.frame_map[frame])]
-
-    def covisible(self, frame: int) -> np.ndarray:
-        """Store indices of the frames covisible with store frame `frame`, best first, in the order of the frame's own map."""
-        return self.covis_frames[self.covis_off[frame]:self.covis_off[frame + 1]].astype(np.int64)
-
-    def rows(self, frame: int) -> np.ndarray:
-        return np.arange(self.frame_off[frame], self.frame_off[frame + 1], dtype=np.int64)
-
-    def rows_by_sid(self, frame: int, sid: int) -> np.ndarray:
-        """The frame's rows with keypoint_segs == sid (an IN-MAP landmark id), original order."""
-        off, n = self._slices[frame].get(int(sid), (0, 0))
-        return self.sel_rows[off:off + n].astype(np.int64)
-
-    def tables(self, device) -> dict:
-        """ReferenceStore.tables' keys over all maps, plus lm_start (uploaded and padded like the others) and n_maps."""
-        key = str(torch.device(device))
-        fresh = key not in self._dev
-        t = ReferenceStore.tables(self, device)      # reads the store through its attributes only
-        if fresh:
-            t["lm_start"] = torch.from_numpy(np.concatenate([self.lm_start, np.zeros(1, dtype=np.int32)])).to(t["lm_frame"].device)
-            t["n_maps"] = self.n_maps
-        return t
-
-    def point_tables(self, device) -> dict:
-        return ReferenceStore.point_tables(self, device)

@@ -38,18 +38,57 @@ def camera_table(cameras: Sequence) -> tuple:
     return ids, params
 
 
+def camera_form(cameras) -> str:
+    """Which of the three forms a ``cameras`` argument has: 'resident' (device_cameras' result: two device tensors and the host
+    ids), 'table' (camera_table's result: two numpy arrays) or 'tuples' (anything else: a sequence of camera tuples, which
+    camera_table checks)."""
+    if isinstance(cameras, tuple) and len(cameras) == 3 and torch.is_tensor(cameras[0]):
+        return "resident"
+    if isinstance(cameras, tuple) and len(cameras) == 2 and isinstance(cameras[0], np.ndarray):
+        return "table"
+    return "tuples"
+
+
 def device_cameras(cameras, device) -> tuple:
     """camera tuples (or camera_table's result) -> (model ids int32 [B], params float64 [B, 8]) on the device plus the ids as a
     host list: what estimate_poses takes as ``cameras`` when the upload (a blocking copy from pageable memory) is to happen once,
     outside the per-batch path."""
-    ids, params = cameras if (isinstance(cameras, tuple) and len(cameras) == 2 and isinstance(cameras[0], np.ndarray)) else camera_table(cameras)
+    ids, params = cameras if camera_form(cameras) == "table" else camera_table(cameras)
     return torch.from_numpy(ids).to(device), torch.from_numpy(params).to(device), [int(i) for i in ids]
 
 
 def _device_cameras(cameras, device):
-    if isinstance(cameras, tuple) and len(cameras) == 3 and torch.is_tensor(cameras[0]):
-        return cameras
-    return device_cameras(cameras, device)
+    return cameras if camera_form(cameras) == "resident" else device_cameras(cameras, device)
+
+
+class ReadBack:
+    """Per-row results on the host after ONE device-to-host copy: est's qvec [P, 4] and tvec [P, 3], the named int32 columns
+    ``ints`` (name -> [P]; they travel as float64, which holds every int32 exactly), optionally an int ``tail`` [P, k] of which
+    row i holds ints[tail_count][i] valid entries, and optionally ``block``, a second int table of any shape packed behind the
+    rows (the selection per query behind the results per pair).  rb[i] -> dict(qvec, tvec, every named int, and 'tail' cut to
+    its count); rb.block -> int64, block's shape."""
+
+    def __init__(self, est: dict, ints: Dict[str, torch.Tensor], tail=None, tail_count=None, block=None):
+        self.names, self.tail_count = tuple(ints), tail_count
+        cols = [est["qvec"], est["tvec"], torch.stack([ints[k] for k in self.names], 1).double()]
+        packed = torch.cat(cols if tail is None else cols + [tail.double()], 1)
+        self.tail_at = packed.shape[1] - (0 if tail is None else tail.shape[1])
+        if block is None:
+            self.rows, self.block = packed.cpu().numpy(), None
+        else:
+            flat = torch.cat([packed.reshape(-1), block.double().reshape(-1)]).cpu().numpy()
+            self.rows, self.block = flat[:packed.numel()].reshape(packed.shape), flat[packed.numel():].reshape(block.shape).astype(np.int64)
+
+    def __len__(self) -> int:
+        return len(self.rows)
+
+    def __getitem__(self, i: int) -> dict:
+        row = self.rows[i]
+        r = {"qvec": row[:4].copy(), "tvec": row[4:7].copy()}
+        r.update({k: int(v) for k, v in zip(self.names, row[7:self.tail_at])})
+        if self.tail_count is not None:
+            r["tail"] = row[self.tail_at:self.tail_at + r[self.tail_count]].astype(np.int64)
+        return r
 
 
 @torch.no_grad()
@@ -103,17 +142,16 @@ def _localize(features: dict, recognition, store, matcher, cameras, *, seg_k: in
                          min_inlier_ratio=min_inlier_ratio, refine_iters=refine_iters, seed=seed)
     chosen = ops.pose_select(est["success"], est["num_inliers"], seg_k, min_inliers)
     # the one read-back: 7 doubles and 3 ints per pair, 3 ints per query
-    packed = torch.cat([est["qvec"], est["tvec"], est["success"].double()[:, None], est["num_inliers"].double()[:, None],
-                        cor["count"].double()[:, None]], 1)
-    packed = torch.cat([packed.reshape(-1), chosen.double().reshape(-1)]).cpu().numpy()
-    per_pair, sel = packed[:B * seg_k * 10].reshape(B * seg_k, 10), packed[B * seg_k * 10:].reshape(B, 3).astype(np.int64)
+    rb = ReadBack(est, {"success": est["success"], "num_inliers": est["num_inliers"], "count": cor["count"]}, block=chosen)
+    sel = rb.block
     lists = _cand._candidate_lists(cor, host, m, store, B, seg_k)
     out = []
     for b in range(B):
         for w, c in enumerate(lists[b]):
             p = b * seg_k + w
-            c.update(success=bool(per_pair[p, 7]), qvec=per_pair[p, :4].copy(), tvec=per_pair[p, 4:7].copy(), num_inliers=int(per_pair[p, 8]),
-                     inliers=est["inliers"][p, :c["n_query_kpts"]], n_matches_host=int(per_pair[p, 9]))
+            v = rb[p]
+            c.update(success=bool(v["success"]), qvec=v["qvec"], tvec=v["tvec"], num_inliers=v["num_inliers"],
+                     inliers=est["inliers"][p, :c["n_query_kpts"]], n_matches_host=v["count"])
         kept, status = int(sel[b, 0]), int(sel[b, 1])
         r = {"success": kept >= 0, "tracking_status": None if status < 0 else bool(status), "candidates": lists[b]}
         if kept >= 0:

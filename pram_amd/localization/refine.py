@@ -21,7 +21,7 @@ reference_frame_id stays the localisation's; the kept matches' xyz are the refer
 points' xyz, the same numbers in a consistent map).  One map per store; no QueryPipeline stage."""
 from __future__ import annotations
 
-from typing import List, Optional
+from typing import Dict, List, Optional
 
 import numpy as np
 import torch
@@ -31,6 +31,61 @@ from pram_amd.localization import candidates as _cand
 from pram_amd.localization import pose as _pose
 
 _MATCHED = ops.MATCH_RESULT_KEYS + (ops.MATCH_SRC,)
+
+
+def enable_mask(enable, B: int, dtype=np.int32):
+    """A per-query ``enable`` argument (None, a list, a numpy array of any dtype, a tensor on any device) -> numpy [B] of dtype;
+    None stays None.  Anything but one entry per query is a ValueError."""
+    if enable is None:
+        return None
+    on = np.asarray(enable.cpu() if torch.is_tensor(enable) else enable).astype(dtype).reshape(-1)
+    if on.size != B:
+        raise ValueError("enable: expected one entry per query")
+    return on
+
+
+def _preamble(features: dict, store, covisibility_frame: Optional[int]):
+    """What both refinements check first -> (counts, device, B, n_cov); the caller returns [] for B == 0."""
+    counts = features["counts"]
+    ops._chk(counts, "counts", torch.int32)
+    n_cov = int(store.covisibility_frame if covisibility_frame is None else covisibility_frame)
+    if n_cov < 1:
+        raise ValueError("covisibility_frame < 1")
+    return counts, counts.device, counts.numel(), n_cov
+
+
+def _device_enable(enable, B: int, dev):
+    on = enable_mask(enable, B)
+    return None if on is None else torch.from_numpy(on).to(dev)
+
+
+def _solve_and_vote(lists: dict, keys, cameras, store, tables: dict, n_cov: int, ref_frame: torch.Tensor, extra: Dict[str, torch.Tensor],
+                    own, pose_kw: dict) -> List[Optional[dict]]:
+    """The tail both refinements share, from a query's stacked matches to its result: ONE pose per query on ``lists``
+    (matched_keypoints, matched_xyzs, matched_point3D_ids, count; seg_k = 1, so the sampler's pair index is the query index), the
+    frame vote of the stack's points, ONE read-back (7 doubles, the ints below, the voted frames), and per query None (ref_frame
+    < 0: not located, or not enabled) or the result dict with lists[keys] cut to the count — reference_frame_id is the vote's
+    first frame and, with an empty vote, stays the localisation's — to which own(b, v) adds the calling form's own entries from
+    the read-back row v (``extra`` by name)."""
+    est = _pose.estimate_poses(lists["matched_keypoints"], lists["matched_xyzs"], lists["count"], cameras, seg_k=1, **pose_kw)
+    k = max(1, min(n_cov, store.n_frames))
+    best_f, _, n_best = ops.refine_frame_vote(lists["matched_point3D_ids"], lists["count"], est["inliers"], est["success"], tables, k)
+    rb = _pose.ReadBack(est, dict(success=est["success"], num_inliers=est["num_inliers"], count=lists["count"], ref_frame=ref_frame, **extra, n_best=n_best),
+                        tail=best_f, tail_count="n_best")
+    out = []
+    for b in range(len(rb)):
+        v = rb[b]
+        if v["ref_frame"] < 0:
+            out.append(None)
+            continue
+        frames = [store.frame_ids[int(i)] for i in v["tail"]]
+        r = {"success": bool(v["success"]), "qvec": v["qvec"], "tvec": v["tvec"], "num_inliers": v["num_inliers"],
+             "inliers": est["inliers"][b, :v["count"]].bool(), "refinement_reference_frame_ids": frames,
+             "reference_frame_id": frames[0] if frames else store.frame_ids[v["ref_frame"]]}
+        r.update({key: lists[key][b, :v["count"]] for key in keys})
+        r.update(own(b, v))
+        out.append(r)
+    return out
 
 
 @torch.no_grad()
@@ -48,53 +103,27 @@ def refine_by_matching(features: dict, state: dict, store, matcher, cameras, *, 
     the m merged rows; refinement_reference_frame_ids (frame ids, at most covisibility_frame), reference_frame_id; n_covisible
     (frames matched), used_init (the localisation's matches were appended), and slots: per covisible frame its frame id,
     n_ref_kpts, matches0 / matching_scores0 [n_query_kpts] and n_matches (0-d device tensor)."""
-    counts = features["counts"]
-    ops._chk(counts, "counts", torch.int32)
-    dev, B = counts.device, counts.numel()
-    n_cov = int(store.covisibility_frame if covisibility_frame is None else covisibility_frame)
-    if n_cov < 1:
-        raise ValueError("covisibility_frame < 1")
+    counts, dev, B, n_cov = _preamble(features, store, covisibility_frame)
     if B == 0:
         return []
     tables = store.tables(dev)
-    seg_k = int(state["seg_k"])
-    if enable is not None:
-        enable = torch.as_tensor(np.asarray(enable.cpu() if torch.is_tensor(enable) else enable).astype(np.int32).reshape(-1)).to(dev)
-        if enable.numel() != B:
-            raise ValueError("enable: expected one entry per query")
     chosen = state["chosen"]
-    plan, ref_frame, used, init_on = ops.refine_plan(chosen, state["plan"], counts.contiguous(), tables, n_cov, enable)
+    plan, ref_frame, used, init_on = ops.refine_plan(chosen, state["plan"], counts.contiguous(), tables, n_cov, _device_enable(enable, B, dev))
     cor, host, m = _cand._match_planned(features, {"plan": plan, "vote": {"tokens": state["tokens"]}}, store, matcher)
     merged = ops.refine_merge(cor, state["cor"], chosen, init_on, n_cov)
-    est = _pose.estimate_poses(merged["matched_keypoints"], merged["matched_xyzs"], merged["count"], cameras, seg_k=1, threshold=threshold,
-                               trials=trials, min_inlier_ratio=min_inlier_ratio, refine_iters=refine_iters, seed=seed)
-    k = max(1, min(n_cov, store.n_frames))
-    best_f, _, n_best = ops.refine_frame_vote(merged["matched_point3D_ids"], merged["count"], est["inliers"], est["success"], tables, k)
-    # the one read-back: 7 doubles and 7 + k ints per query
-    ints = torch.stack([est["success"], est["num_inliers"], merged["count"], ref_frame, used, init_on, n_best], 1)
-    packed = torch.cat([est["qvec"], est["tvec"], ints.double(), best_f.double()], 1).cpu().numpy()
     f = ops.CAND_PLAN_FIELDS
     col = lambda name: host[f.index(name)]
-    out: List[Optional[dict]] = []
-    for b in range(B):
-        succ, ninl, n, rf, nu, ini, nb = (int(v) for v in packed[b, 7:14])
-        if rf < 0:
-            out.append(None)
-            continue
-        frames = [store.frame_ids[int(i)] for i in packed[b, 14:14 + nb]]
-        r = {"success": bool(succ), "qvec": packed[b, :4].copy(), "tvec": packed[b, 4:7].copy(), "num_inliers": ninl,
-             "inliers": est["inliers"][b, :n].bool(), "refinement_reference_frame_ids": frames,
-             "reference_frame_id": frames[0] if frames else store.frame_ids[rf], "n_covisible": nu, "used_init": bool(ini)}
-        r.update({key: merged[key][b, :n] for key in _MATCHED})
+
+    def own(b, v):
         slots = []
-        for j in range(nu):
-            p = b * n_cov + j
+        for p in range(b * n_cov, b * n_cov + v["n_covisible"]):
             l0 = int(col("lens0")[p])
             slots.append({"reference_frame_id": store.frame_ids[int(col("frame")[p])], "n_query_kpts": l0, "n_ref_kpts": int(col("lens1")[p]),
                           "matches0": m["matches0"][p, :l0], "matching_scores0": m["matching_scores0"][p, :l0], "n_matches": cor["count"][p]})
-        r["slots"] = slots
-        out.append(r)
-    return out
+        return {"n_covisible": v["n_covisible"], "used_init": bool(v["used_init"]), "slots": slots}
+
+    return _solve_and_vote(merged, _MATCHED, cameras, store, tables, n_cov, ref_frame, {"n_covisible": used, "used_init": init_on}, own,
+                           dict(threshold=threshold, trials=trials, min_inlier_ratio=min_inlier_ratio, refine_iters=refine_iters, seed=seed))
 
 
 def image_size_table(cameras) -> np.ndarray:
@@ -129,17 +158,11 @@ def refine_by_projection(features: dict, state: dict, store, cameras, *, thresho
     table mark nothing (the reference raises KeyError); a failed solver comes back with success False and zeros and the vote over
     all matched ids (the reference fails at its own print of ret['num_inliers']); with an empty vote reference_frame_id stays the
     localisation's."""
-    counts = features["counts"]
-    ops._chk(counts, "counts", torch.int32)
-    dev, B = counts.device, counts.numel()
-    n_cov = int(store.covisibility_frame if covisibility_frame is None else covisibility_frame)
-    if n_cov < 1:
-        raise ValueError("covisibility_frame < 1")
+    counts, dev, B, n_cov = _preamble(features, store, covisibility_frame)
     if B == 0:
         return []
-    resident = isinstance(cameras, tuple) and len(cameras) == 3 and torch.is_tensor(cameras[0])
     if image_sizes is None:
-        if resident:
+        if _pose.camera_form(cameras) == "resident":
             raise ValueError("refine_by_projection: image_sizes is needed when cameras is device_cameras' result")
         image_sizes = image_size_table(cameras)
     if not torch.is_tensor(image_sizes):
@@ -150,10 +173,7 @@ def refine_by_projection(features: dict, state: dict, store, cameras, *, thresho
     tables = store.point_tables(dev)
     if int(tables["n_points"]) < 1:
         return [None] * B      # a map without points: nothing to project
-    if enable is not None:
-        enable = torch.as_tensor(np.asarray(enable.cpu() if torch.is_tensor(enable) else enable).astype(np.int32).reshape(-1)).to(dev)
-        if enable.numel() != B:
-            raise ValueError("enable: expected one entry per query")
+    enable = _device_enable(enable, B, dev)
     cams = _pose._device_cameras(cameras, dev)
     chosen, loc = state["chosen"], state["est"]
     cap = max(1, min(int(tables["n_points"]), (n_cov + 1) * store.max_frame_rows))
@@ -164,28 +184,10 @@ def refine_by_projection(features: dict, state: dict, store, cameras, *, thresho
     best, d0, d1, accept = ops.projref_match(kpts, features["descriptors"].contiguous(), counts.contiguous(), cand_pt, cand_uv, n_cand, tables,
                                              threshold)
     cor = ops.projref_correspond(accept, best, counts.contiguous(), kpts, cand_pt, n_cand, tables)
-    est = _pose.estimate_poses(cor["matched_keypoints"], cor["matched_xyzs"], cor["count"], cams, seg_k=1, threshold=threshold, trials=trials,
-                               min_inlier_ratio=min_inlier_ratio, refine_iters=refine_iters, seed=seed)
-    k = max(1, min(n_cov, store.n_frames))
-    best_f, _, n_best = ops.refine_frame_vote(cor["matched_point3D_ids"], cor["count"], est["inliers"], est["success"], tables, k)
-    # the one read-back: 7 doubles and 8 + k ints per query
-    ints = torch.stack([est["success"], est["num_inliers"], cor["count"], ref_frame, n_union, n_cand, n_best, counts], 1)
-    packed = torch.cat([est["qvec"], est["tvec"], ints.double(), best_f.double()], 1).cpu().numpy()
     dists = torch.stack([d0, d1], 2)
-    out: List[Optional[dict]] = []
-    for b in range(B):
-        succ, ninl, n, rf, nu, nc, nb, nq = (int(v) for v in packed[b, 7:15])
-        if rf < 0:
-            out.append(None)
-            continue
-        frames = [store.frame_ids[int(i)] for i in packed[b, 15:15 + nb]]
-        r = {"success": bool(succ), "qvec": packed[b, :4].copy(), "tvec": packed[b, 4:7].copy(), "num_inliers": ninl,
-             "inliers": est["inliers"][b, :n].bool(), "refinement_reference_frame_ids": frames,
-             "reference_frame_id": frames[0] if frames else store.frame_ids[rf], "n_union": nu, "n_projected": nc,
-             "dists": dists[b, :max(0, min(nq, dists.shape[1]))]}
-        r.update({key: cor[key][b, :n] for key in _PROJ_MATCHED})
-        out.append(r)
-    return out
+    own = lambda b, v: {"n_union": v["n_union"], "n_projected": v["n_projected"], "dists": dists[b, :max(0, min(v["n_query"], dists.shape[1]))]}
+    return _solve_and_vote(cor, _PROJ_MATCHED, cams, store, tables, n_cov, ref_frame, {"n_union": n_union, "n_projected": n_cand, "n_query": counts}, own,
+                           dict(threshold=threshold, trials=trials, min_inlier_ratio=min_inlier_ratio, refine_iters=refine_iters, seed=seed))
 
 
 @torch.no_grad()
@@ -217,9 +219,7 @@ def localize_and_refine(features: dict, recognition, store, matcher, cameras, *,
             r["refinement"] = x
         return out
     B = len(out)
-    on = np.ones(B, dtype=bool) if enable is None else np.asarray(enable.cpu() if torch.is_tensor(enable) else enable).astype(bool).reshape(-1)
-    if on.size != B:
-        raise ValueError("enable: expected one entry per query")
+    on = np.ones(B, dtype=bool) if enable is None else enable_mask(enable, B, bool)
     located = np.array([r["success"] for r in out], dtype=bool)
     strong = np.array([bool(r["tracking_status"]) and r["num_inliers"] >= projection_min_inliers for r in out], dtype=bool)
     by_proj, by_match = on & located & strong, on & located & ~strong

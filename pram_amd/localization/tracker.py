@@ -28,7 +28,7 @@ an unknown reference frame) changes nothing, as in 4.13; one map per store; trac
 is not built; no QueryPipeline stage."""
 from __future__ import annotations
 
-from typing import List, Optional, Sequence
+from typing import Dict, List, Optional, Sequence
 
 import numpy as np
 import torch
@@ -78,11 +78,29 @@ class TrackState:
         return sum(getattr(self, k).numel() * getattr(self, k).element_size() for k in self.FIELDS)
 
 
+# Tracker's keyword options by the stage that takes them: estimate_poses (and every call built on it), localize_candidates' own,
+# localize_and_refine's own, and the tracker's switches
+OPTION_GROUPS = {"pose": ("threshold", "trials", "min_inlier_ratio", "refine_iters", "seed"),
+                 "localize": ("seg_k", "min_kpts", "min_inliers", "semantic_matching", "overlap_ratio"),
+                 "refine": ("covisibility_frame", "refinement_method", "projection_min_inliers"),
+                 "tracker": ("do_refinement", "refine_below")}
+TRACKER_KEYS = tuple(k for keys in OPTION_GROUPS.values() for k in keys)
+
+
+def split_options(kw: dict, who: str = "Tracker") -> Dict[str, dict]:
+    """A dict of Tracker's keyword options (any subset) -> one dict per group of OPTION_GROUPS; a key of no group is a TypeError."""
+    unknown = sorted(set(kw) - set(TRACKER_KEYS))
+    if unknown:
+        raise TypeError(f"{who}: unknown arguments {unknown} (expected Tracker's: {', '.join(TRACKER_KEYS)})")
+    return {g: {k: kw[k] for k in keys if k in kw} for g, keys in OPTION_GROUPS.items()}
+
+
 def _sub_cameras(cameras, idx: Sequence[int]):
-    if isinstance(cameras, tuple) and len(cameras) == 3 and torch.is_tensor(cameras[0]):      # device_cameras' result
+    form = _pose.camera_form(cameras)
+    if form == "resident":
         t = torch.as_tensor(list(idx), dtype=torch.long, device=cameras[0].device)
         return cameras[0][t].contiguous(), cameras[1][t].contiguous(), [cameras[2][i] for i in idx]
-    if isinstance(cameras, tuple) and len(cameras) == 2 and isinstance(cameras[0], np.ndarray):      # camera_table's result
+    if form == "table":
         return cameras[0][list(idx)], cameras[1][list(idx)]
     return [cameras[i] for i in idx]
 
@@ -115,16 +133,15 @@ class Tracker:
                  do_refinement: bool = True, refinement_method: str = "matching", refine_below: int = 256, projection_min_inliers: int = 64,
                  covisibility_frame: Optional[int] = None, trials: int = 1000, semantic_matching: bool = True, overlap_ratio: float = 0.5,
                  min_inlier_ratio: float = 0.01, refine_iters: int = _pose.DEFAULT_REFINE_ITERS, seed: int = 0, device="cuda"):
+        given = locals()      # the keyword options by name, before anything else is bound
+        opts = split_options({k: given[k] for k in TRACKER_KEYS})
         if refinement_method not in ("matching", "projection"):
             raise NotImplementedError(f"refinement_method {refinement_method!r}")
         self.store, self.matcher = store, matcher
         self.n_streams, self.n_max = int(n_streams), int(n_max)
         self.do_refinement, self.refinement_method, self.refine_below = bool(do_refinement), refinement_method, int(refine_below)
         self.min_inliers, self.threshold = int(min_inliers), float(threshold)
-        self._pose_kw = dict(threshold=threshold, trials=trials, min_inlier_ratio=min_inlier_ratio, refine_iters=refine_iters, seed=seed)
-        self._loc_kw = dict(seg_k=seg_k, min_kpts=min_kpts, min_inliers=min_inliers, semantic_matching=semantic_matching, overlap_ratio=overlap_ratio,
-                            **self._pose_kw)
-        self._ref_kw = dict(covisibility_frame=covisibility_frame, refinement_method=refinement_method, projection_min_inliers=projection_min_inliers)
+        self._pose_kw, self._loc_kw, self._ref_kw = opts["pose"], {**opts["localize"], **opts["pose"]}, opts["refine"]
         self.covisibility_frame = covisibility_frame
         self.state = TrackState(self.n_streams, self.n_max, device)
         self._dummy = torch.zeros(1, device=self.state.device, dtype=torch.int32)
@@ -185,11 +202,20 @@ class Tracker:
                          slot.tolist(), torch.from_numpy(ref).to(dev), _cand._query_norm(features), cor, mask)
 
     @staticmethod
-    def _lost_result(tracking=None, localization=None) -> dict:
-        r = {"source": None, "success": False, "qvec": None, "tvec": None, "num_inliers": 0, "inliers": None, "reference_frame_id": None,
-             "tracking": tracking, "localization": localization}
-        r.update({k: None for k in _LISTS})
+    def _result(source=None, src: Optional[dict] = None, tracking=None, localization=None) -> dict:
+        """A query's result: located by ``source`` on ``src`` (the stage's dict the pose, the inliers, the lists and the
+        reference frame are taken from), or, without src, lost."""
+        src = src or {}
+        r = {"source": source, "success": bool(src), "qvec": src.get("qvec"), "tvec": src.get("tvec"), "num_inliers": src.get("num_inliers", 0),
+             "inliers": src.get("inliers"), "reference_frame_id": src.get("reference_frame_id"), "tracking": tracking, "localization": localization}
+        r.update({k: src.get(k) for k in _LISTS})
         return r
+
+    def _record(self, s: int, src: Optional[dict] = None) -> None:
+        """A stream's outcome: located on src, or (None) lost — its last pose stays, a lost slot is never read."""
+        self.lost[s] = src is None
+        if src is not None:
+            self.qvec[s], self.tvec[s], self.reference_frame_id[s] = src["qvec"], src["tvec"], src["reference_frame_id"]
 
     # ---- the tracking branch
     @torch.no_grad()
@@ -207,30 +233,25 @@ class Tracker:
             return out
         st = self.state.arrays()
         plan, loc_plan = ops.track_plan(counts, torch.from_numpy(slot).to(dev), st, N)
-        T = max(64, _cand._round_up(max(N, self.n_max), 64))      # known on the host: no plan read-back
-        data = ops.cand_gather(plan, self._dummy, ops.track_gather_tables(st, self._dummy), de, kp, sc, _cand._query_norm(features), T)
-        data["keypoints0"], data["keypoints1"] = data["norm_keypoints0"], data["norm_keypoints1"]
-        f = ops.CAND_PLAN_FIELDS
-        data["lens0"], data["lens1"] = plan[f.index("lens0")], plan[f.index("lens1")]
-        net = getattr(self.matcher, "net", self.matcher)
-        m = net.produce_matches(data)
+        data = ops.cand_gather(plan, self._dummy, ops.track_gather_tables(st, self._dummy), de, kp, sc, _cand._query_norm(features),
+                               _cand.padded_size(N, self.n_max))      # known on the host: no plan read-back
+        m = _cand.match_grouped(data, plan, self.matcher)
         cor = ops.track_correspond(m["matches0"][:, :N], plan, st, kp, N)
         est = _pose.estimate_poses(cor["matched_keypoints"], cor["matched_xyzs"], cor["count"], cameras, seg_k=1, **self._pose_kw)
         # the one read-back: 7 doubles and 3 ints per query
-        ints = torch.stack([est["success"], est["num_inliers"], cor["count"]], 1)
-        packed = torch.cat([est["qvec"], est["tvec"], ints.double()], 1).cpu().numpy()
-        cnt_host = None
+        rb = _pose.ReadBack(est, {"success": est["success"], "num_inliers": est["num_inliers"], "n_matches": cor["count"]})
         tracked = np.zeros(B, dtype=bool)
         for b in range(B):
             if slot[b] < 0:
                 continue
-            succ, ninl, n = (int(v) for v in packed[b, 7:10])
-            tracked[b] = bool(succ) and ninl >= self.min_inliers
-            t = {"success": bool(succ), "tracked": bool(tracked[b]), "qvec": packed[b, :4].copy(), "tvec": packed[b, 4:7].copy(), "num_inliers": ninl,
+            v = rb[b]
+            n = v["n_matches"]
+            tracked[b] = bool(v["success"]) and v["num_inliers"] >= self.min_inliers
+            t = {"success": bool(v["success"]), "tracked": bool(tracked[b]), "qvec": v["qvec"], "tvec": v["tvec"], "num_inliers": v["num_inliers"],
                  "inliers": est["inliers"][b, :n].bool(), "n_matches": n, "reference_frame_id": self.reference_frame_id[slots[b]],
                  "matches0": m["matches0"][b], "matching_scores0": m["matching_scores0"][b], "refinement": None}
             t.update({k: cor[k][b, :n] for k in _LISTS})
-            out[b] = self._lost_result(tracking=t)
+            out[b] = self._result(tracking=t)
         # refinement is necessary for tracking last frame (tracker.py:85-94)
         group = tracked & np.array([out[b] is not None and out[b]["tracking"]["num_inliers"] < self.refine_below for b in range(B)])
         refined: List[Optional[dict]] = [None] * B
@@ -247,7 +268,7 @@ class Tracker:
         for b in range(B):
             if not tracked[b]:
                 if slot[b] >= 0:
-                    self.lost[slots[b]] = True
+                    self._record(slots[b])
                 continue
             t, x, s = out[b]["tracking"], refined[b] if group[b] else None, slots[b]
             if x is not None:
@@ -255,18 +276,15 @@ class Tracker:
                 t["refinement"] = x
             if x is not None and x["success"]:      # a refinement with success False changes nothing
                 if x["num_inliers"] < self.min_inliers:      # verified again (tracker.py:94)
-                    tracked[b], t["tracked"], self.lost[s] = False, False, True
+                    tracked[b], t["tracked"] = False, False
+                    self._record(s)
                     continue
-                src, fid = x, x["reference_frame_id"]
-                out[b].update(source="track+refine")
-                members[b] = (s, {k: x[k] for k in _COMMIT_KEYS}, x["inliers"], fid)
+                out[b] = self._result("track+refine", x, t)
+                members[b] = (s, {k: x[k] for k in _COMMIT_KEYS}, x["inliers"], x["reference_frame_id"])
             else:
-                src, fid = t, t["reference_frame_id"]
-                out[b].update(source="track")
-                direct_slot[b], direct_ref[b] = s, self._index_of.get(fid, -1)
-            out[b].update(success=True, qvec=src["qvec"], tvec=src["tvec"], num_inliers=src["num_inliers"], inliers=src["inliers"], reference_frame_id=fid)
-            out[b].update({k: src.get(k) for k in _LISTS})
-            self.qvec[s], self.tvec[s], self.reference_frame_id[s] = src["qvec"], src["tvec"], fid
+                out[b] = self._result("track", t, t)
+                direct_slot[b], direct_ref[b] = s, self._index_of.get(t["reference_frame_id"], -1)
+            self._record(s, out[b])
         # the hand-over: the tracker's inlier rows, or the refinement's (update_current_frame, update_point3ds)
         if (direct_slot >= 0).any():
             self._commit_lists(features, cor, est["inliers"], direct_slot, direct_ref, seg_ids)
@@ -300,24 +318,20 @@ class Tracker:
         seg_ids = torch.full((B, kp.shape[1]), -1, device=dev, dtype=torch.int32)
         seg_ids[t] = vote["seg_ids"]
         out, members = [], {}
-        for i, (b, r) in enumerate(zip(which, res)):
+        for b, r in zip(which, res):
             s = slots[b]
             if not r["success"]:
-                self.lost[s] = True
-                out.append(self._lost_result(localization=r))
+                self._record(s)
+                out.append(self._result(localization=r))
                 continue
             x = r.get("refinement")
             if x is not None and x["success"]:      # multimap3d.py:259-271: the refinement's inlier rows
                 src, inl = x, x["inliers"]
             else:                                    # update_query_frame, multimap3d.py:315-328: ALL matches of the kept candidate
                 src, inl = r, None
-            fid = src["reference_frame_id"]
-            o = {"source": "relocalize", "success": True, "qvec": src["qvec"], "tvec": src["tvec"], "num_inliers": src["num_inliers"],
-                 "inliers": src["inliers"], "reference_frame_id": fid, "tracking": None, "localization": r}
-            o.update({k: src.get(k) for k in _LISTS})
-            out.append(o)
-            members[b] = (s, {k: src[k] for k in _COMMIT_KEYS}, inl, fid)
-            self.lost[s], self.qvec[s], self.tvec[s], self.reference_frame_id[s] = False, src["qvec"], src["tvec"], fid
+            out.append(self._result("relocalize", src, None, r))
+            members[b] = (s, {k: src[k] for k in _COMMIT_KEYS}, inl, src["reference_frame_id"])
+            self._record(s, src)
         self._commit(features, members, seg_ids)
         return out
 

@@ -282,7 +282,7 @@ def _tracking_inputs(trk, feats):
     slot = torch.tensor([s if not trk.lost[s] else -1 for s in range(B)], dtype=torch.int32, device=feats["counts"].device)
     plan, _ = ops.track_plan(feats["counts"], slot, st, N)
     dummy = torch.zeros(1, dtype=torch.int32, device=slot.device)
-    T = max(64, cd._round_up(max(N, trk.n_max), 64))
+    T = cd.padded_size(N, trk.n_max)
     data = ops.cand_gather(plan, dummy, ops.track_gather_tables(st, dummy), feats["descriptors"], feats["keypoints"], feats["scores"], cd._query_norm(feats), T)
     return data, plan.cpu().numpy()
 

@@ -220,3 +220,29 @@ def test_per_point_values_are_checked_on_first_use():
     assert S.store_point_ids(1, 777777) in S.pt_ids
     with pytest.raises(ValueError, match="neither a value nor a row"):
         S.pt_xyz
+
+
+def test_stores_share_the_base_and_the_host_views():
+    """Both stores derive from StoreBase (MultiMapStore is no ReferenceStore) and take every shared method from it; a one-map
+    store answers the host views as the map does."""
+    from pram_amd.localization.candidates import ReferenceStore, StoreBase
+    from pram_amd.localization.multimap import MultiMapStore
+    assert issubclass(ReferenceStore, StoreBase) and issubclass(MultiMapStore, StoreBase) and not issubclass(MultiMapStore, ReferenceStore)
+    for name in ("tables", "point_tables", "covisible", "rows", "rows_by_sid", "n_frames", "n_rows", "max_frame_rows", "pt_xyz", "pt_desc", "pt_sid"):
+        assert name not in vars(ReferenceStore) and name not in vars(MultiMapStore) and name in vars(StoreBase), name
+    assert "_point_values" in vars(ReferenceStore) and "_point_values" in vars(MultiMapStore)
+    assert MultiMapStore._EXTRA_PADDED == ("lm_start",) and MultiMapStore._EXTRA_COUNTS == ("n_maps",) and ReferenceStore._EXTRA_PADDED == ()
+    m = RR.covisible_scene()[0]
+    one = _stores([dict(m, start_sid=0)], covisibility_frame=RR.COVIS)[0]
+    S = MultiMapStore([one], ["only"])
+    assert (S.n_frames, S.n_rows, S.max_frame_rows) == (one.n_frames, one.n_rows, one.max_frame_rows) and S.n_maps == 1
+    for f in range(one.n_frames):
+        assert np.array_equal(S.rows(f), one.rows(f)) and np.array_equal(S.covisible(f), one.covisible(f))
+        for sid in np.unique(one.keypoint_segs[one.rows(f)]).tolist() + [9999]:
+            assert np.array_equal(S.rows_by_sid(f, sid), one.rows_by_sid(f, sid))
+    for name in ("pt_xyz", "pt_desc", "pt_sid"):
+        assert np.array_equal(getattr(S, name), getattr(one, name)) and getattr(S, name).dtype == getattr(one, name).dtype
+    from pram_amd._lib import PramHipError
+    for store in (one, S):
+        with pytest.raises(PramHipError):
+            store.tables("cpu")

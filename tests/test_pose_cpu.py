@@ -165,3 +165,52 @@ def test_exported_symbols():
         assert callable(getattr(ops, fn))
     for k, v in pr.MODELS.items():
         assert ops.CAMERA_MODELS[k] == v and re.search(r"#define PRAM_CAM_%s %d\b" % (k, v), header)
+
+
+def test_camera_form():
+    """The three forms of a ``cameras`` argument, and that a malformed tuple counts as camera tuples (camera_table rejects it)."""
+    import torch
+    from pram_amd.localization.pose import camera_form, camera_table, device_cameras
+    cams = list(pr.SCENE_CAMERAS.values())
+    table = camera_table(cams)
+    assert camera_form(cams) == "tuples" and camera_form(tuple(cams)) == "tuples" and camera_form([]) == "tuples"
+    assert camera_form(table) == "table"
+    resident = device_cameras(table, "cpu")
+    assert camera_form(resident) == "resident" and camera_form(device_cameras(cams, "cpu")) == "resident"
+    assert torch.equal(resident[0], torch.from_numpy(table[0])) and resident[2] == table[0].tolist()
+    # two lists are no camera_table result, three arrays no device_cameras result: both go to camera_table, which refuses them
+    for bad in ((table[0].tolist(), table[1].tolist()), (table[0], table[1], table[0].tolist())):
+        assert camera_form(bad) == "tuples"
+        with pytest.raises((ValueError, IndexError, TypeError)):
+            device_cameras(bad, "cpu")
+
+
+def test_read_back_round_trips():
+    """ReadBack on CPU tensors: qvec / tvec bit for bit, the int32 values -1, 0 and 2**31 - 1 through float64, a ragged tail cut to
+    its count, and the second block behind the rows."""
+    import torch
+    from pram_amd.localization.pose import ReadBack
+    rng = np.random.default_rng(5)
+    P, k = 6, 4
+    q, t = rng.standard_normal((P, 4)), rng.standard_normal((P, 3)) * 1e3
+    q[0, 0], t[1, 2], q[2, 1] = np.nextafter(1.0, 2.0), -0.0, 5e-324      # one ulp above 1, a negative zero, a subnormal
+    est = {"qvec": torch.from_numpy(q), "tvec": torch.from_numpy(t)}
+    a = np.array([-1, 0, 2 ** 31 - 1, 7, -2 ** 31, 1], dtype=np.int32)
+    n_tail = np.array([0, 1, 4, 2, 3, 4], dtype=np.int32)
+    tail = rng.integers(0, 2 ** 31 - 1, (P, k)).astype(np.int32)
+    block = rng.integers(-1, 2 ** 31 - 1, (3, 3)).astype(np.int32)
+    ints = {"first": torch.from_numpy(a), "n_tail": torch.from_numpy(n_tail), "last": torch.from_numpy(a[::-1].copy())}
+    rb = ReadBack(est, ints, tail=torch.from_numpy(tail), tail_count="n_tail", block=torch.from_numpy(block))
+    assert len(rb) == P and rb.block.dtype == np.int64 and np.array_equal(rb.block, block)
+    for i in range(P):
+        v = rb[i]
+        assert v["qvec"].tobytes() == q[i].tobytes() and v["tvec"].tobytes() == t[i].tobytes()
+        assert (v["first"], v["n_tail"], v["last"]) == (int(a[i]), int(n_tail[i]), int(a[P - 1 - i])) and type(v["first"]) is int
+        assert v["tail"].tolist() == tail[i, :n_tail[i]].tolist()
+        v["qvec"][0] = 0.0      # a copy: the next look is unchanged
+        assert rb[i]["qvec"].tobytes() == q[i].tobytes()
+    plain = ReadBack(est, {"only": torch.from_numpy(a)})
+    assert plain.block is None and set(plain[2]) == {"qvec", "tvec", "only"} and plain[2]["only"] == 2 ** 31 - 1
+    empty = ReadBack({"qvec": torch.zeros(0, 4, dtype=torch.float64), "tvec": torch.zeros(0, 3, dtype=torch.float64)},
+                     {"only": torch.zeros(0, dtype=torch.int32)}, block=torch.zeros(0, 3, dtype=torch.int32))
+    assert len(empty) == 0 and empty.block.shape == (0, 3)

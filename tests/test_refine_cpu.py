@@ -138,3 +138,20 @@ def test_restatement_reproduces_the_reference(golden):
         assert out["used_init"] == bool(g[f"case{i}_used_init"])
         n_cases += 1
     assert n_cases >= 4
+
+
+def test_enable_mask_forms():
+    """The ``enable`` argument of the refinements: a list, numpy bool, a tensor, None, and a wrong length."""
+    import torch
+    from pram_amd.localization.refine import enable_mask
+    want = [1, 0, 1, 1]
+    for form in (want, [True, False, True, True], np.array(want, dtype=bool), np.array(want, dtype=np.int64), np.array([[2.0, 0.0], [1.0, -1.0]]),
+                 torch.tensor(want), torch.tensor(want, dtype=torch.bool)):
+        on = enable_mask(form, 4, bool)
+        assert on.dtype == bool and on.tolist() == [bool(x) for x in want]
+    on = enable_mask(np.array(want, dtype=bool), 4)
+    assert on.dtype == np.int32 and on.tolist() == want and on.flags["C_CONTIGUOUS"]
+    assert enable_mask(None, 4) is None and enable_mask(None, 0) is None and enable_mask([], 0).shape == (0,)
+    for bad in (want[:3], want + [1], [], torch.tensor(want[:2])):
+        with pytest.raises(ValueError, match="one entry per query"):
+            enable_mask(bad, 4)

@@ -115,3 +115,31 @@ def test_tracker_module_without_a_gpu():
     sub = T._sub_cameras((ids, params), [3, 1])
     assert sub[0].tolist() == [3, 1] and np.array_equal(sub[1], params[[3, 1]])
     assert "lost = not success" in T.__doc__ and "recogniser" in T.Tracker.__doc__
+
+
+def test_option_groups_partition_the_tracker_keys():
+    """Every keyword option of Tracker stands in exactly one group; the splitter keeps values, takes any subset, and rejects an
+    unknown key the way Localizer does."""
+    import inspect
+    from pram_amd.localization import localizer as L
+    from pram_amd.localization import tracker as T
+    flat = [k for keys in T.OPTION_GROUPS.values() for k in keys]
+    assert set(T.OPTION_GROUPS) == {"pose", "localize", "refine", "tracker"}
+    assert sorted(flat) == sorted(T.TRACKER_KEYS) and len(set(flat)) == len(flat) == 15 and L.TRACKER_KEYS is T.TRACKER_KEYS
+    sig = inspect.signature(T.Tracker.__init__).parameters
+    assert {k for k, p in sig.items() if p.kind is p.KEYWORD_ONLY} - {"device"} == set(T.TRACKER_KEYS)
+    # a group's keys are the keyword arguments of the stage it is handed to
+    takes = lambda fn: set(inspect.signature(fn).parameters)
+    from pram_amd.localization import pose, refine
+    assert set(T.OPTION_GROUPS["pose"]) <= takes(pose.estimate_poses) and set(T.OPTION_GROUPS["pose"]) <= takes(refine.refine_by_projection)
+    assert set(T.OPTION_GROUPS["pose"] + T.OPTION_GROUPS["localize"]) <= takes(pose.localize_candidates)
+    assert set(T.OPTION_GROUPS["pose"] + T.OPTION_GROUPS["localize"] + T.OPTION_GROUPS["refine"]) <= takes(refine.localize_and_refine)
+    assert not set(T.OPTION_GROUPS["tracker"]) & takes(refine.localize_and_refine)
+    kw = {k: i for i, k in enumerate(T.TRACKER_KEYS)}
+    g = T.split_options(kw)
+    assert {k: v for d in g.values() for k, v in d.items()} == kw and all(tuple(g[n]) == T.OPTION_GROUPS[n] for n in g)
+    assert T.split_options({"seed": 3, "refine_below": 9}) == {"pose": {"seed": 3}, "localize": {}, "refine": {}, "tracker": {"refine_below": 9}}
+    with pytest.raises(TypeError, match=r"Localizer: unknown arguments \['n_trials', 'seg'\]"):
+        T.split_options({"seg": 1, "n_trials": 2, "seed": 0}, "Localizer")
+    with pytest.raises(TypeError, match="unknown arguments"):
+        L.Localizer(None, None, pre_filtering_th=0.5, n_trials=3)
