@@ -14,6 +14,7 @@ import numpy as np
 SEED = 20240207
 F, ROWS, FRAME_ID0, UNHELD = 12, 300, 100, 999
 SHORT, ROW_LDS = 32, 512      # the kernel's path boundaries (include/pram_hip.h: PRAM_MAPBUILD_SHORT_TRACK, PRAM_MAPBUILD_ROW_LDS)
+IDX_LDS = SHORT * 128      # a longer track keeps its row indices in the workspace (csrc/mapbuild.hip: MB_IDX_LDS)
 VRF_PARAMS = dict(min_obs=120, topk_imgs=5, n_vrf=3, min_cover_ratio=0.9, gain_floor=0.01)
 IGNORED_FRAME, OUTSIDE_FRAME, ZERO_Z_FRAME = 11, 7, 6
 WIDTH, HEIGHT, INTRINSICS = 640, 480, (500.0, 510.0, 320.0, 240.0)
@@ -138,10 +139,14 @@ def find_best_vrf(p3d_id_list, frame_point_ids, point_frames, ignored, min_obs, 
     if len(all_img_ids) == 0:      # :307-309
         trace["fallback"] = len(img_ids_full) > 0
         all_img_ids = img_ids_full
+    trace["n_encountered"], trace["n_eligible"] = len(set(img_ids_full)), len(img_id_obs)
+    trace["n_candidates"] = len(set(all_img_ids))
     p3d_id_array = np.array(p3d_id_list)
     trace["repeated"] = len(set(p3d_id_list)) < len(p3d_id_list)
     img_observations = {}
     for img_id in all_img_ids:      # :313-322
+        if img_id in img_observations:      # the fallback list names a frame once per encounter: the same mask again
+            continue
         mask = np.zeros(len(p3d_id_list), dtype=bool)
         for pid in frame_point_ids[img_id][frame_point_ids[img_id] > 0].tolist():
             found = np.where(p3d_id_array == pid)[0]
@@ -176,6 +181,7 @@ def find_best_vrf(p3d_id_list, frame_point_ids, point_frames, ignored, min_obs, 
         if len(candidates) >= n_vrf:
             trace["stop"] = "n_vrf"
             break
+    trace["n_picks"] = len(candidates)
     return candidates
 
 
@@ -416,4 +422,438 @@ def scene(seed: int = SEED) -> dict:
     s["point_frames"], s["frame_point_ids"] = point_frames, frame_point_ids
     s["vrf"], s["traces"] = select_reference_frames(landmarks, frame_point_ids, point_frames, xyz, ignored, cams, **VRF_PARAMS)
     _scene_cache[seed] = s
+    return s
+
+
+# ------------------------------------------------------------------------------------------------ the sweep scenes
+# The shape classes of mapbuild_vrf_kernel that the scene above does not reach (landmarks of more than 256 points and of whole
+# words, more than 256 frames / eligible frames / candidates, n_vrf = 64, ids at and above 2^32, long and wrapping probe chains,
+# ragged and empty frames), as the kernel's tables built directly: no ReferenceStore, no descriptors.  Which scene reaches which
+# path is asserted from the traces in tests/test_mapbuild_sweep_cpu.py.
+SWEEP_NAMES = ("wide", "fallback_wide", "n_vrf64", "big_ids", "clash", "degenerate")
+SWEEP_PINNED = ("wide", "fallback_wide", "big_ids", "clash")      # gain_floor = 0.01, the value the reference hard-codes
+WIDE_SIZES = (1, 31, 32, 33, 63, 64, 65, 255, 256, 257, 1000, 2049)
+HASH_MUL = 0x9E3779B97F4A7C15
+_M64 = (1 << 64) - 1
+
+
+def hash_id(i: int) -> int:
+    """csrc/mapbuild.hip hash_id: the high word of the 64-bit product."""
+    return (((int(i) & _M64) * HASH_MUL) & _M64) >> 32
+
+
+def probe_walk(ids, h=None):
+    """The kernel's open-addressing insertion of a landmark's ids > 0 into h = 2 n + 1 slots, in list order -> (slot of every
+    distinct id, start slot of every distinct id, number of steps its probe takes).  The set of occupied slots, which is what a
+    lookup's chain length depends on, is the same for every insertion order."""
+    ids = [int(i) for i in ids]
+    h = 2 * len(ids) + 1 if h is None else h
+    table, slot, start, steps = {}, {}, {}, {}
+    for i in ids:
+        if i <= 0 or i in slot:
+            continue
+        s = start[i] = hash_id(i) % h
+        n = 0
+        while s in table:
+            s = 0 if s + 1 == h else s + 1
+            n += 1
+        table[s], slot[i], steps[i] = i, s, n
+    return slot, start, steps
+
+
+def ids_starting_at(slot: int, h: int, count: int, first: int = 1, also=None):
+    """The first `count` ids >= first whose probe starts in `slot` of h slots (and for which `also` holds)."""
+    out, i = [], first
+    while len(out) < count:
+        if hash_id(i) % h == slot and (also is None or also(i)):
+            out.append(i)
+        i += 1
+    return out
+
+
+class _Sweep:
+    """Frames of R[f] rows of which T[f] carry an id > 0 (placed landmark points first, fillers of no landmark after), the rest ids
+    0, -1 and below -1; the point table; the landmarks' lists; cameras that look at the points."""
+
+    def __init__(self, rng, rows, obs, id_base=0):
+        self.rng, self.R, self.T, self.F = rng, [int(r) for r in rows], [int(t) for t in obs], len(rows)
+        assert all(0 <= t <= r for r, t in zip(self.R, self.T))
+        self.row_ids = [[] for _ in range(self.F)]
+        self.table, self.xyz, self.landmarks = {}, {}, []
+        self.id_base, self.next_id, self.next_lack, self.next_fill = id_base, id_base + 1, id_base + 5 * 10 ** 8, id_base + 10 ** 9
+        self.ignored = np.zeros(self.F, dtype=np.int32)
+        self.cams = np.zeros((self.F, 13))
+        for f in range(self.F):
+            q = np.array([1.0, *(0.01 * rng.standard_normal(3))])
+            self.cams[f, 0:4], self.cams[f, 4:7] = q / np.linalg.norm(q), 0.1 * rng.standard_normal(3)
+            self.cams[f, 7:11], self.cams[f, 11], self.cams[f, 12] = INTRINSICS, WIDTH, HEIGHT
+
+    def ids(self, n):
+        out = list(range(self.next_id, self.next_id + n))
+        self.next_id += n
+        return out
+
+    def lacking(self, n):
+        out = list(range(self.next_lack, self.next_lack + n))
+        self.next_lack += n
+        return out
+
+    def place(self, pid, f):
+        if len(self.row_ids[f]) < self.T[f]:
+            self.row_ids[f].append(pid)
+
+    def point(self, pid, listed, carried, z=None):
+        rng = self.rng
+        self.table[pid] = [int(f) for f in listed]
+        self.xyz[pid] = np.array([rng.uniform(-1, 1), rng.uniform(-1, 1), float(z) if z is not None else rng.uniform(5.5, 8.0)])
+        for f in carried:
+            self.place(pid, int(f))
+
+    def scatter(self, own, list_pool, carry_pool, list_k=(2, 6), carry_c=(1, 2), z=None):
+        """Every id of `own`: listed on list_k frames of list_pool and on the carry_c frames of carry_pool whose rows carry it, in
+        a shuffled order, one list in four with its first frame once more at the end."""
+        rng = self.rng
+        for p in own:
+            k, c = int(rng.integers(list_k[0], list_k[1] + 1)), int(rng.integers(carry_c[0], carry_c[1] + 1))
+            listed = rng.choice(list_pool, size=min(k, len(list_pool)), replace=False).tolist()
+            carried = rng.choice(carry_pool, size=min(c, len(carry_pool)), replace=False).tolist()
+            listed += [f for f in carried if f not in listed]
+            rng.shuffle(listed)
+            if rng.random() < 0.25:
+                listed.append(listed[0])
+            self.point(p, listed, carried, z)
+
+    def close(self, pts, repeats=0, id0=False, shuffle=True):
+        """The landmark's list: pts shuffled, `repeats` ids once more at a random position, an id 0."""
+        rng = self.rng
+        pts = [int(p) for p in pts]
+        if shuffle:
+            pts = [pts[i] for i in rng.permutation(len(pts))]
+        for _ in range(repeats):
+            pts.insert(int(rng.integers(len(pts) + 1)), pts[int(rng.integers(len(pts)))])
+        if id0:
+            pts.insert(int(rng.integers(len(pts) + 1)), 0)
+            if 0 not in self.table:
+                self.table[0], self.xyz[0] = [int(rng.integers(self.F))], np.array([0.1, -0.2, 6.0])
+        self.landmarks.append(pts)
+        return pts
+
+    def landmark(self, n, list_pool, carry_pool, list_k=(2, 6), carry_c=(1, 2), lacking=0, repeats=0, id0=False, negative=0, ids=None):
+        """A landmark of n list entries: its own points scattered, `lacking` ids the table does not hold (each on the rows of one
+        frame all the same), `negative` ids below -1, and close()'s extras."""
+        own = list(ids) if ids is not None else self.ids(n - lacking - repeats - int(id0) - negative)
+        assert len(own) + lacking + repeats + int(id0) + negative == n
+        self.scatter(own, list_pool, carry_pool, list_k, carry_c)
+        lack = self.lacking(lacking)
+        for p in lack:
+            self.place(p, int(self.rng.choice(carry_pool)))
+        return self.close(own + lack + [-7 - i for i in range(negative)], repeats, id0)
+
+    def finish(self, params, landmarks=None) -> dict:
+        """The kernel's tables, the restatement's inputs and the restatement's result."""
+        rng, F = self.rng, self.F
+        landmarks = self.landmarks if landmarks is None else landmarks
+        frame_point_ids = []
+        for f in range(F):
+            ids = list(self.row_ids[f])
+            n_pos = sum(1 for p in ids if p > 0)
+            ids += list(range(self.next_fill, self.next_fill + self.T[f] - n_pos))
+            self.next_fill += self.T[f] - n_pos
+            ids += [(0, -1, -1, -5, -1, -123456789012)[i % 6] for i in range(self.R[f] - len(ids))]
+            a = np.array(ids, dtype=np.int64)[rng.permutation(len(ids))] if ids else np.zeros(0, dtype=np.int64)
+            assert len(a) == self.R[f] and int((a > 0).sum()) == self.T[f]
+            frame_point_ids.append(a)
+        frame_off = np.zeros(F + 1, dtype=np.int32)
+        frame_off[1:] = np.cumsum(self.R)
+        pt_ids = np.array(sorted(self.table), dtype=np.int64)
+        raw = []      # the table as the kernel reads it: one list in seven names a frame the map does not hold (-1, F), which it skips
+        for i, p in enumerate(pt_ids.tolist()):
+            lst = list(self.table[p])
+            if i % 7 == 3:
+                lst.insert(int(rng.integers(len(lst) + 1)), -1)
+                lst.insert(int(rng.integers(len(lst) + 1)), F)
+            raw.append(lst)
+        pt_off = np.zeros(len(raw) + 1, dtype=np.int32)
+        pt_off[1:] = np.cumsum([len(v) for v in raw])
+        s = {"F": F, "frame_off": frame_off, "point3D_ids": np.concatenate(frame_point_ids) if F else np.zeros(0, dtype=np.int64),
+             "pt_ids": pt_ids, "pt_off": pt_off, "pt_frames": np.array([f for v in raw for f in v], dtype=np.int32),
+             "pt_xyz": np.array([self.xyz[p] for p in pt_ids.tolist()], dtype=np.float64).reshape(-1, 3), "cams": self.cams,
+             "ignored": self.ignored, "landmarks": [list(v) for v in landmarks], "params": dict(params),
+             "frame_point_ids": frame_point_ids, "point_frames": self.table, "xyz": self.xyz}
+        s["vrf"], s["traces"] = select_reference_frames(s["landmarks"], frame_point_ids, self.table, self.xyz, self.ignored, self.cams, **params)
+        return s
+
+
+def _ragged(rng, n_big, n_small, lo=130, hi=400):
+    """n_big frames that reach min_obs = 120 (lo .. hi rows, at least 120 of them with an id > 0), then n_small that do not: 0 to
+    119 rows, the first three of 0, 10 and 63 rows, and ten of 300 rows that carry few ids."""
+    R = np.concatenate([rng.integers(lo, hi + 1, n_big), rng.integers(0, 120, n_small)])
+    T = np.concatenate([[int(rng.integers(120, r - 1)) for r in R[:n_big]], (R[n_big:] * rng.uniform(0.3, 1.0, n_small)).astype(np.int64)])
+    R[n_big:n_big + 3], T[n_big:n_big + 3] = (0, 10, 63), (0, 7, 40)
+    R[n_big + 3:n_big + 13], T[n_big + 3:n_big + 13] = 300, rng.integers(50, 120, 10)
+    return R, T.astype(np.int64)
+
+
+WIDE_IGNORED, WIDE_AWAY, WIDE_DEPTH0, WIDE_LACK_ONLY, WIDE_RESERVED = (0, 1, 2), 5, 6, 7, 8
+WIDE_PARAMS = dict(min_obs=120, topk_imgs=260, n_vrf=10, min_cover_ratio=0.9, gain_floor=0.01)
+WIDE_LM_EMPTY, WIDE_LM_DROPS = 3, 10      # positions in the scene's landmarks
+
+
+def _wide(rng):
+    n_big, F = 340, 600
+    R, T = _ragged(rng, n_big, F - n_big)
+    R[:WIDE_RESERVED], T[:WIDE_RESERVED] = 400, 380
+    w = _Sweep(rng, R, T)
+    w.ignored[list(WIDE_IGNORED)] = 1
+    w.cams[WIDE_AWAY, 0:7] = [1, 0, 0, 0, 100.0, 0, 0]      # every point far to the side of the image
+    w.cams[WIDE_DEPTH0, 0:7] = [1, 0, 0, 0, 0, 0, -5.0]      # the points at z = 5 at depth 0 exactly
+    big, small = np.arange(WIDE_RESERVED, n_big), np.arange(n_big, F)
+    both, ign = np.concatenate([big, small]), np.array(WIDE_IGNORED)
+    pool = lambda n: rng.choice(big, size=n, replace=False)
+    # 1 point: one pick covers it
+    w.landmark(1, pool(1), big[:1], list_k=(1, 1), carry_c=(1, 1))
+    # 31: two frames of ten points each, then no candidate is left
+    a, two = w.ids(31), pool(2)
+    for i, p in enumerate(a):
+        w.point(p, [two[0], two[1]], [two[i // 10]] if i < 20 else [])
+    w.close(a, shuffle=False)
+    w.landmark(32, pool(6), pool(3), carry_c=(1, 2))
+    w.close([])
+    w.landmark(33, pool(8), pool(4), lacking=2, repeats=2, id0=True)
+    w.landmark(63, pool(12), pool(5))
+    w.landmark(64, pool(12), pool(5), repeats=1)
+    w.landmark(65, pool(12), pool(5), lacking=1)
+    w.landmark(255, np.concatenate([pool(40), small[:40], ign]), np.concatenate([pool(12), ign]), repeats=2)
+    w.landmark(256, pool(60), pool(40), carry_c=(1, 1))      # about six points a frame: ten picks do not cover it
+    # 257: the frame with the largest gain carries only ids the table lacks (no point to project), the next two see every point
+    # outside the image or at depth 0; 56 ordinary points and a repeat
+    p6, lack = pool(6), w.lacking(100)
+    for p in lack:
+        w.place(p, WIDE_LACK_ONLY)
+    away, depth0, rest = w.ids(60), w.ids(40), w.ids(56)
+    for p in away:
+        w.point(p, [WIDE_AWAY] + pool(2).tolist(), [WIDE_AWAY])
+    for p in depth0:
+        w.point(p, [int(pool(1)[0]), WIDE_DEPTH0], [WIDE_DEPTH0], z=5.0)
+    w.scatter(rest, np.concatenate([pool(20), [WIDE_LACK_ONLY]]), p6, carry_c=(1, 1))
+    w.table[rest[0]].append(WIDE_LACK_ONLY)
+    w.close(lack + away + depth0 + rest, repeats=1)
+    w.landmark(1000, pool(250), pool(200), carry_c=(1, 1), lacking=3, repeats=3)      # about five points a frame: below the gain floor
+    w.landmark(2049, np.concatenate([both, ign]), np.concatenate([pool(40), ign]), list_k=(3, 7), lacking=5, repeats=5, negative=2)
+    assert [len(v) for v in w.landmarks if len(v)] == list(WIDE_SIZES) and w.landmarks[WIDE_LM_EMPTY] == []
+    return w.finish(WIDE_PARAMS)
+
+
+def _fallback_wide(rng):
+    F = 420
+    R = rng.integers(0, 401, F)
+    R[:3] = (0, 5, 400)
+    T = (R * rng.uniform(0.4, 1.0, F)).astype(np.int64)
+    w = _Sweep(rng, R, T)
+    w.ignored[[7, 8]] = 1
+    every = np.arange(F)
+    w.landmark(20, rng.choice(every, 5, replace=False), rng.choice(every[R > 50], 3, replace=False))
+    w.landmark(300, rng.choice(every, 150, replace=False), rng.choice(every[R > 100], 20, replace=False), repeats=2)
+    w.close([])
+    w.landmark(700, every, rng.choice(every[R > 100], 30, replace=False), list_k=(3, 7), lacking=4, repeats=3)
+    return w.finish(dict(min_obs=int(R.max()) + 1, topk_imgs=3, n_vrf=10, min_cover_ratio=0.9, gain_floor=0.01))
+
+
+def _n_vrf64(rng):
+    n_big, F = 300, 330
+    R, T = _ragged(rng, n_big, F - n_big)
+    w = _Sweep(rng, R, T)
+    big = np.arange(n_big)
+    pool = lambda n: rng.choice(big, size=n, replace=False)
+    w.landmark(40, pool(10), pool(4), repeats=1)      # ten candidates: the four that carry points, then picks of gain 0
+    w.landmark(300, pool(120), pool(100), carry_c=(1, 1), repeats=2)
+    w.close([])
+    w.landmark(700, np.arange(F), pool(150), list_k=(3, 7), carry_c=(1, 1), repeats=3, lacking=2)
+    return w.finish(dict(min_obs=120, topk_imgs=257, n_vrf=64, min_cover_ratio=1.0, gain_floor=0.0))
+
+
+BIG_ID_BASE = (1 << 40) + 12345
+BIG_LM_PAIRS = 0
+
+
+def _big_ids(rng):
+    n_big, F = 30, 44
+    R, T = _ragged(rng, n_big, F - n_big, 130, 300)
+    w = _Sweep(rng, R, T, id_base=BIG_ID_BASE)
+    big = np.arange(n_big)
+    # five pairs id, id + 2^32 in a list of 15.  The two hashes differ by the multiplier's low word, which 2 * 15 + 1 = 31 divides:
+    # both probes start in the same slot.  Compared on 32 bits one half answers for the other, whichever of them took the slot
+    # first, and frames X and Y get the same mask.  As it is: W (6), Y (5), X (3) cover 14 of 15.  With equal masks the second of X
+    # and Y gains nothing and V (1) goes before it.
+    X, Y, W, V = 3, 4, 5, 6
+    same_slot = lambda i: hash_id(i) + (HASH_MUL & 0xffffffff) < (1 << 32) and hash_id(i) % 31 == hash_id(i + (1 << 32)) % 31
+    a = [i for i in range(BIG_ID_BASE + 1, BIG_ID_BASE + 200) if same_slot(i)][:5]
+    b = [i + (1 << 32) for i in a]
+    assert len(a) == 5
+    w.next_id = max(b) + 1
+    c = w.ids(5)
+    for i, p in enumerate(a):
+        w.point(p, [X, Y, W], [X, W] if i < 2 else [X])
+    for p in b:
+        w.point(p, [Y, W, X], [Y])
+    for i, p in enumerate(c):
+        w.point(p, [W, X] if i < 4 else [V, W], [W] if i < 4 else [V])
+    w.close(a + b + c, shuffle=False)
+    w.close([])
+    w.landmark(50, rng.choice(big, 8, replace=False), rng.choice(big, 4, replace=False), lacking=2, repeats=1, negative=2)
+    w.landmark(300, np.arange(F), rng.choice(big, 25, replace=False), repeats=2, negative=1)
+    return w.finish(dict(min_obs=120, topk_imgs=20, n_vrf=10, min_cover_ratio=0.9, gain_floor=0.01))
+
+
+def truncated_ids(s: dict):
+    """The restatement on the scene with every id > 0 cut to its low 32 bits: what a 32-bit comparison would compute."""
+    cut = lambda i: int(i) & 0xffffffff if i > 0 else int(i)
+    rows = [np.where(a > 0, a & 0xffffffff, a) for a in s["frame_point_ids"]]
+    table, xyz = {}, {}
+    for p, v in s["point_frames"].items():
+        table.setdefault(cut(p), v)
+        xyz.setdefault(cut(p), s["xyz"][p])
+    return select_reference_frames([[cut(p) for p in v] for v in s["landmarks"]], rows, table, xyz, s["ignored"], s["cams"], **s["params"])
+
+
+CLASH_SLOT, CLASH_N, CLASH_LM, CLASH_LM_SEQUENTIAL = 71, 40, 0, 1
+
+
+def _clash(rng):
+    n_big, F = 24, 38
+    R, T = _ragged(rng, n_big, F - n_big, 130, 300)
+    w = _Sweep(rng, R, T)
+    big = np.arange(n_big)
+    # 40 ids whose probes all start in slot 71 of the 81: the chain runs to the table's end and on from slot 0
+    w.landmark(CLASH_N, rng.choice(big, 10, replace=False), rng.choice(big, 5, replace=False), ids=ids_starting_at(CLASH_SLOT, 2 * CLASH_N + 1, CLASH_N))
+    w.next_id = 10 ** 6
+    w.landmark(40, rng.choice(big, 10, replace=False), rng.choice(big, 5, replace=False))
+    w.landmarks[CLASH_LM_SEQUENTIAL].sort()
+    return w.finish(dict(min_obs=120, topk_imgs=20, n_vrf=10, min_cover_ratio=0.9, gain_floor=0.01))
+
+
+def _degenerate(rng):
+    """Separate small calls, under "calls": every landmark empty, one frame, min_cover_ratio 0, topk_imgs 1, n_vrf 1."""
+    base = dict(min_obs=120, topk_imgs=20, n_vrf=10, min_cover_ratio=0.9, gain_floor=0.01)
+
+    def small(F, sizes):
+        R, T = rng.integers(150, 300, F), rng.integers(120, 150, F)
+        w = _Sweep(rng, R, T)
+        for n in sizes:
+            w.landmark(n, np.arange(F), np.arange(F), list_k=(1, 3)) if n else w.close([])
+        return w
+
+    calls = {"all_empty": small(6, []).finish(base, [[], [], []]), "F1": small(1, [10, 0, 40]).finish(base)}
+    for name, change in (("cover0", dict(min_cover_ratio=0.0)), ("topk1", dict(topk_imgs=1)), ("n_vrf1", dict(n_vrf=1))):
+        calls[name] = small(6, [5, 40, 0, 70]).finish({**base, **change})
+    return {"calls": calls}
+
+
+_SWEEPS = {"wide": _wide, "fallback_wide": _fallback_wide, "n_vrf64": _n_vrf64, "big_ids": _big_ids, "clash": _clash,
+           "degenerate": _degenerate}
+_sweep_cache = {}
+
+
+def sweep_scene(name: str, seed: int = SEED) -> dict:
+    """One sweep scene (cached; treat as read-only): the kernel's tables as numpy arrays (point3D_ids, frame_off, pt_ids, pt_off,
+    pt_frames, pt_xyz, cams, ignored), the landmarks' lists, the parameters, the restatement's inputs (frame_point_ids,
+    point_frames, xyz) and its results (vrf, traces).  "degenerate" holds several such dicts under "calls"."""
+    if (name, seed) not in _sweep_cache:
+        _sweep_cache[(name, seed)] = _SWEEPS[name](np.random.default_rng([seed, SWEEP_NAMES.index(name)]))
+    return _sweep_cache[(name, seed)]
+
+
+def sweep_calls(name: str, seed: int = SEED) -> dict:
+    """tag -> one call's scene dict, for every scene alike."""
+    s = sweep_scene(name, seed)
+    return s["calls"] if "calls" in s else {name: s}
+
+
+def filter_verdicts(s: dict) -> list:
+    """The projection filter's verdict on every chosen frame that carries a point of the list: (landmark, frame, kept, decisive).
+    Decisive: the verdict does not hang on the last bit of the projection.  A kept frame has a point inside the image that is more
+    than 1e-6 px from every border at a depth of at least 1e-6; every point of a dropped frame is as far outside, or sits at depth
+    0 exactly under an identity rotation, where the sum has one nonzero term besides the translation and no order to differ in."""
+    out = []
+    for l, (pts, trace) in enumerate(zip(s["landmarks"], s["traces"])):
+        for f in trace.get("chosen", []):
+            on_rows = set(s["frame_point_ids"][f].tolist())
+            sel = [p for p in pts if p >= 0 and p in s["point_frames"] and p in on_rows]
+            if not sel:
+                continue
+            cam = s["cams"][f]
+            k = reproject(cam, np.array([s["xyz"][p] for p in sel]))
+            u, v, z = k[:, 0], k[:, 1], k[:, 2]
+            inside = (u >= 0) & (u < cam[11]) & (v >= 0) & (v < cam[12])
+            with np.errstate(invalid="ignore"):
+                margin = np.minimum(np.minimum(np.abs(u), np.abs(u - cam[11])), np.minimum(np.abs(v), np.abs(v - cam[12])))
+                firm = np.isfinite(u) & np.isfinite(v) & (np.abs(z) >= 1e-6) & (margin > 1e-6)
+            exact0 = (z == 0.0) & bool((cam[0:4] == (1, 0, 0, 0)).all())
+            kept = bool(inside.any())
+            out.append((l, f, kept, bool((inside & firm).any()) if kept else bool((firm | exact0).all())))
+    return out
+
+
+# ------------------------------------------------------------------------------------------------ the long tracks (stage 1)
+LT_F, LT_ROWS = 20, 300
+_long_cache = {}
+
+
+def long_track_scene(seed: int = SEED) -> dict:
+    """Tracks beyond IDX_LDS entries (row indices in the workspace), and dropped entries in the workspace Gram row (cached; treat as
+    read-only).  "special": name -> track index; "n_prefix": the number of leading tracks whose last is a long one, so that the
+    tables cut there end with the workspace (desc_long_end == E), while the whole tables have short tracks beyond it."""
+    if seed in _long_cache:
+        return _long_cache[seed]
+    rng = np.random.default_rng([seed, 77])
+    n_rows = LT_F * LT_ROWS
+    frame_off = np.arange(LT_F + 1, dtype=np.int32) * LT_ROWS
+    centres = rng.standard_normal((8, 128))
+    centres /= np.linalg.norm(centres, axis=1, keepdims=True)
+    d = centres[np.arange(n_rows) % 8] + 0.6 * rng.standard_normal((n_rows, 128))
+    descriptors = (d / np.linalg.norm(d, axis=1, keepdims=True)).astype(np.float32)
+    dropped = lambda i: ((-1, 3), (LT_F, 0), (i % LT_F, LT_ROWS), (LT_F + 3, 5), (i % LT_F, LT_ROWS + 7), (i % LT_F, -1), (-7, 0))[i % 7]
+    tracks, special = [], {}
+
+    def add(name, length, kept_pos, rows):
+        fr, kp = np.zeros(length, dtype=np.int32), np.zeros(length, dtype=np.int32)
+        for i in range(length):
+            fr[i], kp[i] = dropped(i)
+        for i, r in zip(kept_pos, rows):
+            fr[i], kp[i] = int(r) // LT_ROWS, int(r) % LT_ROWS
+        if name:
+            special[name] = len(tracks)
+        tracks.append((fr, kp))
+
+    def short(count):
+        for n in rng.integers(2, 21, size=count).tolist():
+            add(None, n, range(n), rng.choice(n_rows, n, replace=False))
+
+    def sparse(name, length, n_kept, fixed):
+        free = np.setdiff1d(np.arange(length), fixed)
+        pos = np.sort(np.concatenate([fixed, rng.choice(free, n_kept - len(fixed), replace=False)]))
+        add(name, length, pos.tolist(), rng.choice(n_rows, n_kept, replace=False))
+
+    short(5)
+    sparse("len4095", 4095, 47, [0, 4094])
+    sparse("len4096", 4096, 48, [0, 4095])
+    short(2)
+    sparse("len4097", 4097, 48, [0, 4095, 4096])
+    sparse("len5000", 5000, 47, [0, 4090, 4095, 4096, 4100, 4999])
+    for n in (600, 513, 512):      # a third dropped: NaN in the Gram row, in the workspace (600, 513) and in LDS (512)
+        pos = [i for i in range(n) if i % 3 != 1]
+        add(f"len{n}_dropped", n, pos, rng.choice(n_rows, len(pos), replace=False))
+    rows = rng.choice(n_rows, 60, replace=False)
+    rows[41] = rows[9]      # a bit-identical repeat among the kept rows: equal medians, the lower position wins
+    sparse_pos = np.sort(rng.choice(700, 60, replace=False))
+    add("repeat_long", 700, sparse_pos.tolist(), rows)
+    n_prefix = len(tracks)
+    short(4)
+    trk_off = np.zeros(len(tracks) + 1, dtype=np.int32)
+    trk_off[1:] = np.cumsum([len(t[0]) for t in tracks])
+    s = {"descriptors": descriptors, "frame_off": frame_off, "n_frames": LT_F, "n_rows": n_rows, "trk_off": trk_off,
+         "trk_frame": np.concatenate([t[0] for t in tracks]), "trk_kpt": np.concatenate([t[1] for t in tracks]), "special": special,
+         "n_prefix": n_prefix}
+    s["choice"], s["desc"], s["medians"] = assign_point_descriptors(descriptors, frame_off, trk_off, s["trk_frame"], s["trk_kpt"])
+    _long_cache[seed] = s
     return s
