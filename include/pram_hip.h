@@ -1077,6 +1077,77 @@ int pram_kmeans_lloyd(const double* x, long long n, int k, double* centers, doub
 /* One assignment step: labels [n] int32 and dist [n] float64 of x against centers [k][3].  Needs no workspace. */
 int pram_kmeans_assign(const double* x, long long n, const double* centers, int k, int* labels, double* dist, void* stream);
 
+/* ---- triangulation (csrc/triangulate.hip): a map's points from pairwise matches and known poses ------------------------------
+ * What localization/triangulation.py of the reference does with COLMAP: verify every pair's matches against the epipolar geometry
+ * of the two known poses, join the kept matches into tracks, triangulate every track.  NOT COLMAP's incremental triangulator: a
+ * batched one with fixed budgets (DESIGN.md 4.21 lists the deviations).  float64; nothing here has been timed.
+ *
+ * The stages share one frame table, laid out as the store's: keypoints [n_rows][2] float32 of all frames concatenated, frame_off
+ * [n_frames + 1] int32; a "row" is a keypoint's index in it.  Cameras are per frame: cam_model [n_frames] (PRAM_CAM_*), cam_params
+ * [n_frames][PRAM_POSE_CAM_PARAMS], cam_model_host a HOST copy the launcher validates (PRAM_E_UNSUPPORTED).  Poses are
+ * cam_from_world: qvec [n_frames][4] (w, x, y, z; normalised inside), tvec [n_frames][3].  Every entry refuses (PRAM_E_ARG) a null
+ * or misaligned pointer (float64 buffers 8 bytes, int32 4) and a negative size; none waits for the stream; a buffer of zero
+ * logical length still needs a valid pointer. */
+#define PRAM_TRI_GN_STEPS 5            /* Gauss-Newton steps of the point-only refit */
+#define PRAM_TRI_FRAME_COLS 16         /* R [9] row-major, t [3], C = -R^T t [3], mean focal length */
+#define PRAM_TRI_CC_STATE_WORDS 4      /* hooked this round, done, rounds run, spare */
+
+/* table [n_frames][PRAM_TRI_FRAME_COLS]: what verification and triangulation read of a frame's pose and camera. */
+int pram_tri_frames(const double* qvec, const double* tvec, const int* cam_model, const double* cam_params,
+                    const int* cam_model_host, int n_frames, double* table, void* stream);
+
+/* norm [n_rows][2]: every keypoint (x + pixel_offset, y + pixel_offset) through its frame's inverse camera model, with
+ * pram_pose_prepare's undistortion (PRAM_POSE_UNDISTORT_STEPS Newton steps).  The reference verifies with offset 0 and
+ * triangulates with offset 0.5. */
+int pram_tri_normalize(const float* keypoints, const int* frame_off, const int* cam_model, const double* cam_params,
+                       const int* cam_model_host, int n_frames, int n_rows, double pixel_offset, double* norm, void* stream);
+
+/* pairs [n_pairs][2] frame indices; match_off [n_pairs + 1] and matches [n_matches][2] (keypoint index in frame 0, in frame 1):
+ * the matches of every pair as CSR.  E = [t / |t|]x R of cam1_from_cam0; a match is kept when its two epipolar errors
+ * (colmap_utils/geometry.py compute_epipolar_errors) are <= max_error / mean focal length of their frame.  keep [n_matches]: the
+ * mask; kept [n_matches][2]: the kept matches of pair p in their original order from match_off[p] on, count [n_pairs] of them;
+ * edges [n_matches][2]: the rows a kept match joins, (-1, -1) for a dropped one.  A match with an index outside its frame, and
+ * every match of a pair that names a frame outside the table, is dropped without being dereferenced. */
+int pram_tri_verify(const double* norm, const int* frame_off, const int* pairs, const int* match_off, const int* matches,
+                    const double* table, int n_frames, int n_pairs, int n_matches, double max_error, unsigned char* keep,
+                    int* kept, int* edges, int* count, void* stream);
+
+/* Connected components over the rows with `edges` [n_edges][2] (an edge with an end outside [0, n_rows) is ignored): rounds
+ * first_round .. first_round + n_rounds - 1 of (hook the larger root to the smaller with an atomic min; jump every pointer to its
+ * root; close the round), three launches each.  first_round == 0 sets label[i] = i and clears state
+ * [PRAM_TRI_CC_STATE_WORDS] (device): [0] hooked this round, [1] done, [2] rounds run.  Once done is set the launches of later
+ * rounds return at once, so a caller enqueues rounds in groups and reads state[1] once per group.  At the end label[i] is the
+ * smallest row of i's component, whatever order the atomics landed in.  n_rows <= 2^30, n_rounds <= 1024. */
+int pram_tri_components(const int* edges, int n_edges, int n_rows, int first_round, int n_rounds, int* label, int* state,
+                        void* stream);
+
+/* The tracks of `label` as CSR: a track is a component of two rows or more, tracks in ascending label, entries in ascending row.
+ * trk_off [n_rows / 2 + 2], trk_label [n_rows / 2 + 1], trk_row / trk_frame / trk_kpt [n_rows] are sized for the worst case;
+ * sizes [2] (device) = (tracks, entries) says how much of them is written.  Counts, a scan over the labels, a cursor fill and a
+ * bitonic sort of every track by one wave, in place: no cap on a track's length.  workspace: 256-byte aligned. */
+size_t pram_tri_tracks_workspace_bytes(int n_rows);
+int pram_tri_tracks(const int* label, const int* frame_off, int n_frames, int n_rows, void* workspace, size_t workspace_bytes,
+                    int* trk_off, int* trk_label, int* trk_row, int* trk_frame, int* trk_kpt, int* sizes, void* stream);
+
+/* One wave per track (trk_off [n_tracks + 1], trk_label [n_tracks], trk_row / trk_frame [n_entries]; norm: pram_tri_normalize
+ * with the offset 0.5).  Hypotheses: every pair of entries in lexicographic order when there are at most `trials`, else `trials`
+ * pairs from the pose stage's sampler keyed by (seed, trk_label, trial), smaller entry first; a pair of one frame is skipped.  A
+ * hypothesis is the midpoint of the two rays, refused when a depth is not positive or the rays meet below min_tri_angle
+ * (radians); its score is the number of entries with positive depth and a reprojection error (pixels, full camera model, keypoint
+ * + 0.5) <= max_reproj_error, which must be 2 at least; most inliers win, then the smaller sum of squared errors, then the lower
+ * index (best [n_tracks], -1: none).  Refit on the winner's inliers: the least-squares point of their rays, then
+ * PRAM_TRI_GN_STEPS Gauss-Newton steps on the pixel error (a step that is not finite or not positive definite is not taken).
+ * Inliers are marked again at the refit point; of a frame's several inliers the one with the smallest error stays, the lowest
+ * row on a tie.  accept [n_tracks]: two kept entries at least and some two of them seeing the point under min_tri_angle or
+ * more; xyz [n_tracks][3]; error [n_tracks]: the mean reprojection error of the kept entries; kept [n_tracks]: their number;
+ * entry_keep [n_entries] uint8; entry_error [n_entries]: the final inliers' error in pixels, -1 for the others.  An entry naming
+ * a row or frame outside the tables is never an inlier. */
+int pram_tri_triangulate(const double* norm, const float* keypoints, const double* table, const int* cam_model,
+                         const double* cam_params, const int* trk_off, const int* trk_label, const int* trk_row,
+                         const int* trk_frame, int n_tracks, int n_entries, int n_frames, int n_rows, int trials,
+                         unsigned long long seed, double min_tri_angle, double max_reproj_error, int* accept, double* xyz,
+                         double* error, int* kept, int* best, unsigned char* entry_keep, double* entry_error, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -136,6 +136,13 @@ _SIGS = {
     "pram_kmeans_init_pp": (I, [P, LL, I, I, P, I, P, SZ, P, P, P]),
     "pram_kmeans_lloyd": (I, [P, LL, I, P, C.c_double, I, I, I, I, P, SZ, P, P, P, P, P]),
     "pram_kmeans_assign": (I, [P, LL, P, I, P, P, P]),
+    "pram_tri_frames": (I, [P, P, P, P, P, I, P, P]),
+    "pram_tri_normalize": (I, [P, P, P, P, P, I, I, C.c_double, P, P]),
+    "pram_tri_verify": (I, [P, P, P, P, P, P, I, I, I, C.c_double, P, P, P, P, P]),
+    "pram_tri_components": (I, [P, I, I, I, I, P, P, P]),
+    "pram_tri_tracks_workspace_bytes": (SZ, [I]),
+    "pram_tri_tracks": (I, [P, P, I, I, P, SZ, P, P, P, P, P, P, P]),
+    "pram_tri_triangulate": (I, [P, P, P, P, P, P, P, P, P, I, I, I, I, I, C.c_ulonglong, C.c_double, C.c_double, P, P, P, P, P, P, P, P]),
 }
 
 

@@ -1,0 +1,49 @@
+// What the float64 geometry kernels share (pose.hip, triangulate.hip): COLMAP's camera models unified to OPENCV, its distortion
+// function and Jacobian, the butterfly sum of a wave and the counter-based sampler's mixing function.
+#pragma once
+#include "common.h"
+
+struct Cam { double fx, fy, cx, cy, k1, k2, p1, p2; };
+
+// every supported model is OPENCV with some coefficients zero (COLMAP's parameter order)
+__device__ __forceinline__ Cam cam_unify(int model, const double* __restrict__ p) {
+    Cam c;
+    switch (model) {
+        case PRAM_CAM_PINHOLE: c = {p[0], p[1], p[2], p[3], 0.0, 0.0, 0.0, 0.0}; break;
+        case PRAM_CAM_SIMPLE_RADIAL: c = {p[0], p[0], p[1], p[2], p[3], 0.0, 0.0, 0.0}; break;
+        case PRAM_CAM_RADIAL: c = {p[0], p[0], p[1], p[2], p[3], p[4], 0.0, 0.0}; break;
+        case PRAM_CAM_OPENCV: c = {p[0], p[1], p[2], p[3], p[4], p[5], p[6], p[7]}; break;
+        default: c = {p[0], p[0], p[1], p[2], 0.0, 0.0, 0.0, 0.0}; break;      // PRAM_CAM_SIMPLE_PINHOLE
+    }
+    return c;
+}
+
+__device__ __forceinline__ void distort(const Cam& c, double u, double v, double& ud, double& vd) {
+    const double r2 = u * u + v * v;
+    const double rad = c.k1 * r2 + c.k2 * r2 * r2;
+    const double du = u * rad + 2.0 * c.p1 * u * v + c.p2 * (r2 + 2.0 * u * u);
+    const double dv = v * rad + 2.0 * c.p2 * u * v + c.p1 * (r2 + 2.0 * v * v);
+    ud = u + du; vd = v + dv;
+}
+
+__device__ __forceinline__ void distort_jac(const Cam& c, double u, double v, double& j11, double& j12, double& j22) {
+    const double r2 = u * u + v * v;
+    const double rad = c.k1 * r2 + c.k2 * r2 * r2;
+    const double dr = c.k1 + 2.0 * c.k2 * r2;
+    j11 = 1.0 + rad + 2.0 * u * u * dr + 2.0 * c.p1 * v + 6.0 * c.p2 * u;
+    j12 = 2.0 * u * v * dr + 2.0 * c.p1 * u + 2.0 * c.p2 * v;
+    j22 = 1.0 + rad + 2.0 * v * v * dr + 2.0 * c.p2 * u + 6.0 * c.p1 * v;
+}
+
+__device__ __forceinline__ double wave_sum_f64(double v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+
+__device__ __forceinline__ unsigned long long sm64(unsigned long long x) {
+    x += 0x9E3779B97F4A7C15ull;
+    x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
+    x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
+    return x ^ (x >> 31);
+}

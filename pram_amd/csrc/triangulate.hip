@@ -1,0 +1,649 @@
+// A map's points from pairwise matches and known poses (what localization/triangulation.py of the reference hands to COLMAP):
+// normalised keypoints, the epipolar test of every match, connected components over the kept matches, the CSR table of tracks and
+// one robust multi-view solve per track.  float64 throughout; every sum runs per lane in ascending entry order and is combined by
+// the butterfly of wave_sum_f64, so a result does not depend on the launch or the run.  DESIGN.md 4.21 has the formulas and the
+// deviations from COLMAP's incremental triangulator.
+#include "camera.h"
+#include "glue.h"
+#include <math.h>
+
+namespace {
+
+constexpr int UNDISTORT_STEPS = PRAM_POSE_UNDISTORT_STEPS;
+constexpr int GN_STEPS = PRAM_TRI_GN_STEPS;
+constexpr int FC = PRAM_TRI_FRAME_COLS;      // R [9] row-major, t [3], C = -R^T t [3], mean focal length
+constexpr int SCAN = 256;                    // rows per block of the scan over labels
+
+// the frame f with frame_off[f] <= r < frame_off[f + 1] (frames may be empty); 32 steps cover every n_frames an int holds
+__device__ __forceinline__ int frame_of_row(const int* __restrict__ frame_off, int n_frames, int r) {
+    int lo = 0, hi = n_frames - 1;
+    for (int it = 0; it < 32 && lo < hi; ++it) {
+        const int mid = lo + ((hi - lo) >> 1);
+        if (frame_off[mid + 1] <= r) lo = mid + 1; else hi = mid;
+    }
+    return lo;
+}
+
+// ---------------------------------------------------------------- the frame table
+__global__ __launch_bounds__(64) void tri_frames_kernel(const double* __restrict__ qvec, const double* __restrict__ tvec,
+                                                        const int* __restrict__ cam_model, const double* __restrict__ cam_params, int n_frames,
+                                                        double* __restrict__ table) {
+    const int f = blockIdx.x * 64 + threadIdx.x;
+    if (f >= n_frames) return;
+    const double* q = qvec + (size_t)f * 4;
+    const double nq = sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
+    const double qw = q[0] / nq, qx = q[1] / nq, qy = q[2] / nq, qz = q[3] / nq;
+    const double tx = tvec[(size_t)f * 3], ty = tvec[(size_t)f * 3 + 1], tz = tvec[(size_t)f * 3 + 2];
+    double* T = table + (size_t)f * FC;
+    T[0] = 1.0 - 2.0 * qy * qy - 2.0 * qz * qz; T[1] = 2.0 * qx * qy - 2.0 * qw * qz; T[2] = 2.0 * qz * qx + 2.0 * qw * qy;
+    T[3] = 2.0 * qx * qy + 2.0 * qw * qz; T[4] = 1.0 - 2.0 * qx * qx - 2.0 * qz * qz; T[5] = 2.0 * qy * qz - 2.0 * qw * qx;
+    T[6] = 2.0 * qz * qx - 2.0 * qw * qy; T[7] = 2.0 * qy * qz + 2.0 * qw * qx; T[8] = 1.0 - 2.0 * qx * qx - 2.0 * qy * qy;
+    T[9] = tx; T[10] = ty; T[11] = tz;
+    T[12] = -(T[0] * tx + T[3] * ty + T[6] * tz);
+    T[13] = -(T[1] * tx + T[4] * ty + T[7] * tz);
+    T[14] = -(T[2] * tx + T[5] * ty + T[8] * tz);
+    const Cam c = cam_unify(cam_model[f], cam_params + (size_t)f * PRAM_POSE_CAM_PARAMS);
+    T[15] = (c.fx + c.fy) / 2.0;
+}
+
+// ---------------------------------------------------------------- normalise: pixels -> normalised camera plane, once per table
+__global__ __launch_bounds__(256) void tri_normalize_kernel(const float* __restrict__ kpts, const int* __restrict__ frame_off,
+                                                            const int* __restrict__ cam_model, const double* __restrict__ cam_params,
+                                                            int n_frames, int n_rows, double off, double* __restrict__ norm) {
+    const int r = blockIdx.x * 256 + threadIdx.x;
+    if (r >= n_rows) return;
+    const int f = frame_of_row(frame_off, n_frames, r);
+    const Cam c = cam_unify(cam_model[f], cam_params + (size_t)f * PRAM_POSE_CAM_PARAMS);
+    const double xd = (((double)kpts[(size_t)r * 2] + off) - c.cx) / c.fx, yd = (((double)kpts[(size_t)r * 2 + 1] + off) - c.cy) / c.fy;
+    double u = xd, v = yd;
+    for (int it = 0; it < UNDISTORT_STEPS; ++it) {
+        double fu, fv, j11, j12, j22;
+        distort(c, u, v, fu, fv);
+        fu -= xd; fv -= yd;
+        distort_jac(c, u, v, j11, j12, j22);
+        const double det = j11 * j22 - j12 * j12;
+        if (fabs(det) > 1e-12) {
+            const double su = (j22 * fu - j12 * fv) / det, sv = (j11 * fv - j12 * fu) / det;
+            u -= su; v -= sv;
+        }
+    }
+    norm[(size_t)r * 2] = u; norm[(size_t)r * 2 + 1] = v;
+}
+
+// ---------------------------------------------------------------- verify: one workgroup per pair, ordered compaction
+__global__ __launch_bounds__(256) void tri_verify_kernel(const double* __restrict__ norm, const int* __restrict__ frame_off,
+                                                         const int* __restrict__ pairs, const int* __restrict__ m_off,
+                                                         const int* __restrict__ matches, const double* __restrict__ table, int n_frames,
+                                                         int n_matches, double max_error, unsigned char* __restrict__ keep,
+                                                         int* __restrict__ kept, int* __restrict__ edges, int* __restrict__ count) {
+    __shared__ int wsum[4];
+    const int p = blockIdx.x, tid = threadIdx.x;
+    const int f0 = pairs[(size_t)p * 2], f1 = pairs[(size_t)p * 2 + 1];
+    int m0 = m_off[p], m1 = m_off[p + 1];
+    m0 = m0 < 0 ? 0 : (m0 > n_matches ? n_matches : m0);
+    m1 = m1 < m0 ? m0 : (m1 > n_matches ? n_matches : m1);
+    const bool okp = f0 >= 0 && f0 < n_frames && f1 >= 0 && f1 < n_frames;      // uniform
+    int r0 = 0, r1 = 0, n0 = 0, n1 = 0;
+    double E[9], th0 = 0.0, th1 = 0.0;
+#pragma unroll
+    for (int a = 0; a < 9; ++a) E[a] = 0.0;
+    if (okp) {
+        r0 = frame_off[f0]; n0 = frame_off[f0 + 1] - r0;
+        r1 = frame_off[f1]; n1 = frame_off[f1 + 1] - r1;
+        const double* A = table + (size_t)f0 * FC;
+        const double* B = table + (size_t)f1 * FC;
+        double R[9];      // cam1_from_cam0: R = R1 R0^T, t = t1 - R t0
+        for (int a = 0; a < 3; ++a)
+            for (int c = 0; c < 3; ++c) R[a * 3 + c] = B[a * 3] * A[c * 3] + B[a * 3 + 1] * A[c * 3 + 1] + B[a * 3 + 2] * A[c * 3 + 2];
+        const double tx = B[9] - (R[0] * A[9] + R[1] * A[10] + R[2] * A[11]);
+        const double ty = B[10] - (R[3] * A[9] + R[4] * A[10] + R[5] * A[11]);
+        const double tz = B[11] - (R[6] * A[9] + R[7] * A[10] + R[8] * A[11]);
+        const double nt = sqrt(tx * tx + ty * ty + tz * tz);      // 0: E is NaN, every match of the pair is dropped
+        const double x = tx / nt, y = ty / nt, z = tz / nt;
+        for (int c = 0; c < 3; ++c) {      // E = [t / |t|]x R
+            E[c] = y * R[6 + c] - z * R[3 + c];
+            E[3 + c] = z * R[c] - x * R[6 + c];
+            E[6 + c] = x * R[3 + c] - y * R[c];
+        }
+        th0 = max_error / A[15]; th1 = max_error / B[15];
+    }
+    int base = 0;
+    for (int c0 = m0; c0 < m1; c0 += 256) {
+        const int e = c0 + tid;
+        bool k = false;
+        int i0 = -1, i1 = -1;
+        if (e < m1) {
+            i0 = matches[(size_t)e * 2]; i1 = matches[(size_t)e * 2 + 1];
+            if (okp && i0 >= 0 && i0 < n0 && i1 >= 0 && i1 < n1) {      // an index outside its frame is never dereferenced
+                const double u0 = norm[(size_t)(r0 + i0) * 2], v0 = norm[(size_t)(r0 + i0) * 2 + 1];
+                const double u1 = norm[(size_t)(r1 + i1) * 2], v1 = norm[(size_t)(r1 + i1) * 2 + 1];
+                const double lj0 = E[0] * u0 + E[1] * v0 + E[2], lj1 = E[3] * u0 + E[4] * v0 + E[5];
+                const double li0 = E[0] * u1 + E[3] * v1 + E[6], li1 = E[1] * u1 + E[4] * v1 + E[7], li2 = E[2] * u1 + E[5] * v1 + E[8];
+                const double dist = fabs(u0 * li0 + v0 * li1 + li2);
+                const double e0 = dist / sqrt(li0 * li0 + li1 * li1), e1 = dist / sqrt(lj0 * lj0 + lj1 * lj1);
+                k = e0 <= th0 && e1 <= th1;      // NaN compares false
+            }
+            keep[e] = k;
+            edges[(size_t)e * 2] = k ? r0 + i0 : -1; edges[(size_t)e * 2 + 1] = k ? r1 + i1 : -1;
+        }
+        int total;
+        const int o = chunk_offset<4>(k, wsum, total);
+        if (k) { kept[(size_t)(m0 + base + o) * 2] = i0; kept[(size_t)(m0 + base + o) * 2 + 1] = i1; }
+        base += total;
+    }
+    if (tid == 0) count[p] = base;
+}
+
+// ---------------------------------------------------------------- components: hook to the smaller root, jump, until nothing hooks
+// state: [0] a hook happened this round, [1] done, [2] rounds run.  A label only ever decreases and always names a row of the same
+// component, so whatever order the atomics land in, the fixed point labels every row with its component's smallest row.
+__global__ __launch_bounds__(256) void tri_cc_init_kernel(int* __restrict__ label, int n_rows, int* __restrict__ state) {
+    const int x = blockIdx.x * 256 + threadIdx.x;
+    if (x < n_rows) label[x] = x;
+    if (x < PRAM_TRI_CC_STATE_WORDS) state[x] = 0;
+}
+
+__global__ __launch_bounds__(256) void tri_cc_hook_kernel(const int* __restrict__ edges, int n_edges, int n_rows, int* label, int* state) {
+    if (state[1]) return;
+    const int e = blockIdx.x * 256 + threadIdx.x;
+    if (e >= n_edges) return;
+    const int u = edges[(size_t)e * 2], v = edges[(size_t)e * 2 + 1];
+    if (u < 0 || v < 0 || u >= n_rows || v >= n_rows) return;
+    const int ru = label[u], rv = label[v];
+    if (ru != rv) {
+        atomicMin(&label[ru > rv ? ru : rv], ru > rv ? rv : ru);
+        state[0] = 1;
+    }
+}
+
+__global__ __launch_bounds__(256) void tri_cc_jump_kernel(int* label, int n_rows, const int* __restrict__ state) {
+    if (state[1]) return;
+    const int x = blockIdx.x * 256 + threadIdx.x;
+    if (x >= n_rows) return;
+    int l = label[x];
+    for (int it = 0; it < n_rows; ++it) {      // labels strictly decrease along a chain
+        const int nl = label[l];
+        if (nl == l) break;
+        l = nl;
+    }
+    label[x] = l;
+}
+
+__global__ void tri_cc_end_kernel(int* __restrict__ state) {
+    if (state[1]) return;
+    if (!state[0]) state[1] = 1;
+    state[0] = 0;
+    state[2] += 1;
+}
+
+// ---------------------------------------------------------------- tracks: counts, a scan over labels, a cursor fill, a sort per track
+struct TrackWs { int* size; int* tidx; int* eoff; int* cursor; int* bsum; };
+
+__global__ __launch_bounds__(256) void tri_count_kernel(const int* __restrict__ label, int n_rows, int* __restrict__ size) {
+    const int x = blockIdx.x * 256 + threadIdx.x;
+    if (x >= n_rows) return;
+    const int l = label[x];
+    if (l >= 0 && l < n_rows) atomicAdd(&size[l], 1);
+}
+
+// block-local exclusive scans of (is a track, its entries) over the labels, and the block's totals
+__global__ __launch_bounds__(SCAN) void tri_scan_blocks_kernel(TrackWs ws, int n_rows) {
+    __shared__ int wsum[4];
+    const int x = blockIdx.x * SCAN + threadIdx.x;
+    const int s = x < n_rows ? ws.size[x] : 0;
+    const int a = s >= 2 ? 1 : 0, b = s >= 2 ? s : 0;
+    int ta, tb;
+    const int oa = chunk_offset_n<4>(a, wsum, ta);
+    const int ob = chunk_offset_n<4>(b, wsum, tb);
+    if (x < n_rows) { ws.tidx[x] = oa; ws.eoff[x] = ob; }
+    if (threadIdx.x == 0) { ws.bsum[(size_t)blockIdx.x * 2] = ta; ws.bsum[(size_t)blockIdx.x * 2 + 1] = tb; }
+}
+
+// one workgroup: the block totals -> their exclusive scan in place; sizes = (tracks, entries); trk_off's last entry
+__global__ __launch_bounds__(256) void tri_scan_totals_kernel(TrackWs ws, int n_blocks, int* __restrict__ sizes, int* __restrict__ trk_off) {
+    __shared__ int wsum[4];
+    int base_a = 0, base_b = 0;
+    for (int c0 = 0; c0 < n_blocks; c0 += 256) {
+        const int i = c0 + threadIdx.x;
+        const int a = i < n_blocks ? ws.bsum[(size_t)i * 2] : 0, b = i < n_blocks ? ws.bsum[(size_t)i * 2 + 1] : 0;
+        int ta, tb;
+        const int oa = chunk_offset_n<4>(a, wsum, ta);
+        const int ob = chunk_offset_n<4>(b, wsum, tb);
+        if (i < n_blocks) { ws.bsum[(size_t)i * 2] = base_a + oa; ws.bsum[(size_t)i * 2 + 1] = base_b + ob; }
+        base_a += ta; base_b += tb;
+    }
+    if (threadIdx.x == 0) { sizes[0] = base_a; sizes[1] = base_b; trk_off[base_a] = base_b; }
+}
+
+__global__ __launch_bounds__(256) void tri_fill_kernel(const int* __restrict__ label, TrackWs ws, int n_rows, int* __restrict__ trk_off,
+                                                       int* __restrict__ trk_label, int* __restrict__ trk_row) {
+    const int x = blockIdx.x * 256 + threadIdx.x;
+    if (x >= n_rows) return;
+    const int l = label[x];
+    if (l < 0 || l >= n_rows || ws.size[l] < 2) return;
+    const int t = ws.tidx[l] + ws.bsum[(size_t)(l / SCAN) * 2], eo = ws.eoff[l] + ws.bsum[(size_t)(l / SCAN) * 2 + 1];
+    const int pos = atomicAdd(&ws.cursor[l], 1);
+    if (eo + pos < n_rows) trk_row[eo + pos] = x;
+    if (x == l) { trk_off[t] = eo; trk_label[t] = l; }
+}
+
+// One wave per track: a bitonic network in its flip form (every comparator ascending, so the positions beyond the track's length
+// stand for +inf and are skipped), in place in global memory; no cap on the length.
+__global__ __launch_bounds__(64) void tri_sort_kernel(const int* __restrict__ sizes, const int* __restrict__ trk_off, int* trk_row, int n_rows) {
+    const int t = blockIdx.x, lane = threadIdx.x;
+    if (t >= sizes[0]) return;
+    int beg = trk_off[t], end = trk_off[t + 1];
+    beg = beg < 0 ? 0 : (beg > n_rows ? n_rows : beg);
+    end = end < beg ? beg : (end > n_rows ? n_rows : end);
+    const int L = end - beg;
+    int* a = trk_row + beg;
+    int N2 = 1;
+    for (int it = 0; it < 31 && N2 < L; ++it) N2 <<= 1;
+    for (int k = 2; k <= N2; k <<= 1) {
+        const int h = k >> 1;
+        for (int i = lane; i < (N2 >> 1); i += 64) {
+            const int blk = i / h, w = i - blk * h, lo = blk * k + w, hi = blk * k + k - 1 - w;
+            if (hi < L) { const int x = a[lo], y = a[hi]; if (x > y) { a[lo] = y; a[hi] = x; } }
+        }
+        __syncthreads();
+        for (int j = k >> 2; j >= 1; j >>= 1) {
+            for (int i = lane; i < (N2 >> 1); i += 64) {
+                const int blk = i / j, lo = blk * 2 * j + (i - blk * j), hi = lo + j;
+                if (hi < L) { const int x = a[lo], y = a[hi]; if (x > y) { a[lo] = y; a[hi] = x; } }
+            }
+            __syncthreads();
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void tri_derive_kernel(const int* __restrict__ sizes, const int* __restrict__ trk_row,
+                                                         const int* __restrict__ frame_off, int n_frames, int n_rows,
+                                                         int* __restrict__ trk_frame, int* __restrict__ trk_kpt) {
+    const int e = blockIdx.x * 256 + threadIdx.x;
+    if (e >= sizes[1] || e >= n_rows) return;
+    const int r = trk_row[e];
+    const int f = frame_of_row(frame_off, n_frames, r);
+    trk_frame[e] = f; trk_kpt[e] = r - frame_off[f];
+}
+
+// ---------------------------------------------------------------- triangulate: one wave per track
+struct TriArgs {
+    const double* norm; const float* kpts; const double* table; const int* cam_model; const double* cam_params;
+    const int* trk_row; const int* trk_frame; int n_frames, n_rows;
+};
+
+struct V3 { double x, y, z; };
+__device__ __forceinline__ V3 sub(V3 a, V3 b) { return {a.x - b.x, a.y - b.y, a.z - b.z}; }
+__device__ __forceinline__ double dot(V3 a, V3 b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
+__device__ __forceinline__ V3 cross(V3 a, V3 b) { return {a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x}; }
+__device__ __forceinline__ double angle(V3 a, V3 b) { const V3 c = cross(a, b); return atan2(sqrt(dot(c, c)), dot(a, b)); }
+__device__ __forceinline__ bool fin(double x) { return isfinite(x); }
+
+// entry e names a row and a frame the tables hold (a caller's own track table may not)
+__device__ __forceinline__ bool entry_ok(const TriArgs& g, int e) {
+    const int r = g.trk_row[e], f = g.trk_frame[e];
+    return r >= 0 && r < g.n_rows && f >= 0 && f < g.n_frames;
+}
+
+__device__ __forceinline__ V3 entry_centre(const TriArgs& g, int e) {
+    const double* T = g.table + (size_t)g.trk_frame[e] * FC;
+    return {T[12], T[13], T[14]};
+}
+
+// the observation's unit ray in world coordinates: R^T (u, v, 1) / |(u, v, 1)|
+__device__ __forceinline__ V3 entry_ray(const TriArgs& g, int e) {
+    const double* T = g.table + (size_t)g.trk_frame[e] * FC;
+    const size_t r = (size_t)g.trk_row[e];
+    const double u = g.norm[r * 2], v = g.norm[r * 2 + 1];
+    const double n = sqrt(u * u + v * v + 1.0);
+    const double x = u / n, y = v / n, z = 1.0 / n;
+    return {T[0] * x + T[3] * y + T[6] * z, T[1] * x + T[4] * y + T[7] * z, T[2] * x + T[5] * y + T[8] * z};
+}
+
+__device__ __forceinline__ double entry_depth(const TriArgs& g, int e, V3 X) {
+    const double* T = g.table + (size_t)g.trk_frame[e] * FC;
+    return T[6] * X.x + T[7] * X.y + T[8] * X.z + T[11];
+}
+
+// pixel residual of X in entry e through the full camera model; z: the depth; with_jac: J [2][3] = d residual / d X
+__device__ __forceinline__ void entry_residual(const TriArgs& g, int e, V3 X, double& z, double& r0, double& r1, bool with_jac, double* J) {
+    const int f = g.trk_frame[e];
+    const double* T = g.table + (size_t)f * FC;
+    const Cam c = cam_unify(g.cam_model[f], g.cam_params + (size_t)f * PRAM_POSE_CAM_PARAMS);
+    const size_t r = (size_t)g.trk_row[e];
+    const double xc = T[0] * X.x + T[1] * X.y + T[2] * X.z + T[9];
+    const double yc = T[3] * X.x + T[4] * X.y + T[5] * X.z + T[10];
+    z = T[6] * X.x + T[7] * X.y + T[8] * X.z + T[11];
+    const double u = xc / z, v = yc / z;
+    double ud, vd;
+    distort(c, u, v, ud, vd);
+    r0 = c.fx * ud + c.cx - ((double)g.kpts[r * 2] + 0.5);
+    r1 = c.fy * vd + c.cy - ((double)g.kpts[r * 2 + 1] + 0.5);
+    if (with_jac) {
+        double j11, j12, j22;
+        distort_jac(c, u, v, j11, j12, j22);
+        const double iz = 1.0 / z;
+        const double a00 = c.fx * j11 * iz, a01 = c.fx * j12 * iz, a02 = -c.fx * (j11 * u + j12 * v) * iz;
+        const double a10 = c.fy * j12 * iz, a11 = c.fy * j22 * iz, a12 = -c.fy * (j12 * u + j22 * v) * iz;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            J[k] = a00 * T[k] + a01 * T[3 + k] + a02 * T[6 + k];
+            J[3 + k] = a10 * T[k] + a11 * T[3 + k] + a12 * T[6 + k];
+        }
+    }
+}
+
+// squared reprojection error and the inlier test: positive depth and error <= thr (NaN compares false)
+__device__ __forceinline__ bool entry_inlier(const TriArgs& g, int e, V3 X, double thr2, double& err2) {
+    if (!entry_ok(g, e)) { err2 = 0.0; return false; }
+    double z, r0, r1;
+    entry_residual(g, e, X, z, r0, r1, false, nullptr);
+    err2 = r0 * r0 + r1 * r1;
+    return z > 0.0 && err2 <= thr2;
+}
+
+// A x = b for a symmetric A given as a00 a01 a02 a11 a12 a22, by Cholesky; false when a pivot is not positive or x is not finite
+__device__ bool chol_solve3(const double* __restrict__ A, const double* __restrict__ b, double* x) {
+    if (!(A[0] > 0.0)) return false;
+    const double l00 = sqrt(A[0]), l10 = A[1] / l00, l20 = A[2] / l00;
+    const double d1 = A[3] - l10 * l10;
+    if (!(d1 > 0.0)) return false;
+    const double l11 = sqrt(d1), l21 = (A[4] - l20 * l10) / l11;
+    const double d2 = A[5] - l20 * l20 - l21 * l21;
+    if (!(d2 > 0.0)) return false;
+    const double l22 = sqrt(d2);
+    const double y0 = b[0] / l00, y1 = (b[1] - l10 * y0) / l11, y2 = (b[2] - l20 * y0 - l21 * y1) / l22;
+    x[2] = y2 / l22;
+    x[1] = (y1 - l21 * x[2]) / l11;
+    x[0] = (y0 - l10 * x[1] - l20 * x[2]) / l00;
+    return fin(x[0]) && fin(x[1]) && fin(x[2]);
+}
+
+__device__ __forceinline__ int wave_sum_i32(int v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+
+__global__ __launch_bounds__(64) void tri_triangulate_kernel(TriArgs g, const int* __restrict__ trk_off, const int* __restrict__ trk_label,
+                                                             int n_entries, int trials, unsigned long long seed, double min_angle,
+                                                             double max_err, int* __restrict__ accept, double* __restrict__ xyz,
+                                                             double* __restrict__ err, int* __restrict__ kept_n, int* __restrict__ best,
+                                                             unsigned char* ent_keep, double* ent_err) {
+    const int t = blockIdx.x, lane = threadIdx.x;
+    int beg = trk_off[t], end = trk_off[t + 1];
+    beg = beg < 0 ? 0 : (beg > n_entries ? n_entries : beg);
+    end = end < beg ? beg : (end > n_entries ? n_entries : end);
+    const int L = end - beg;
+    const double thr2 = max_err * max_err;
+    const long long all = (long long)L * (L - 1) / 2;
+    const bool exhaustive = all <= (long long)trials;
+    const int H = exhaustive ? (int)all : trials;
+    const unsigned long long key0 = sm64(seed) ^ ((unsigned long long)(unsigned)trk_label[t] << 32);
+
+    // ---- hypotheses: every value below is uniform over the wave
+    int bc = 0, bh = -1, hi_ = 0, hj_ = 1;
+    double bs = 0.0;
+    V3 bX = {0.0, 0.0, 0.0};
+    for (int h = 0; h < H; ++h) {
+        int i, j;
+        if (exhaustive) {
+            i = hi_; j = hj_;
+            if (++hj_ == L) { ++hi_; hj_ = hi_ + 1; }
+        } else {
+            const unsigned long long key = sm64(key0 ^ (unsigned long long)(unsigned)h);
+            int a = (int)__umul64hi(sm64(key + 0ull), (unsigned long long)L);
+            int b = (int)__umul64hi(sm64(key + 1ull), (unsigned long long)(L - 1));
+            b += b >= a;
+            i = a < b ? a : b; j = a < b ? b : a;
+        }
+        const int ei = beg + i, ej = beg + j;
+        if (!entry_ok(g, ei) || !entry_ok(g, ej) || g.trk_frame[ei] == g.trk_frame[ej]) continue;
+        const V3 C1 = entry_centre(g, ei), C2 = entry_centre(g, ej), d1 = entry_ray(g, ei), d2 = entry_ray(g, ej);
+        if (!(angle(d1, d2) >= min_angle)) continue;
+        const V3 w = sub(C1, C2);
+        const double a = dot(d1, d1), b = dot(d1, d2), c = dot(d2, d2), d = dot(d1, w), e = dot(d2, w);
+        const double den = a * c - b * b;
+        const double s = (b * e - c * d) / den, u = (a * e - b * d) / den;
+        const V3 X = {0.5 * ((C1.x + s * d1.x) + (C2.x + u * d2.x)), 0.5 * ((C1.y + s * d1.y) + (C2.y + u * d2.y)),
+                      0.5 * ((C1.z + s * d1.z) + (C2.z + u * d2.z))};
+        if (!(entry_depth(g, ei, X) > 0.0) || !(entry_depth(g, ej, X) > 0.0)) continue;
+        int cnt = 0;
+        double sse = 0.0;
+        for (int k = lane; k < L; k += 64) {
+            double e2;
+            const bool in = entry_inlier(g, beg + k, X, thr2, e2);
+            cnt += in;
+            sse += in ? e2 : 0.0;
+        }
+        cnt = wave_sum_i32(cnt);
+        sse = wave_sum_f64(sse);
+        if (cnt >= 2 && (cnt > bc || (cnt == bc && sse < bs))) { bc = cnt; bs = sse; bh = h; bX = X; }      // the lower index keeps a tie
+    }
+    if (bh < 0) {
+        for (int k = lane; k < L; k += 64) { ent_keep[beg + k] = 0; ent_err[beg + k] = -1.0; }
+        if (lane == 0) {
+            accept[t] = 0; kept_n[t] = 0; best[t] = -1; err[t] = 0.0;
+            xyz[(size_t)t * 3] = 0.0; xyz[(size_t)t * 3 + 1] = 0.0; xyz[(size_t)t * 3 + 2] = 0.0;
+        }
+        return;
+    }
+
+    // ---- refit on the winner's inliers (ent_keep holds them until the final marking; a lane reads back its own entries only)
+    V3 X = bX;
+    {
+        double acc[9];
+#pragma unroll
+        for (int q = 0; q < 9; ++q) acc[q] = 0.0;
+        for (int k = lane; k < L; k += 64) {
+            double e2;
+            const bool in = entry_inlier(g, beg + k, bX, thr2, e2);
+            ent_keep[beg + k] = in;
+            if (!in) continue;
+            const V3 dd = entry_ray(g, beg + k), C = entry_centre(g, beg + k);
+            const double m00 = 1.0 - dd.x * dd.x, m01 = -dd.x * dd.y, m02 = -dd.x * dd.z, m11 = 1.0 - dd.y * dd.y, m12 = -dd.y * dd.z,
+                         m22 = 1.0 - dd.z * dd.z;
+            acc[0] += m00; acc[1] += m01; acc[2] += m02; acc[3] += m11; acc[4] += m12; acc[5] += m22;
+            acc[6] += m00 * C.x + m01 * C.y + m02 * C.z;
+            acc[7] += m01 * C.x + m11 * C.y + m12 * C.z;
+            acc[8] += m02 * C.x + m12 * C.y + m22 * C.z;
+        }
+#pragma unroll
+        for (int q = 0; q < 9; ++q) acc[q] = wave_sum_f64(acc[q]);
+        double x[3];
+        if (chol_solve3(acc, acc + 6, x)) X = {x[0], x[1], x[2]};
+    }
+    for (int it = 0; it < GN_STEPS; ++it) {
+        double acc[9];
+#pragma unroll
+        for (int q = 0; q < 9; ++q) acc[q] = 0.0;
+        for (int k = lane; k < L; k += 64) {
+            if (!ent_keep[beg + k]) continue;
+            double z, r0, r1, J[6];
+            entry_residual(g, beg + k, X, z, r0, r1, true, J);
+            if (!(z > 1e-12) || !fin(r0 * r0 + r1 * r1)) continue;
+            acc[0] += J[0] * J[0] + J[3] * J[3]; acc[1] += J[0] * J[1] + J[3] * J[4]; acc[2] += J[0] * J[2] + J[3] * J[5];
+            acc[3] += J[1] * J[1] + J[4] * J[4]; acc[4] += J[1] * J[2] + J[4] * J[5]; acc[5] += J[2] * J[2] + J[5] * J[5];
+            acc[6] -= J[0] * r0 + J[3] * r1; acc[7] -= J[1] * r0 + J[4] * r1; acc[8] -= J[2] * r0 + J[5] * r1;
+        }
+#pragma unroll
+        for (int q = 0; q < 9; ++q) acc[q] = wave_sum_f64(acc[q]);
+        double x[3];
+        if (chol_solve3(acc, acc + 6, x)) X = {X.x + x[0], X.y + x[1], X.z + x[2]};
+    }
+
+    // ---- final marking at X, then one entry per frame: the smallest error, the lowest row on a tie (a frame's entries are adjacent)
+    for (int k = lane; k < L; k += 64) {
+        double e2;
+        const bool in = entry_inlier(g, beg + k, X, thr2, e2);
+        ent_err[beg + k] = in ? sqrt(e2) : -1.0;
+    }
+    __syncthreads();
+    int cnt = 0;
+    double esum = 0.0;
+    for (int k = lane; k < L; k += 64) {
+        const double mine = ent_err[beg + k];
+        bool keep = mine >= 0.0;
+        if (keep) {
+            const int f = g.trk_frame[beg + k];
+            for (int o = k - 1; o >= 0 && g.trk_frame[beg + o] == f; --o) {
+                const double other = ent_err[beg + o];
+                if (other >= 0.0 && other <= mine) { keep = false; break; }
+            }
+            for (int o = k + 1; keep && o < L && g.trk_frame[beg + o] == f; ++o) {
+                const double other = ent_err[beg + o];
+                if (other >= 0.0 && other < mine) keep = false;
+            }
+        }
+        ent_keep[beg + k] = keep;
+        cnt += keep;
+        esum += keep ? mine : 0.0;
+    }
+    cnt = wave_sum_i32(cnt);
+    esum = wave_sum_f64(esum);
+    __syncthreads();
+    // ---- some pair of kept entries sees X under min_angle or more
+    bool found = false;
+    for (int k = lane; k < L && !found; k += 64) {
+        if (!ent_keep[beg + k]) continue;
+        const V3 vi = sub(X, entry_centre(g, beg + k));
+        for (int o = k + 1; o < L; ++o) {
+            if (!ent_keep[beg + o]) continue;
+            if (angle(vi, sub(X, entry_centre(g, beg + o))) >= min_angle) { found = true; break; }
+        }
+    }
+    const bool any = __any(found);
+    if (lane == 0) {
+        accept[t] = cnt >= 2 && any; kept_n[t] = cnt; best[t] = bh; err[t] = cnt > 0 ? esum / (double)cnt : 0.0;
+        xyz[(size_t)t * 3] = X.x; xyz[(size_t)t * 3 + 1] = X.y; xyz[(size_t)t * 3 + 2] = X.z;
+    }
+}
+
+int check_models(const int* cam_model_host, int n_frames, const char* what) {
+    for (int f = 0; f < n_frames; ++f)
+        if (cam_model_host[f] < PRAM_CAM_SIMPLE_PINHOLE || cam_model_host[f] > PRAM_CAM_OPENCV) {
+            pram_set_error("%s: camera model id %d of frame %d is not supported", what, cam_model_host[f], f);
+            return PRAM_E_UNSUPPORTED;
+        }
+    return PRAM_OK;
+}
+
+constexpr int MAX_ROWS = 1 << 30;      // the sort's network doubles a length
+
+size_t align_up(size_t x) { return (x + 255) & ~(size_t)255; }
+
+}  // namespace
+
+extern "C" int pram_tri_frames(const double* qvec, const double* tvec, const int* cam_model, const double* cam_params,
+                               const int* cam_model_host, int n_frames, double* table, void* stream) {
+    PRAM_REQUIRE(qvec && tvec && cam_model && cam_params && cam_model_host && table, "pram_tri_frames: null pointer");
+    PRAM_REQUIRE(aligned(qvec, 8) && aligned(tvec, 8) && aligned(cam_model, 4) && aligned(cam_params, 8) && aligned(table, 8),
+                 "pram_tri_frames: misaligned pointer");
+    PRAM_REQUIRE(n_frames >= 0, "pram_tri_frames: needs n_frames >= 0");
+    const int rc = check_models(cam_model_host, n_frames, "pram_tri_frames");
+    if (rc != PRAM_OK) return rc;
+    if (n_frames == 0) return PRAM_OK;
+    hipLaunchKernelGGL(tri_frames_kernel, dim3(cdiv(n_frames, 64)), dim3(64), 0, (hipStream_t)stream, qvec, tvec, cam_model, cam_params, n_frames,
+                       table);
+    return pram_launch_status("pram_tri_frames");
+}
+
+extern "C" int pram_tri_normalize(const float* keypoints, const int* frame_off, const int* cam_model, const double* cam_params,
+                                  const int* cam_model_host, int n_frames, int n_rows, double pixel_offset, double* norm, void* stream) {
+    PRAM_REQUIRE(keypoints && frame_off && cam_model && cam_params && cam_model_host && norm, "pram_tri_normalize: null pointer");
+    PRAM_REQUIRE(aligned(keypoints, 4) && aligned(frame_off, 4) && aligned(cam_model, 4) && aligned(cam_params, 8) && aligned(norm, 8),
+                 "pram_tri_normalize: misaligned pointer");
+    PRAM_REQUIRE(n_frames >= 0 && n_rows >= 0 && (n_rows == 0 || n_frames >= 1) && isfinite(pixel_offset),
+                 "pram_tri_normalize: needs n_frames >= 0, n_rows >= 0 (0 without frames), a finite pixel_offset");
+    const int rc = check_models(cam_model_host, n_frames, "pram_tri_normalize");
+    if (rc != PRAM_OK) return rc;
+    if (n_rows == 0) return PRAM_OK;
+    hipLaunchKernelGGL(tri_normalize_kernel, dim3(cdiv(n_rows, 256)), dim3(256), 0, (hipStream_t)stream, keypoints, frame_off, cam_model,
+                       cam_params, n_frames, n_rows, pixel_offset, norm);
+    return pram_launch_status("pram_tri_normalize");
+}
+
+extern "C" int pram_tri_verify(const double* norm, const int* frame_off, const int* pairs, const int* match_off, const int* matches,
+                               const double* table, int n_frames, int n_pairs, int n_matches, double max_error, unsigned char* keep,
+                               int* kept, int* edges, int* count, void* stream) {
+    PRAM_REQUIRE(norm && frame_off && pairs && match_off && matches && table && keep && kept && edges && count, "pram_tri_verify: null pointer");
+    PRAM_REQUIRE(aligned(norm, 8) && aligned(frame_off, 4) && aligned(pairs, 4) && aligned(match_off, 4) && aligned(matches, 4) &&
+                 aligned(table, 8) && aligned(kept, 4) && aligned(edges, 4) && aligned(count, 4), "pram_tri_verify: misaligned pointer");
+    PRAM_REQUIRE(n_frames >= 0 && n_pairs >= 0 && n_matches >= 0 && max_error > 0.0,
+                 "pram_tri_verify: needs n_frames >= 0, n_pairs >= 0, n_matches >= 0, max_error > 0");
+    if (n_pairs == 0) return PRAM_OK;
+    hipLaunchKernelGGL(tri_verify_kernel, dim3(n_pairs), dim3(256), 0, (hipStream_t)stream, norm, frame_off, pairs, match_off, matches, table,
+                       n_frames, n_matches, max_error, keep, kept, edges, count);
+    return pram_launch_status("pram_tri_verify");
+}
+
+extern "C" int pram_tri_components(const int* edges, int n_edges, int n_rows, int first_round, int n_rounds, int* label, int* state,
+                                   void* stream) {
+    PRAM_REQUIRE(edges && label && state, "pram_tri_components: null pointer");
+    PRAM_REQUIRE(aligned(edges, 4) && aligned(label, 4) && aligned(state, 4), "pram_tri_components: misaligned pointer");
+    PRAM_REQUIRE(n_edges >= 0 && n_rows >= 0 && n_rows <= MAX_ROWS && first_round >= 0 && n_rounds >= 0 && n_rounds <= 1024,
+                 "pram_tri_components: needs n_edges >= 0, 0 <= n_rows <= 2^30, first_round >= 0, 0 <= n_rounds <= 1024");
+    hipStream_t st = (hipStream_t)stream;
+    if (first_round == 0) hipLaunchKernelGGL(tri_cc_init_kernel, dim3(cdiv(n_rows > 0 ? n_rows : 1, 256)), dim3(256), 0, st, label, n_rows, state);
+    for (int r = 0; r < n_rounds; ++r) {
+        if (n_edges) hipLaunchKernelGGL(tri_cc_hook_kernel, dim3(cdiv(n_edges, 256)), dim3(256), 0, st, edges, n_edges, n_rows, label, state);
+        if (n_rows) hipLaunchKernelGGL(tri_cc_jump_kernel, dim3(cdiv(n_rows, 256)), dim3(256), 0, st, label, n_rows, state);
+        hipLaunchKernelGGL(tri_cc_end_kernel, dim3(1), dim3(1), 0, st, state);
+    }
+    return pram_launch_status("pram_tri_components");
+}
+
+extern "C" size_t pram_tri_tracks_workspace_bytes(int n_rows) {
+    if (n_rows < 0 || n_rows > MAX_ROWS) return 0;
+    const size_t n = (size_t)(n_rows > 0 ? n_rows : 1);
+    return 4 * align_up(n * sizeof(int)) + align_up((size_t)cdiv((int)n, SCAN) * 2 * sizeof(int));
+}
+
+extern "C" int pram_tri_tracks(const int* label, const int* frame_off, int n_frames, int n_rows, void* workspace, size_t workspace_bytes,
+                               int* trk_off, int* trk_label, int* trk_row, int* trk_frame, int* trk_kpt, int* sizes, void* stream) {
+    PRAM_REQUIRE(label && frame_off && workspace && trk_off && trk_label && trk_row && trk_frame && trk_kpt && sizes, "pram_tri_tracks: null pointer");
+    PRAM_REQUIRE(aligned(label, 4) && aligned(frame_off, 4) && aligned(workspace, 256) && aligned(trk_off, 4) && aligned(trk_label, 4) &&
+                 aligned(trk_row, 4) && aligned(trk_frame, 4) && aligned(trk_kpt, 4) && aligned(sizes, 4), "pram_tri_tracks: misaligned pointer");
+    PRAM_REQUIRE(n_frames >= 0 && n_rows >= 0 && n_rows <= MAX_ROWS && (n_rows == 0 || n_frames >= 1),
+                 "pram_tri_tracks: needs n_frames >= 0, 0 <= n_rows <= 2^30 (0 without frames)");
+    PRAM_REQUIRE(workspace_bytes >= pram_tri_tracks_workspace_bytes(n_rows), "pram_tri_tracks: workspace too small");
+    hipStream_t st = (hipStream_t)stream;
+    const size_t n = (size_t)(n_rows > 0 ? n_rows : 1), stride = align_up(n * sizeof(int));
+    char* w = static_cast<char*>(workspace);
+    TrackWs ws = {reinterpret_cast<int*>(w), reinterpret_cast<int*>(w + stride), reinterpret_cast<int*>(w + 2 * stride),
+                  reinterpret_cast<int*>(w + 3 * stride), reinterpret_cast<int*>(w + 4 * stride)};
+    const int nb = cdiv((int)n, SCAN);
+    if (hipMemsetAsync(ws.size, 0, stride, st) != hipSuccess || hipMemsetAsync(ws.cursor, 0, stride, st) != hipSuccess)
+        return pram_launch_status("pram_tri_tracks");
+    if (n_rows) hipLaunchKernelGGL(tri_count_kernel, dim3(cdiv(n_rows, 256)), dim3(256), 0, st, label, n_rows, ws.size);
+    hipLaunchKernelGGL(tri_scan_blocks_kernel, dim3(nb), dim3(SCAN), 0, st, ws, n_rows);
+    hipLaunchKernelGGL(tri_scan_totals_kernel, dim3(1), dim3(256), 0, st, ws, nb, sizes, trk_off);
+    if (n_rows >= 2) {
+        hipLaunchKernelGGL(tri_fill_kernel, dim3(cdiv(n_rows, 256)), dim3(256), 0, st, label, ws, n_rows, trk_off, trk_label, trk_row);
+        hipLaunchKernelGGL(tri_sort_kernel, dim3(n_rows / 2), dim3(64), 0, st, sizes, trk_off, trk_row, n_rows);
+        hipLaunchKernelGGL(tri_derive_kernel, dim3(cdiv(n_rows, 256)), dim3(256), 0, st, sizes, trk_row, frame_off, n_frames, n_rows, trk_frame,
+                           trk_kpt);
+    }
+    return pram_launch_status("pram_tri_tracks");
+}
+
+extern "C" int pram_tri_triangulate(const double* norm, const float* keypoints, const double* table, const int* cam_model,
+                                    const double* cam_params, const int* trk_off, const int* trk_label, const int* trk_row,
+                                    const int* trk_frame, int n_tracks, int n_entries, int n_frames, int n_rows, int trials,
+                                    unsigned long long seed, double min_tri_angle, double max_reproj_error, int* accept, double* xyz,
+                                    double* error, int* kept, int* best, unsigned char* entry_keep, double* entry_error, void* stream) {
+    PRAM_REQUIRE(norm && keypoints && table && cam_model && cam_params && trk_off && trk_label && trk_row && trk_frame && accept && xyz && error &&
+                 kept && best && entry_keep && entry_error, "pram_tri_triangulate: null pointer");
+    PRAM_REQUIRE(aligned(norm, 8) && aligned(keypoints, 4) && aligned(table, 8) && aligned(cam_model, 4) && aligned(cam_params, 8) &&
+                 aligned(trk_off, 4) && aligned(trk_label, 4) && aligned(trk_row, 4) && aligned(trk_frame, 4) && aligned(accept, 4) &&
+                 aligned(xyz, 8) && aligned(error, 8) && aligned(kept, 4) && aligned(best, 4) && aligned(entry_error, 8),
+                 "pram_tri_triangulate: misaligned pointer");
+    PRAM_REQUIRE(n_tracks >= 0 && n_entries >= 0 && n_frames >= 0 && n_rows >= 0 && trials >= 1 && trials <= (1 << 24) && min_tri_angle >= 0.0 &&
+                 max_reproj_error > 0.0,
+                 "pram_tri_triangulate: needs n_tracks >= 0, n_entries >= 0, n_frames >= 0, n_rows >= 0, 1 <= trials <= 2^24, min_tri_angle >= 0, max_reproj_error > 0");
+    if (n_tracks == 0) return PRAM_OK;
+    const TriArgs g = {norm, keypoints, table, cam_model, cam_params, trk_row, trk_frame, n_frames, n_rows};
+    hipLaunchKernelGGL(tri_triangulate_kernel, dim3(n_tracks), dim3(64), 0, (hipStream_t)stream, g, trk_off, trk_label, n_entries, trials, seed,
+                       min_tri_angle, max_reproj_error, accept, xyz, error, kept, best, entry_keep, entry_error);
+    return pram_launch_status("pram_tri_triangulate");
+}

@@ -2240,3 +2240,129 @@ def kmeans_assign(x: torch.Tensor, centers: torch.Tensor):
     dist = torch.empty(max(n, 1), device=x.device, dtype=torch.float64)
     _lib.check(L.pram_kmeans_assign(_p(x), n, _p(centers), k, _p(labels), _p(dist), _st()), "pram_kmeans_assign")
     return labels[:n], dist[:n]
+
+
+# ---- triangulation (csrc/triangulate.hip; pram_amd/localization/triangulation.py drives these) --------------------------------
+TRI_GN_STEPS, TRI_FRAME_COLS, TRI_CC_STATE_WORDS = 5, 16, 4      # include/pram_hip.h
+TRI_CC_DONE = 1      # the word of the components' state that says the labels are final
+
+
+def _tri_chk(items):
+    for t, nm, dt in items:
+        _chk(t, nm, dt)
+        assert t.is_contiguous(), nm
+
+
+def _tri_models(cam_model_host, n_frames: int):
+    import ctypes
+    assert len(cam_model_host) == n_frames
+    return (ctypes.c_int * max(n_frames, 1))(*[int(m) for m in cam_model_host])
+
+
+def tri_frames(qvec: torch.Tensor, tvec: torch.Tensor, cam_model: torch.Tensor, cam_params: torch.Tensor, cam_model_host) -> torch.Tensor:
+    """cam_from_world poses qvec float64 [F, 4] (w, x, y, z), tvec float64 [F, 3] and the frames' cameras (cam_model int32 [F],
+    cam_params float64 [F, POSE_CAM_PARAMS], cam_model_host: the ids on the host) -> the frame table float64 [F, TRI_FRAME_COLS]
+    that tri_verify and tri_triangulate read.  Every tensor holds one row at least (the rows beyond F are not read)."""
+    import ctypes
+    L = _lib.load()
+    _tri_chk(((qvec, "qvec", torch.float64), (tvec, "tvec", torch.float64), (cam_model, "cam_model", torch.int32),
+              (cam_params, "cam_params", torch.float64)))
+    F = len(cam_model_host)
+    assert qvec.numel() >= 4 * F and tvec.numel() >= 3 * F and cam_model.numel() >= F and cam_params.numel() >= POSE_CAM_PARAMS * F
+    host = _tri_models(cam_model_host, F)
+    table = torch.empty(max(F, 1), TRI_FRAME_COLS, device=qvec.device, dtype=torch.float64)
+    _lib.check(L.pram_tri_frames(_p(qvec), _p(tvec), _p(cam_model), _p(cam_params), ctypes.addressof(host), F, _p(table), _st()), "pram_tri_frames")
+    return table
+
+
+def tri_normalize(keypoints: torch.Tensor, frame_off: torch.Tensor, cam_model: torch.Tensor, cam_params: torch.Tensor, cam_model_host,
+                  n_rows: int, pixel_offset: float) -> torch.Tensor:
+    """keypoints float32 [n_rows, 2] of all frames, frame_off int32 [F + 1] -> float64 [n_rows, 2] on the normalised plane of each
+    row's frame, (x + pixel_offset, y + pixel_offset) undistorted as pose_prepare does."""
+    import ctypes
+    L = _lib.load()
+    _tri_chk(((keypoints, "keypoints", torch.float32), (frame_off, "frame_off", torch.int32), (cam_model, "cam_model", torch.int32),
+              (cam_params, "cam_params", torch.float64)))
+    F, n_rows = len(cam_model_host), int(n_rows)
+    assert keypoints.numel() >= 2 * n_rows and frame_off.numel() >= F + 1 and cam_model.numel() >= F and cam_params.numel() >= POSE_CAM_PARAMS * F
+    host = _tri_models(cam_model_host, F)
+    norm = torch.empty(max(n_rows, 1), 2, device=keypoints.device, dtype=torch.float64)
+    _lib.check(L.pram_tri_normalize(_p(keypoints), _p(frame_off), _p(cam_model), _p(cam_params), ctypes.addressof(host), F, n_rows,
+                                    float(pixel_offset), _p(norm), _st()), "pram_tri_normalize")
+    return norm
+
+
+def tri_verify(norm: torch.Tensor, frame_off: torch.Tensor, pairs: torch.Tensor, match_off: torch.Tensor, matches: torch.Tensor,
+               table: torch.Tensor, n_frames: int, n_pairs: int, n_matches: int, max_error: float) -> dict:
+    """norm: tri_normalize with offset 0; pairs int32 [Pn, 2] frame indices; the matches as CSR, match_off int32 [Pn + 1] and
+    matches int32 [M, 2] -> keep uint8 [M], kept int32 [M, 2] (pair p's kept matches from match_off[p] on, original order), edges
+    int32 [M, 2] (rows, -1 where dropped), count int32 [Pn]."""
+    L = _lib.load()
+    _tri_chk(((norm, "norm", torch.float64), (frame_off, "frame_off", torch.int32), (pairs, "pairs", torch.int32),
+              (match_off, "match_off", torch.int32), (matches, "matches", torch.int32), (table, "table", torch.float64)))
+    F, Pn, M = int(n_frames), int(n_pairs), int(n_matches)
+    assert frame_off.numel() >= F + 1 and pairs.numel() >= 2 * Pn and match_off.numel() >= Pn + 1 and matches.numel() >= 2 * M
+    assert table.numel() >= TRI_FRAME_COLS * F
+    dev = norm.device
+    out = {"keep": torch.empty(max(M, 1), device=dev, dtype=torch.uint8), "kept": torch.empty(max(M, 1), 2, device=dev, dtype=torch.int32),
+           "edges": torch.empty(max(M, 1), 2, device=dev, dtype=torch.int32), "count": torch.empty(max(Pn, 1), device=dev, dtype=torch.int32)}
+    _lib.check(L.pram_tri_verify(_p(norm), _p(frame_off), _p(pairs), _p(match_off), _p(matches), _p(table), F, Pn, M, float(max_error),
+                                 _p(out["keep"]), _p(out["kept"]), _p(out["edges"]), _p(out["count"]), _st()), "pram_tri_verify")
+    return out
+
+
+def tri_components(edges: torch.Tensor, n_edges: int, n_rows: int, first_round: int, n_rounds: int, label: torch.Tensor, state: torch.Tensor):
+    """Rounds first_round .. first_round + n_rounds - 1 of the connected components over rows (edges int32 [n_edges, 2]) on label
+    int32 [n_rows] and state int32 [TRI_CC_STATE_WORDS]; state[TRI_CC_DONE] says when label holds every row's smallest row."""
+    L = _lib.load()
+    _tri_chk(((edges, "edges", torch.int32), (label, "label", torch.int32), (state, "state", torch.int32)))
+    assert edges.numel() >= 2 * int(n_edges) and label.numel() >= int(n_rows) and state.numel() >= TRI_CC_STATE_WORDS
+    _lib.check(L.pram_tri_components(_p(edges), int(n_edges), int(n_rows), int(first_round), int(n_rounds), _p(label), _p(state), _st()),
+               "pram_tri_components")
+
+
+def tri_tracks(label: torch.Tensor, frame_off: torch.Tensor, n_frames: int, n_rows: int, workspace: Optional[torch.Tensor] = None) -> dict:
+    """label int32 [n_rows] (tri_components) -> the tracks as CSR, sized for the worst case: trk_off int32 [n_rows // 2 + 2],
+    trk_label int32 [n_rows // 2 + 1], trk_row / trk_frame / trk_kpt int32 [n_rows], and sizes int32 [2] = (tracks, entries), all on
+    the device.  ``workspace``: uint8, at least pram_tri_tracks_workspace_bytes; None allocates it."""
+    L = _lib.load()
+    _tri_chk(((label, "label", torch.int32), (frame_off, "frame_off", torch.int32)))
+    F, n = int(n_frames), int(n_rows)
+    assert label.numel() >= n and frame_off.numel() >= F + 1
+    dev = label.device
+    need = int(L.pram_tri_tracks_workspace_bytes(n))
+    if need == 0:
+        raise _lib.PramHipError("pram_tri_tracks: more than 2^30 rows")
+    if workspace is None:
+        workspace = torch.empty(need, device=dev, dtype=torch.uint8)
+    _chk(workspace, "workspace", torch.uint8)
+    i32 = lambda m: torch.empty(max(m, 1), device=dev, dtype=torch.int32)
+    out = {"trk_off": i32(n // 2 + 2), "trk_label": i32(n // 2 + 1), "trk_row": i32(n), "trk_frame": i32(n), "trk_kpt": i32(n), "sizes": i32(2)}
+    _lib.check(L.pram_tri_tracks(_p(label), _p(frame_off), F, n, _p(workspace), workspace.numel(), _p(out["trk_off"]), _p(out["trk_label"]),
+                                 _p(out["trk_row"]), _p(out["trk_frame"]), _p(out["trk_kpt"]), _p(out["sizes"]), _st()), "pram_tri_tracks")
+    return out
+
+
+def tri_triangulate(norm: torch.Tensor, keypoints: torch.Tensor, table: torch.Tensor, cam_model: torch.Tensor, cam_params: torch.Tensor,
+                    trk_off: torch.Tensor, trk_label: torch.Tensor, trk_row: torch.Tensor, trk_frame: torch.Tensor, n_tracks: int,
+                    n_entries: int, n_frames: int, n_rows: int, trials: int = 128, seed: int = 0, min_tri_angle: float = 0.026179938779914945,
+                    max_reproj_error: float = 4.0) -> dict:
+    """norm: tri_normalize with offset 0.5; the tracks of tri_tracks (or a caller's own table) -> accept int32 [T], xyz float64
+    [T, 3], error float64 [T], kept int32 [T], best int32 [T] (the winning hypothesis, -1: none), entry_keep uint8 [E], entry_error
+    float64 [E].  min_tri_angle in radians."""
+    L = _lib.load()
+    _tri_chk(((norm, "norm", torch.float64), (keypoints, "keypoints", torch.float32), (table, "table", torch.float64),
+              (cam_model, "cam_model", torch.int32), (cam_params, "cam_params", torch.float64), (trk_off, "trk_off", torch.int32),
+              (trk_label, "trk_label", torch.int32), (trk_row, "trk_row", torch.int32), (trk_frame, "trk_frame", torch.int32)))
+    T, E, F, n = int(n_tracks), int(n_entries), int(n_frames), int(n_rows)
+    assert norm.numel() >= 2 * n and keypoints.numel() >= 2 * n and table.numel() >= TRI_FRAME_COLS * F and cam_model.numel() >= F
+    assert cam_params.numel() >= POSE_CAM_PARAMS * F and trk_off.numel() >= T + 1 and trk_label.numel() >= T and trk_row.numel() >= E and trk_frame.numel() >= E
+    dev = norm.device
+    new = lambda m, dt, *rest: torch.empty(max(m, 1), *rest, device=dev, dtype=dt)
+    out = {"accept": new(T, torch.int32), "xyz": new(T, torch.float64, 3), "error": new(T, torch.float64), "kept": new(T, torch.int32),
+           "best": new(T, torch.int32), "entry_keep": new(E, torch.uint8), "entry_error": new(E, torch.float64)}
+    _lib.check(L.pram_tri_triangulate(_p(norm), _p(keypoints), _p(table), _p(cam_model), _p(cam_params), _p(trk_off), _p(trk_label), _p(trk_row),
+                                      _p(trk_frame), T, E, F, n, int(trials), int(seed) & 0xFFFFFFFFFFFFFFFF, float(min_tri_angle),
+                                      float(max_reproj_error), _p(out["accept"]), _p(out["xyz"]), _p(out["error"]), _p(out["kept"]), _p(out["best"]),
+                                      _p(out["entry_keep"]), _p(out["entry_error"]), _st()), "pram_tri_triangulate")
+    return out
