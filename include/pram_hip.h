@@ -26,6 +26,8 @@
  *   - Sinkhorn / dual-softmax matching handles at most 8191 rows (m_max) and 4351 columns (n_max) per pair, the dust-bin row
  *     and column excluded (pram_sinkhorn_match_f32, pram_dual_softmax_match_f32);
  *   - k-means labelling takes at most PRAM_KMEANS_MAX_K = 4096 clusters and fewer than 2^31 points (the pram_kmeans entries);
+ *   - statistical outlier removal keeps at most PRAM_KNN_MAX_K = 32 neighbours per point, in registers, and takes fewer than
+ *     2^31 points (pram_knn_mean_distance, pram_sor_select);
  *   - LayerNorm rows are at most 1024 wide; the split-fp16 GEMMs need K % 32 == 0 (other shapes: the exact-fp32 entry);
  *   - the split-fp16 operands carry value * s in fp16 (s = 16 by default, pram_x3_set_act_scale): a finite |x| >= 65520 / s
  *     (4094.97) does not fit.  This one is NOT a silent limit
@@ -1147,6 +1149,45 @@ int pram_tri_triangulate(const double* norm, const float* keypoints, const doubl
                          const int* trk_frame, int n_tracks, int n_entries, int n_frames, int n_rows, int trials,
                          unsigned long long seed, double min_tri_angle, double max_reproj_error, int* accept, double* xyz,
                          double* error, int* kept, int* best, unsigned char* entry_keep, double* entry_error, void* stream);
+
+/* ---- statistical outlier removal of a map's points (csrc/knn.hip; pram_amd/localization/outliers.py drives these) -------------
+ * What RecMap.remove_statics_outlier (recmap.py:43-61) takes from Open3D's PointCloud::RemoveStatisticalOutliers, written from
+ * knowledge of its source and NOT pinned to it (Open3D was never run beside this).  x [n][3] float64.
+ *   1. for every point i its kk = min(k, n) nearest points, ITSELF INCLUDED at distance 0; avg[i] is the mean of the kk Euclidean
+ *      distances.  The search is all-pairs and exact.  Ties at the kk-th distance do not matter: the multiset of the kk smallest
+ *      distances is unique.  No neighbour index is returned;
+ *   2. a point is valid when avg[i] > 0 (a point with kk - 1 exact duplicates or more is not); nv is the number of valid points;
+ *   3. over the valid points mean = sum(avg) / nv, std = sqrt(sum((avg - mean)^2) / (nv - 1)), threshold = mean + std_ratio * std;
+ *   4. the inliers are the valid points with avg[i] < threshold (strict), in ascending index.  With nv < 2 there is no threshold
+ *      (std and threshold are NaN) and no point is an inlier.
+ * One fixed arithmetic, so a result is the same bits on every run and equals the numpy restatement tests/outliers_ref.py:
+ *   - d2 = (dx * dx + dy * dy) + dz * dz with dx = x[j] - x[i], products and sums written out;
+ *   - a point's kk smallest d2 in ascending order, each square-rooted, added to 0.0 in that order, the sum divided by (double)kk;
+ *   - the two sums over points follow the k-means rule above with blocks of PRAM_SOR_BLOCK consecutive indices: inside a block the
+ *     terms are added to 0.0 in ascending index (an invalid point contributes nothing), the block sums are added to 0.0 in
+ *     ascending block index; two passes, the mean first, then the squared deviations (d * d with d = avg - mean).  Results depend
+ *     on PRAM_SOR_BLOCK.  No floating-point atomics; counts are integers.
+ * Both entries refuse (PRAM_E_ARG) n < 1, n >= 2^31 (n travels as long long so that this is a refusal and not a wrapped int), a
+ * null or misaligned pointer (float64 buffers and the workspace 8 bytes, int32 4); k > n is allowed (kk is the algorithm's own
+ * rule).  Coordinates are finite: a NaN d2 fails every `<`, so a candidate with a non-finite coordinate is never kept and a
+ * query with one keeps nothing finite (its avg is then inf or NaN, which is not an inlier); pram_amd's Python layer refuses such
+ * input before it gets here.  Nothing waits for the stream. */
+#define PRAM_KNN_TILE 1024             /* candidates per LDS tile of the all-pairs search: three planes of float64 */
+#define PRAM_KNN_MAX_K 32              /* a thread's sorted list of smallest d2 lives in registers: this many entries at most */
+#define PRAM_SOR_BLOCK 1024            /* points per block of the two sums over points; the results depend on it */
+
+/* avg [n] float64: step 1.  One thread per query point, the candidates streamed through LDS in tiles of PRAM_KNN_TILE.  Refuses
+ * k < 1 and k > PRAM_KNN_MAX_K as well.  Needs no workspace. */
+int pram_knn_mean_distance(const double* x, long long n, int k, double* avg, void* stream);
+
+/* 0 for an n the entries refuse. */
+size_t pram_sor_workspace_bytes(long long n);
+
+/* Steps 2 to 4 on avg [n]: stats [4] float64 = (mean, std, threshold, nv); mask [n] uint8 (1: inlier); inlier_idx [n] int32: the
+ * inliers' indices in ascending order, entries beyond the count unspecified; count [2] int32 = (inliers, nv).  nv == 0 gives a
+ * NaN mean too.  Refuses a std_ratio that is not > 0 and a workspace that is too small. */
+int pram_sor_select(const double* avg, long long n, double std_ratio, void* workspace, size_t workspace_bytes, double* stats,
+                    unsigned char* mask, int* inlier_idx, int* count, void* stream);
 
 #ifdef __cplusplus
 }

@@ -19,7 +19,8 @@ three scenes); a point within rounding of the boundary between two centres can d
 variance before centring, this from the centred points: the same number up to rounding.
 
 Not here: method='birch' (its CF-tree is built by inserting samples one at a time and its global step is an agglomerative merge:
-neither is data-parallel) and Open3D outlier removal (recmap.py:36-61)."""
+neither is data-parallel).  Open3D's statistical outlier removal (recmap.py:43-61), which the reference runs before this step on its
+outdoor datasets, is localization/outliers.py: its filter_points takes and returns the two dicts label_points takes."""
 from __future__ import annotations
 
 from typing import Dict, Optional

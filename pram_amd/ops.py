@@ -2366,3 +2366,45 @@ def tri_triangulate(norm: torch.Tensor, keypoints: torch.Tensor, table: torch.Te
                                       float(max_reproj_error), _p(out["accept"]), _p(out["xyz"]), _p(out["error"]), _p(out["kept"]), _p(out["best"]),
                                       _p(out["entry_keep"]), _p(out["entry_error"]), _st()), "pram_tri_triangulate")
     return out
+
+
+# ---- statistical outlier removal (csrc/knn.hip; pram_amd/localization/outliers.py drives these) -------------------------------
+KNN_TILE, KNN_MAX_K, SOR_BLOCK = 1024, 32, 1024      # include/pram_hip.h
+SOR_MEAN, SOR_STD, SOR_THRESHOLD, SOR_NV = 0, 1, 2, 3      # entries of the statistics
+
+
+def knn_mean_distance(x: torch.Tensor, k: int) -> torch.Tensor:
+    """x float64 [n, 3] -> float64 [n]: every point's mean distance to its min(k, n) nearest points, itself included (all pairs,
+    exact).  1 <= k <= KNN_MAX_K."""
+    L = _lib.load()
+    n = _kmeans_x(x)
+    avg = torch.empty(max(n, 1), device=x.device, dtype=torch.float64)
+    _lib.check(L.pram_knn_mean_distance(_p(x), n, int(k), _p(avg), _st()), "pram_knn_mean_distance")
+    return avg[:n]
+
+
+def sor_workspace(n: int, device) -> torch.Tensor:
+    need = int(_lib.load().pram_sor_workspace_bytes(int(n)))
+    if need == 0:
+        raise _lib.PramHipError(f"sor_select: needs 1 <= n < 2^31, got n = {n}")
+    return torch.empty(need, device=device, dtype=torch.uint8)
+
+
+def sor_select(avg: torch.Tensor, std_ratio: float, workspace: Optional[torch.Tensor] = None) -> dict:
+    """avg float64 [n] (:func:`knn_mean_distance`) -> stats float64 [4] (mean, std, threshold and the number of valid points, over
+    the points with avg > 0), mask uint8 [n] (valid and avg < threshold), inlier_idx int32 [n] (the inliers' indices, ascending;
+    the entries beyond count[0] are unspecified) and count int32 [2] (inliers, valid points).  Nothing is read back."""
+    L = _lib.load()
+    _chk(avg, "avg", torch.float64)
+    if avg.dim() != 1 or not avg.is_contiguous():
+        raise _lib.PramHipError(f"avg: expected a contiguous float64 [n] tensor, got {tuple(avg.shape)}")
+    n, dev = int(avg.shape[0]), avg.device
+    if workspace is None:
+        workspace = sor_workspace(n, dev)
+    _chk(workspace, "workspace", torch.uint8)
+    out = {"stats": torch.empty(4, device=dev, dtype=torch.float64), "mask": torch.empty(max(n, 1), device=dev, dtype=torch.uint8),
+           "inlier_idx": torch.empty(max(n, 1), device=dev, dtype=torch.int32), "count": torch.empty(2, device=dev, dtype=torch.int32)}
+    _lib.check(L.pram_sor_select(_p(avg), n, float(std_ratio), _p(workspace), workspace.numel(), _p(out["stats"]), _p(out["mask"]),
+                                 _p(out["inlier_idx"]), _p(out["count"]), _st()), "pram_sor_select")
+    out["mask"], out["inlier_idx"] = out["mask"][:n], out["inlier_idx"][:n]
+    return out
