@@ -1150,6 +1150,31 @@ int pram_tri_triangulate(const double* norm, const float* keypoints, const doubl
                          unsigned long long seed, double min_tri_angle, double max_reproj_error, int* accept, double* xyz,
                          double* error, int* kept, int* best, unsigned char* entry_keep, double* entry_error, void* stream);
 
+/* Stage 2b, between pram_tri_verify and pram_tri_components: a match joins the track graph only when observations of third frames
+ * agree with it.  pram_tri_adjacency builds the rows' adjacency over `edges` [n_edges][2] as CSR: adj_off [n_rows + 1], adj
+ * [2 * n_edges] of which adj_off[n_rows] entries are written, every row's list ascending with duplicates kept, and row_frame
+ * [n_rows], each row's frame.  An edge counts when both ends are in [0, n_rows) and differ; any other, (-1, -1) included, is
+ * skipped and never dereferenced.  Degrees by integer atomics, a scan, a cursor fill and the tracks' sort of every list: the
+ * table is a function of the set of edges alone; no cap on a degree.  n_edges < 2^30, n_rows <= 2^30; workspace: 256-byte
+ * aligned.  Without edges adj_off is all zero and adj is not touched. */
+size_t pram_tri_adjacency_workspace_bytes(int n_rows, int n_edges);
+int pram_tri_adjacency(const int* edges, int n_edges, const int* frame_off, int n_frames, int n_rows, void* workspace,
+                       size_t workspace_bytes, int* adj_off, int* adj, int* row_frame, void* stream);
+
+/* One wave per edge (u, v).  support [n_edges] is 0 for an edge that does not count or whose rows share a frame.  Otherwise a
+ * witness is a distinct row w of adj(u) or adj(v) other than u and v, in a frame that is neither u's nor v's; a row in both
+ * lists, or twice in one, is one witness.  Of the pairs (u, v), (u, w), (v, w) the one whose rays (norm: offset 0.5) meet under
+ * the largest angle is taken, the first in that order on a tie; below min_tri_angle (radians) w does not confirm; X is the
+ * midpoint of that pair's rays as pram_tri_triangulate forms a hypothesis; w confirms when u, v and w all have positive depth at
+ * X and a reprojection error (pixels, full camera model, keypoint + 0.5) <= max_reproj_error.  support counts the confirming
+ * witnesses; edges_out [n_edges][2] is the edge where support >= min_support and (-1, -1) elsewhere, the layout
+ * pram_tri_components takes.  adj_off is clamped into [0, 2 * n_edges] and a w outside [0, n_rows) or with a frame outside the
+ * table is skipped, so a caller's own table cannot lead out of bounds.  Integer counts only: the result repeats bit for bit. */
+int pram_tri_support(const double* norm, const float* keypoints, const double* table, const int* cam_model,
+                     const double* cam_params, const int* edges, int n_edges, const int* adj_off, const int* adj,
+                     const int* row_frame, int n_frames, int n_rows, double min_tri_angle, double max_reproj_error,
+                     int min_support, int* support, int* edges_out, void* stream);
+
 /* ---- statistical outlier removal of a map's points (csrc/knn.hip; pram_amd/localization/outliers.py drives these) -------------
  * What RecMap.remove_statics_outlier (recmap.py:43-61) takes from Open3D's PointCloud::RemoveStatisticalOutliers, written from
  * knowledge of its source and NOT pinned to it (Open3D was never run beside this).  x [n][3] float64.

@@ -519,6 +519,182 @@ __global__ __launch_bounds__(64) void tri_triangulate_kernel(TriArgs g, const in
     }
 }
 
+// ---------------------------------------------------------------- stage 2b: the rows' adjacency and every edge's third-view support
+// adjacency: degrees by integer atomics, an exclusive scan, a cursor fill, then tri_sort_kernel over adj_off, so that the table is
+// a function of the edge set alone.  An edge counts when both ends are rows and differ.
+struct AdjWs { int* deg; int* cursor; int* bsum; int* count; };
+
+__device__ __forceinline__ bool edge_ok(int u, int v, int n_rows) { return u >= 0 && v >= 0 && u < n_rows && v < n_rows && u != v; }
+
+__global__ __launch_bounds__(256) void tri_adj_count_kernel(const int* __restrict__ edges, int n_edges, int n_rows, int* __restrict__ deg) {
+    const int e = blockIdx.x * 256 + threadIdx.x;
+    if (e >= n_edges) return;
+    const int u = edges[(size_t)e * 2], v = edges[(size_t)e * 2 + 1];
+    if (!edge_ok(u, v, n_rows)) return;
+    atomicAdd(&deg[u], 1);
+    atomicAdd(&deg[v], 1);
+}
+
+// block-local exclusive scans of the degrees over rows 0 .. n_rows (the last stands for the total), and the block's totals
+__global__ __launch_bounds__(SCAN) void tri_adj_scan_blocks_kernel(AdjWs ws, int n_rows, int* __restrict__ adj_off) {
+    __shared__ int wsum[4];
+    const int x = blockIdx.x * SCAN + threadIdx.x;
+    int total;
+    const int o = chunk_offset_n<4>(x < n_rows ? ws.deg[x] : 0, wsum, total);
+    if (x <= n_rows) adj_off[x] = o;
+    if (threadIdx.x == 0) ws.bsum[blockIdx.x] = total;
+}
+
+// one workgroup: the block totals -> their exclusive scan in place; count = n_rows, which the sort reads as its number of segments
+__global__ __launch_bounds__(256) void tri_adj_scan_totals_kernel(AdjWs ws, int n_blocks, int n_rows) {
+    __shared__ int wsum[4];
+    int base = 0;
+    for (int c0 = 0; c0 < n_blocks; c0 += 256) {
+        const int i = c0 + threadIdx.x;
+        int total;
+        const int o = chunk_offset_n<4>(i < n_blocks ? ws.bsum[i] : 0, wsum, total);
+        if (i < n_blocks) ws.bsum[i] = base + o;
+        base += total;
+    }
+    if (threadIdx.x == 0) ws.count[0] = n_rows;
+}
+
+__global__ __launch_bounds__(256) void tri_adj_offsets_kernel(AdjWs ws, const int* __restrict__ frame_off, int n_frames, int n_rows,
+                                                              int* __restrict__ adj_off, int* __restrict__ row_frame) {
+    const int x = blockIdx.x * 256 + threadIdx.x;
+    if (x > n_rows) return;
+    adj_off[x] += ws.bsum[x / SCAN];
+    if (x < n_rows) row_frame[x] = frame_of_row(frame_off, n_frames, x);
+}
+
+__global__ __launch_bounds__(256) void tri_adj_fill_kernel(const int* __restrict__ edges, int n_edges, int n_rows, AdjWs ws,
+                                                           const int* __restrict__ adj_off, int* __restrict__ adj) {
+    const int e = blockIdx.x * 256 + threadIdx.x;
+    if (e >= n_edges) return;
+    const int u = edges[(size_t)e * 2], v = edges[(size_t)e * 2 + 1];
+    if (!edge_ok(u, v, n_rows)) return;
+    const long long pu = (long long)adj_off[u] + atomicAdd(&ws.cursor[u], 1), pv = (long long)adj_off[v] + atomicAdd(&ws.cursor[v], 1);
+    if (pu >= 0 && pu < 2ll * n_edges) adj[pu] = v;
+    if (pv >= 0 && pv < 2ll * n_edges) adj[pv] = u;
+}
+
+// support: what stage 4 computes of an entry, here of a row r of frame f (the same formulas in the same order)
+struct SupArgs {
+    const double* norm; const float* kpts; const double* table; const int* cam_model; const double* cam_params;
+    const int* adj_off; const int* adj; const int* row_frame; int n_frames, n_rows, n_adj;
+};
+
+__device__ __forceinline__ V3 row_centre(const SupArgs& g, int f) {
+    const double* T = g.table + (size_t)f * FC;
+    return {T[12], T[13], T[14]};
+}
+
+__device__ __forceinline__ V3 row_ray(const SupArgs& g, int r, int f) {
+    const double* T = g.table + (size_t)f * FC;
+    const double u = g.norm[(size_t)r * 2], v = g.norm[(size_t)r * 2 + 1];
+    const double n = sqrt(u * u + v * v + 1.0);
+    const double x = u / n, y = v / n, z = 1.0 / n;
+    return {T[0] * x + T[3] * y + T[6] * z, T[1] * x + T[4] * y + T[7] * z, T[2] * x + T[5] * y + T[8] * z};
+}
+
+// positive depth and a squared pixel error <= thr2 through the full camera model, against keypoint + 0.5 (NaN compares false)
+__device__ __forceinline__ bool row_inlier(const SupArgs& g, int r, int f, V3 X, double thr2) {
+    const double* T = g.table + (size_t)f * FC;
+    const Cam c = cam_unify(g.cam_model[f], g.cam_params + (size_t)f * PRAM_POSE_CAM_PARAMS);
+    const double xc = T[0] * X.x + T[1] * X.y + T[2] * X.z + T[9];
+    const double yc = T[3] * X.x + T[4] * X.y + T[5] * X.z + T[10];
+    const double z = T[6] * X.x + T[7] * X.y + T[8] * X.z + T[11];
+    const double u = xc / z, v = yc / z;
+    double ud, vd;
+    distort(c, u, v, ud, vd);
+    const double r0 = c.fx * ud + c.cx - ((double)g.kpts[(size_t)r * 2] + 0.5);
+    const double r1 = c.fy * vd + c.cy - ((double)g.kpts[(size_t)r * 2 + 1] + 0.5);
+    return z > 0.0 && r0 * r0 + r1 * r1 <= thr2;
+}
+
+// the midpoint of the closest points of two rays, as a hypothesis of stage 4
+__device__ __forceinline__ V3 ray_midpoint(V3 C1, V3 d1, V3 C2, V3 d2) {
+    const V3 w = sub(C1, C2);
+    const double a = dot(d1, d1), b = dot(d1, d2), c = dot(d2, d2), d = dot(d1, w), e = dot(d2, w);
+    const double den = a * c - b * b;
+    const double s = (b * e - c * d) / den, u = (a * e - b * d) / den;
+    return {0.5 * ((C1.x + s * d1.x) + (C2.x + u * d2.x)), 0.5 * ((C1.y + s * d1.y) + (C2.y + u * d2.y)),
+            0.5 * ((C1.z + s * d1.z) + (C2.z + u * d2.z))};
+}
+
+// row r's list in adj, its offsets clamped into the table
+__device__ __forceinline__ void adj_range(const SupArgs& g, int r, int& beg, int& len) {
+    int b = g.adj_off[r], e = g.adj_off[r + 1];
+    b = b < 0 ? 0 : (b > g.n_adj ? g.n_adj : b);
+    e = e < b ? b : (e > g.n_adj ? g.n_adj : e);
+    beg = b; len = e - b;
+}
+
+constexpr int SUP_WAVES = 4;      // edges per workgroup
+
+// One wave per edge (u, v): the lanes stride over adj(u) followed by adj(v); a witness is a row of a third frame, counted once.
+// Of the pairs (u, v), (u, w), (v, w) the one whose rays meet under the largest angle (the first on a tie) gives X; w confirms the
+// edge when that angle reaches min_angle and u, v and w are inliers of X.  No LDS and no floating-point atomics.
+__global__ __launch_bounds__(64 * SUP_WAVES) void tri_support_kernel(SupArgs g, const int* __restrict__ edges, int n_edges, double min_angle,
+                                                                     double max_err, int min_support, int* __restrict__ support,
+                                                                     int* __restrict__ edges_out) {
+    const int e = blockIdx.x * SUP_WAVES + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (e >= n_edges) return;
+    const int u = edges[(size_t)e * 2], v = edges[(size_t)e * 2 + 1];
+    const double thr2 = max_err * max_err;
+    int cnt = 0;
+    bool ok = edge_ok(u, v, g.n_rows);
+    int fu = -1, fv = -1;
+    if (ok) {
+        fu = g.row_frame[u]; fv = g.row_frame[v];
+        ok = fu >= 0 && fu < g.n_frames && fv >= 0 && fv < g.n_frames && fu != fv;
+    }
+    if (ok) {      // uniform over the wave
+        const V3 Cu = row_centre(g, fu), Cv = row_centre(g, fv), du = row_ray(g, u, fu), dv = row_ray(g, v, fv);
+        const double a_uv = angle(du, dv);
+        int bu, nu, bv, nv;
+        adj_range(g, u, bu, nu);
+        adj_range(g, v, bv, nv);
+        const long long total = (long long)nu + nv;
+        for (long long k = lane; k < total; k += 64) {
+            int w;
+            if (k < nu) {
+                w = g.adj[bu + (int)k];
+                if (k > 0 && g.adj[bu + (int)k - 1] == w) continue;
+            } else {
+                const int j = (int)(k - nu);
+                w = g.adj[bv + j];
+                if (j > 0 && g.adj[bv + j - 1] == w) continue;
+                int lo = 0, hi = nu;      // the first element of adj(u) that is not below w
+                for (int it = 0; it < 32 && lo < hi; ++it) {
+                    const int mid = lo + ((hi - lo) >> 1);
+                    if (g.adj[bu + mid] < w) lo = mid + 1; else hi = mid;
+                }
+                if (lo < nu && g.adj[bu + lo] == w) continue;
+            }
+            if (w < 0 || w >= g.n_rows || w == u || w == v) continue;
+            const int fw = g.row_frame[w];
+            if (fw < 0 || fw >= g.n_frames || fw == fu || fw == fv) continue;
+            const V3 Cw = row_centre(g, fw), dw = row_ray(g, w, fw);
+            const double a_uw = angle(du, dw), a_vw = angle(dv, dw);
+            int pick = 0;
+            double best = a_uv;
+            if (a_uw > best) { pick = 1; best = a_uw; }
+            if (a_vw > best) { pick = 2; best = a_vw; }
+            if (!(best >= min_angle)) continue;
+            const V3 X = pick == 0 ? ray_midpoint(Cu, du, Cv, dv) : (pick == 1 ? ray_midpoint(Cu, du, Cw, dw) : ray_midpoint(Cv, dv, Cw, dw));
+            const bool iu = row_inlier(g, u, fu, X, thr2), iv = row_inlier(g, v, fv, X, thr2), iw = row_inlier(g, w, fw, X, thr2);
+            cnt += iu && iv && iw;
+        }
+    }
+    cnt = wave_sum_i32(cnt);
+    if (lane == 0) {
+        const bool keep = cnt >= min_support;
+        support[e] = cnt;
+        edges_out[(size_t)e * 2] = keep ? u : -1; edges_out[(size_t)e * 2 + 1] = keep ? v : -1;
+    }
+}
+
 int check_models(const int* cam_model_host, int n_frames, const char* what) {
     for (int f = 0; f < n_frames; ++f)
         if (cam_model_host[f] < PRAM_CAM_SIMPLE_PINHOLE || cam_model_host[f] > PRAM_CAM_OPENCV) {
@@ -646,4 +822,55 @@ extern "C" int pram_tri_triangulate(const double* norm, const float* keypoints, 
     hipLaunchKernelGGL(tri_triangulate_kernel, dim3(n_tracks), dim3(64), 0, (hipStream_t)stream, g, trk_off, trk_label, n_entries, trials, seed,
                        min_tri_angle, max_reproj_error, accept, xyz, error, kept, best, entry_keep, entry_error);
     return pram_launch_status("pram_tri_triangulate");
+}
+
+extern "C" size_t pram_tri_adjacency_workspace_bytes(int n_rows, int n_edges) {
+    if (n_rows < 0 || n_rows > MAX_ROWS || n_edges < 0 || n_edges >= MAX_ROWS) return 0;
+    const size_t n = (size_t)(n_rows > 0 ? n_rows : 1);
+    return 2 * align_up(n * sizeof(int)) + align_up((size_t)cdiv(n_rows + 1, SCAN) * sizeof(int)) + align_up(sizeof(int));
+}
+
+extern "C" int pram_tri_adjacency(const int* edges, int n_edges, const int* frame_off, int n_frames, int n_rows, void* workspace,
+                                  size_t workspace_bytes, int* adj_off, int* adj, int* row_frame, void* stream) {
+    PRAM_REQUIRE(edges && frame_off && workspace && adj_off && adj && row_frame, "pram_tri_adjacency: null pointer");
+    PRAM_REQUIRE(aligned(edges, 4) && aligned(frame_off, 4) && aligned(workspace, 256) && aligned(adj_off, 4) && aligned(adj, 4) &&
+                 aligned(row_frame, 4), "pram_tri_adjacency: misaligned pointer");
+    PRAM_REQUIRE(n_edges >= 0 && n_edges < MAX_ROWS && n_frames >= 0 && n_rows >= 0 && n_rows <= MAX_ROWS && (n_rows == 0 || n_frames >= 1),
+                 "pram_tri_adjacency: needs 0 <= n_edges < 2^30, n_frames >= 0, 0 <= n_rows <= 2^30 (0 without frames)");
+    PRAM_REQUIRE(workspace_bytes >= pram_tri_adjacency_workspace_bytes(n_rows, n_edges), "pram_tri_adjacency: workspace too small");
+    hipStream_t st = (hipStream_t)stream;
+    const size_t n = (size_t)(n_rows > 0 ? n_rows : 1), stride = align_up(n * sizeof(int));
+    const int nb = cdiv(n_rows + 1, SCAN);
+    char* w = static_cast<char*>(workspace);
+    AdjWs ws = {reinterpret_cast<int*>(w), reinterpret_cast<int*>(w + stride), reinterpret_cast<int*>(w + 2 * stride),
+                reinterpret_cast<int*>(w + 2 * stride + align_up((size_t)nb * sizeof(int)))};
+    if (hipMemsetAsync(ws.deg, 0, 2 * stride, st) != hipSuccess) return pram_launch_status("pram_tri_adjacency");      // deg and cursor
+    if (n_edges && n_rows) hipLaunchKernelGGL(tri_adj_count_kernel, dim3(cdiv(n_edges, 256)), dim3(256), 0, st, edges, n_edges, n_rows, ws.deg);
+    hipLaunchKernelGGL(tri_adj_scan_blocks_kernel, dim3(nb), dim3(SCAN), 0, st, ws, n_rows, adj_off);
+    hipLaunchKernelGGL(tri_adj_scan_totals_kernel, dim3(1), dim3(256), 0, st, ws, nb, n_rows);
+    hipLaunchKernelGGL(tri_adj_offsets_kernel, dim3(cdiv(n_rows + 1, 256)), dim3(256), 0, st, ws, frame_off, n_frames, n_rows, adj_off, row_frame);
+    if (n_edges && n_rows) {
+        hipLaunchKernelGGL(tri_adj_fill_kernel, dim3(cdiv(n_edges, 256)), dim3(256), 0, st, edges, n_edges, n_rows, ws, adj_off, adj);
+        hipLaunchKernelGGL(tri_sort_kernel, dim3(n_rows), dim3(64), 0, st, ws.count, adj_off, adj, 2 * n_edges);
+    }
+    return pram_launch_status("pram_tri_adjacency");
+}
+
+extern "C" int pram_tri_support(const double* norm, const float* keypoints, const double* table, const int* cam_model,
+                                const double* cam_params, const int* edges, int n_edges, const int* adj_off, const int* adj,
+                                const int* row_frame, int n_frames, int n_rows, double min_tri_angle, double max_reproj_error,
+                                int min_support, int* support, int* edges_out, void* stream) {
+    PRAM_REQUIRE(norm && keypoints && table && cam_model && cam_params && edges && adj_off && adj && row_frame && support && edges_out,
+                 "pram_tri_support: null pointer");
+    PRAM_REQUIRE(aligned(norm, 8) && aligned(keypoints, 4) && aligned(table, 8) && aligned(cam_model, 4) && aligned(cam_params, 8) &&
+                 aligned(edges, 4) && aligned(adj_off, 4) && aligned(adj, 4) && aligned(row_frame, 4) && aligned(support, 4) &&
+                 aligned(edges_out, 4), "pram_tri_support: misaligned pointer");
+    PRAM_REQUIRE(n_edges >= 0 && n_edges < MAX_ROWS && n_frames >= 0 && n_rows >= 0 && n_rows <= MAX_ROWS && min_support >= 0 &&
+                 min_tri_angle >= 0.0 && max_reproj_error > 0.0,
+                 "pram_tri_support: needs 0 <= n_edges < 2^30, n_frames >= 0, 0 <= n_rows <= 2^30, min_support >= 0, min_tri_angle >= 0, max_reproj_error > 0");
+    if (n_edges == 0) return PRAM_OK;
+    const SupArgs g = {norm, keypoints, table, cam_model, cam_params, adj_off, adj, row_frame, n_frames, n_rows, 2 * n_edges};
+    hipLaunchKernelGGL(tri_support_kernel, dim3(cdiv(n_edges, SUP_WAVES)), dim3(64 * SUP_WAVES), 0, (hipStream_t)stream, g, edges, n_edges,
+                       min_tri_angle, max_reproj_error, min_support, support, edges_out);
+    return pram_launch_status("pram_tri_support");
 }

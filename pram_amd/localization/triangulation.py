@@ -8,7 +8,13 @@ Reference: localization/triangulation.py (hloc's), which every dataset of the re
     :func:`build_tracks` and :func:`triangulate_tracks`.
 :func:`triangulate_map` runs all of it and returns what mapbuild.build_store_inputs and labelling.label_points take.  The
 kernels are csrc/triangulate.hip; torch here is plumbing: uploads, the components' done flag, the table sizes
-and one read-back of the results at the end.  Nothing here has been timed.
+and one read-back of the results at the end.  profiles/triangulation_timing.md has the time of every stage.
+
+Between verification and the tracks an optional stage 2b (:func:`support_matches`, ``min_support`` of :func:`triangulate_map`)
+keeps a match only when ``min_support`` observations in third frames agree with it: a wrong match that lies on the epipolar line
+passes verification by construction, and a single one joins two real tracks.  It is off by default (``min_support=0``);
+profiles/triangulation_support.md has what it does to a simulated map and which value to use.  :func:`track_conflicts` counts,
+per track, the frames seen twice: the sign that components are glued.
 
 The stages share one device-resident table of frames (:func:`frame_table`): the keypoints of all frames concatenated plus
 frame_off, as StoreBase lays them out; a "row" is a keypoint's index in that table.
@@ -18,7 +24,10 @@ Where this differs from the reference, on purpose:
     search from a seed observation; there is no Merge, Complete or Retriangulate and no bundle adjustment beyond a point-only
     refit (the poses are given and stay).  The trial budget is fixed (every pair of a track's entries up to ``trials`` of them,
     else ``trials`` sampled pairs) instead of confidence-driven.  A component that wrong matches glued from two real points yields
-    one of them at most: the hypothesis with most inliers wins and the other point's entries fall out as outliers.
+    one of them at most: the hypothesis with most inliers wins and the other point's entries fall out as outliers.  Stage 2b
+    removes most such matches before they join anything, where COLMAP accepts an observation only when it reprojects; a match
+    that no third frame sees (a two-view track) cannot be confirmed and falls out with ``min_support`` >= 1, as it would later
+    at the reference's own min_obs / obs_thresh of 3.  A component that stays glued after the filter still yields one point.
   * pixel offsets: verification reads the keypoints as stored (offset 0), triangulation adds 0.5, as in the reference
     (geometric_verification passes get_keypoints' array, import_features adds 0.5 for COLMAP).  The inconsistency is kept.
   * out-of-range indices: a match with a keypoint index outside its frame is dropped, where the reference would raise.
@@ -39,6 +48,7 @@ from pram_amd.localization import formats
 VERIFY_DEFAULTS = dict(max_error=4.0)      # geometric_verification's
 TRI_DEFAULTS = dict(trials=128, seed=0, min_tri_angle=1.5, max_reproj_error=4.0)      # degrees and pixels: COLMAP's
 DEFAULTS = {**VERIFY_DEFAULTS, **TRI_DEFAULTS}
+SUPPORT_DEFAULTS = dict(min_support=0)      # stage 2b's confirming third views per match; 0: the stage does not run
 CC_GROUP = 8      # rounds of the components enqueued per look at the done flag
 
 
@@ -212,6 +222,59 @@ def build_tracks(table: dict, edges) -> dict:
 
 
 @torch.no_grad()
+def _support(table: dict, edges: torch.Tensor, n_edges: int, p: dict) -> dict:
+    a = ops.tri_adjacency(edges, n_edges, table["frame_off"], table["n_frames"], table["n_rows"])
+    out = ops.tri_support(table["norm05"], table["keypoints"], table["frames"], table["cam_model"], table["cam_params"], edges, n_edges,
+                          a["adj_off"], a["adj"], a["row_frame"], table["n_frames"], table["n_rows"],
+                          min_tri_angle=float(np.deg2rad(p["min_tri_angle"])), max_reproj_error=p["max_reproj_error"], min_support=p["min_support"])
+    out.update(a)
+    return out
+
+
+def _min_support(p: dict) -> dict:
+    if int(p["min_support"]) != p["min_support"] or p["min_support"] < 0:
+        raise ValueError("min_support: an integer >= 0")
+    return {**p, "min_support": int(p["min_support"])}
+
+
+def adjacency(table: dict, edges) -> dict:
+    """edges: int [n, 2] rows of the table (:func:`build_tracks`') -> on the host the rows' adjacency as stage 2b reads it:
+    ``adj_off`` int32 [n_rows + 1], ``adj`` int32 [adj_off[-1]] (every row's neighbours ascending, one entry per edge, so a match
+    given twice is there twice) and ``row_frame`` int32 [n_rows]."""
+    e = _edges(edges)
+    a = ops.tri_adjacency(_up(e, table["keypoints"].device), e.shape[0], table["frame_off"], table["n_frames"], table["n_rows"])
+    off = a["adj_off"][:table["n_rows"] + 1].cpu().numpy()
+    return {"adj_off": off, "adj": a["adj"][:int(off[-1])].cpu().numpy(), "row_frame": a["row_frame"][:table["n_rows"]].cpu().numpy()}
+
+
+def support_matches(table: dict, edges, **params) -> dict:
+    """Stage 2b on its own.  edges: int [n, 2] rows joined by a verified match -> on the host ``support`` int32 [n], the number of
+    observations in third frames that confirm the match (a neighbour w of either end, in a frame of neither: of the three pairs of
+    rays the one under the largest angle gives a point, and the two ends and w all reproject to it within max_reproj_error, that
+    angle being min_tri_angle at least), ``keep`` (bool, support >= min_support) and ``edges`` int32 [n, 2], (-1, -1) where keep is
+    false.  params: min_support (1 here), min_tri_angle (degrees), max_reproj_error (pixels)."""
+    p = _min_support(_params("support_matches", params, dict(min_support=1, min_tri_angle=TRI_DEFAULTS["min_tri_angle"],
+                                                             max_reproj_error=TRI_DEFAULTS["max_reproj_error"])))
+    e = _edges(edges)
+    out = _support(table, _up(e, table["keypoints"].device), e.shape[0], p)
+    sup = out["support"][:e.shape[0]].cpu().numpy()
+    return {"support": sup, "keep": sup >= p["min_support"], "edges": out["edges"][:e.shape[0]].cpu().numpy()}
+
+
+def track_conflicts(tracks: dict) -> np.ndarray:
+    """tracks: :func:`build_tracks`' dict -> int64 [T]: per track the number of frames that hold more than one of its entries.  A
+    point is seen once per frame, so a track with conflicts is two points or more that wrong matches glued together (numpy, on
+    the host)."""
+    off, frame = np.asarray(tracks["trk_off"], dtype=np.int64).reshape(-1), np.asarray(tracks["trk_frame"], dtype=np.int64).reshape(-1)
+    T = off.shape[0] - 1
+    if T <= 0 or frame.shape[0] == 0:
+        return np.zeros(max(T, 0), dtype=np.int64)
+    trk = np.repeat(np.arange(T), np.diff(off))
+    _, first, count = np.unique(trk * (int(frame.max()) + 1) + frame, return_index=True, return_counts=True)
+    return np.bincount(trk[first][count > 1], minlength=T).astype(np.int64)
+
+
+@torch.no_grad()
 def _triangulate(table: dict, t: dict, p: dict) -> dict:
     return ops.tri_triangulate(table["norm05"], table["keypoints"], table["frames"], table["cam_model"], table["cam_params"], t["trk_off"],
                                t["trk_label"], t["trk_row"], t["trk_frame"], t["n_tracks"], t["n_entries"], table["n_frames"], table["n_rows"],
@@ -251,11 +314,15 @@ def triangulate_map(frames: Sequence[dict], cameras: Sequence, poses, pairs, mat
       ``pair_index`` and ``inlier_ratio`` as verify_matches gives them.
     With ``xyz = dict(zip(point_ids.tolist(), point3D_xyzs))``, labelling.label_points(tracks, xyz, k, device) and
     mapbuild.build_store_inputs(frames, tracks, landmarks, xyz, device) a ReferenceStore follows with no further tool.
-    params: DEFAULTS.  The stages run back to back on the device; the results are read back once, at the end."""
-    p = _params("triangulate_map", params, DEFAULTS)
+    params: DEFAULTS and SUPPORT_DEFAULTS.  With ``min_support`` >= 1 the verified matches go through stage 2b
+    (:func:`support_matches`) before the tracks, and the dict also holds ``support``: per processed pair an int32 array over its
+    matches, -1 where verification had dropped the match.  The stages run back to back on the device; the results are read back
+    once, at the end."""
+    p = _min_support(_params("triangulate_map", params, {**DEFAULTS, **SUPPORT_DEFAULTS}))
     table = frame_table(frames, cameras, poses, device)
     v = _verify(table, pairs, matches, p["max_error"])
-    t = _tracks(table, v["edges"], v["n_matches"])
+    sup = _support(table, v["edges"], v["n_matches"], p) if p["min_support"] > 0 else None
+    t = _tracks(table, v["edges"] if sup is None else sup["edges"], v["n_matches"])
     out = _triangulate(table, t, p)
     # ---- the one read-back
     T, E, Pn = t["n_tracks"], t["n_entries"], len(v["pair_index"])
@@ -270,6 +337,10 @@ def triangulate_map(frames: Sequence[dict], cameras: Sequence, poses, pairs, mat
     res = map_tables(frame_ids, table["frame_off_host"], {"trk_off": off, "trk_row": row, "trk_frame": frame, "trk_kpt": kpt},
                      {"accept": accept, "xyz": xyz, "error": err, "entry_keep": keep})
     res.update(pair_index=v["pair_index"], inlier_ratio=ratio)
+    if sup is not None:
+        M, m_off = v["n_matches"], v["match_off"]
+        support = np.where(v["keep"][:M].cpu().numpy().astype(bool), sup["support"][:M].cpu().numpy(), -1).astype(np.int32)
+        res["support"] = [support[a:b] for a, b in zip(m_off[:-1], m_off[1:])]
     return res
 
 

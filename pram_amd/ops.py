@@ -2368,6 +2368,52 @@ def tri_triangulate(norm: torch.Tensor, keypoints: torch.Tensor, table: torch.Te
     return out
 
 
+def tri_adjacency(edges: torch.Tensor, n_edges: int, frame_off: torch.Tensor, n_frames: int, n_rows: int,
+                  workspace: Optional[torch.Tensor] = None) -> dict:
+    """edges int32 [n_edges, 2] rows (an edge with an end outside [0, n_rows) or with equal ends is skipped) -> the rows' adjacency
+    on the device: adj_off int32 [n_rows + 1], adj int32 [2 * n_edges] (adj_off[n_rows] of them written, every row's list
+    ascending, duplicates kept) and row_frame int32 [n_rows].  ``workspace``: uint8, at least
+    pram_tri_adjacency_workspace_bytes; None allocates it."""
+    L = _lib.load()
+    _tri_chk(((edges, "edges", torch.int32), (frame_off, "frame_off", torch.int32)))
+    m, F, n = int(n_edges), int(n_frames), int(n_rows)
+    assert edges.numel() >= 2 * m and frame_off.numel() >= F + 1
+    dev = edges.device
+    need = int(L.pram_tri_adjacency_workspace_bytes(n, m))
+    if need == 0:
+        raise _lib.PramHipError("pram_tri_adjacency: more than 2^30 rows or 2^30 - 1 edges")
+    if workspace is None:
+        workspace = torch.empty(need, device=dev, dtype=torch.uint8)
+    _chk(workspace, "workspace", torch.uint8)
+    i32 = lambda k: torch.empty(max(k, 1), device=dev, dtype=torch.int32)
+    out = {"adj_off": i32(n + 1), "adj": i32(2 * m), "row_frame": i32(n)}
+    _lib.check(L.pram_tri_adjacency(_p(edges), m, _p(frame_off), F, n, _p(workspace), workspace.numel(), _p(out["adj_off"]), _p(out["adj"]),
+                                    _p(out["row_frame"]), _st()), "pram_tri_adjacency")
+    return out
+
+
+def tri_support(norm: torch.Tensor, keypoints: torch.Tensor, table: torch.Tensor, cam_model: torch.Tensor, cam_params: torch.Tensor,
+                edges: torch.Tensor, n_edges: int, adj_off: torch.Tensor, adj: torch.Tensor, row_frame: torch.Tensor, n_frames: int,
+                n_rows: int, min_tri_angle: float = 0.026179938779914945, max_reproj_error: float = 4.0, min_support: int = 1) -> dict:
+    """norm: tri_normalize with offset 0.5; adj_off / adj / row_frame: tri_adjacency over the same edges -> support int32 [n_edges]
+    (the witnesses of third frames that confirm the edge) and edges int32 [n_edges, 2]: the edge where support >= min_support,
+    (-1, -1) elsewhere.  min_tri_angle in radians."""
+    L = _lib.load()
+    _tri_chk(((norm, "norm", torch.float64), (keypoints, "keypoints", torch.float32), (table, "table", torch.float64),
+              (cam_model, "cam_model", torch.int32), (cam_params, "cam_params", torch.float64), (edges, "edges", torch.int32),
+              (adj_off, "adj_off", torch.int32), (adj, "adj", torch.int32), (row_frame, "row_frame", torch.int32)))
+    m, F, n = int(n_edges), int(n_frames), int(n_rows)
+    assert norm.numel() >= 2 * n and keypoints.numel() >= 2 * n and table.numel() >= TRI_FRAME_COLS * F and cam_model.numel() >= F
+    assert cam_params.numel() >= POSE_CAM_PARAMS * F and edges.numel() >= 2 * m and adj_off.numel() >= n + 1 and adj.numel() >= 2 * m
+    assert row_frame.numel() >= n
+    dev = norm.device
+    out = {"support": torch.empty(max(m, 1), device=dev, dtype=torch.int32), "edges": torch.empty(max(m, 1), 2, device=dev, dtype=torch.int32)}
+    _lib.check(L.pram_tri_support(_p(norm), _p(keypoints), _p(table), _p(cam_model), _p(cam_params), _p(edges), m, _p(adj_off), _p(adj),
+                                  _p(row_frame), F, n, float(min_tri_angle), float(max_reproj_error), int(min_support), _p(out["support"]),
+                                  _p(out["edges"]), _st()), "pram_tri_support")
+    return out
+
+
 # ---- statistical outlier removal (csrc/knn.hip; pram_amd/localization/outliers.py drives these) -------------------------------
 KNN_TILE, KNN_MAX_K, SOR_BLOCK = 1024, 32, 1024      # include/pram_hip.h
 SOR_MEAN, SOR_STD, SOR_THRESHOLD, SOR_NV = 0, 1, 2, 3      # entries of the statistics
