@@ -1175,6 +1175,24 @@ int pram_tri_support(const double* norm, const float* keypoints, const double* t
                      const int* row_frame, int n_frames, int n_rows, double min_tri_angle, double max_reproj_error,
                      int min_support, int* support, int* edges_out, void* stream);
 
+/* Between one round's pram_tri_triangulate and the next round's pram_tri_components: what a round left over becomes the next
+ * round's match graph.  state [n_rows] holds one byte per row, PRAM_TRI_ROW_*; first == 1 sets every row DEAD before anything
+ * else.  Marking, one thread per entry of the round's track table (trk_off [n_tracks + 1], trk_row [n_entries]) with its results
+ * (accept [n_tracks], entry_keep [n_entries] of pram_tri_triangulate): the entry's row becomes TAKEN when its track was accepted
+ * and the entry kept, FREE when the track was accepted and the entry not kept, DEAD when the track was not accepted (it would
+ * come back identical).  The thread finds its track by bisection in trk_off; offsets are clamped into [0, n_entries], an entry
+ * outside its track's clamped range and a row outside [0, n_rows) are skipped.  A table of pram_tri_tracks holds a row once, so
+ * every byte has one writer; in a caller's table that names a row twice one of the writes stays.  Filtering, one thread per edge
+ * of `edges` [n_edges][2]: edges_out [n_edges][2] is the edge when both ends are in [0, n_rows) and FREE, and (-1, -1)
+ * otherwise; n_live [1] (device) counts the survivors, by a ballot per wave and one integer atomic.  Bytes and integers only:
+ * the result repeats bit for bit.  n_entries, n_rows <= 2^30, n_edges < 2^30. */
+#define PRAM_TRI_ROW_FREE 0
+#define PRAM_TRI_ROW_TAKEN 1
+#define PRAM_TRI_ROW_DEAD 2
+int pram_tri_split(const int* trk_off, const int* trk_row, int n_tracks, int n_entries, const int* accept,
+                   const unsigned char* entry_keep, const int* edges, int n_edges, int n_rows, int first, unsigned char* state,
+                   int* edges_out, int* n_live, void* stream);
+
 /* ---- statistical outlier removal of a map's points (csrc/knn.hip; pram_amd/localization/outliers.py drives these) -------------
  * What RecMap.remove_statics_outlier (recmap.py:43-61) takes from Open3D's PointCloud::RemoveStatisticalOutliers, written from
  * knowledge of its source and NOT pinned to it (Open3D was never run beside this).  x [n][3] float64.

@@ -695,6 +695,54 @@ __global__ __launch_bounds__(64 * SUP_WAVES) void tri_support_kernel(SupArgs g, 
     }
 }
 
+// ---------------------------------------------------------------- split: mark the rows a round used, keep the edges between free rows
+constexpr unsigned char ROW_FREE = PRAM_TRI_ROW_FREE, ROW_TAKEN = PRAM_TRI_ROW_TAKEN, ROW_DEAD = PRAM_TRI_ROW_DEAD;
+
+__global__ __launch_bounds__(256) void tri_split_init_kernel(unsigned char* __restrict__ state, int n_rows, int first, int* __restrict__ n_live) {
+    const int x = blockIdx.x * 256 + threadIdx.x;
+    if (first && x < n_rows) state[x] = ROW_DEAD;
+    if (x == 0) n_live[0] = 0;
+}
+
+__device__ __forceinline__ int clamp_off(int o, int n) { return o < 0 ? 0 : (o > n ? n : o); }
+
+// One thread per entry: its track is the last whose (clamped) offset is not beyond it; 32 steps cover every n_tracks an int
+// holds.  A row is in one track, so every byte has one writer.
+__global__ __launch_bounds__(256) void tri_split_mark_kernel(const int* __restrict__ trk_off, const int* __restrict__ trk_row, int n_tracks,
+                                                             int n_entries, const int* __restrict__ accept,
+                                                             const unsigned char* __restrict__ entry_keep, int n_rows,
+                                                             unsigned char* __restrict__ state) {
+    const int e = blockIdx.x * 256 + threadIdx.x;
+    if (e >= n_entries) return;
+    int lo = 0, hi = n_tracks - 1;
+    for (int it = 0; it < 32 && lo < hi; ++it) {
+        const int mid = lo + ((hi - lo + 1) >> 1);
+        if (clamp_off(trk_off[mid], n_entries) <= e) lo = mid; else hi = mid - 1;
+    }
+    const int beg = clamp_off(trk_off[lo], n_entries);
+    int end = clamp_off(trk_off[lo + 1], n_entries);
+    end = end < beg ? beg : end;
+    if (e < beg || e >= end) return;
+    const int r = trk_row[e];
+    if (r < 0 || r >= n_rows) return;
+    state[r] = accept[lo] ? (entry_keep[e] ? ROW_TAKEN : ROW_FREE) : ROW_DEAD;
+}
+
+// One thread per edge; the survivors of a wave are counted by a ballot and added by its first lane.
+__global__ __launch_bounds__(256) void tri_split_filter_kernel(const int* __restrict__ edges, int n_edges, int n_rows,
+                                                               const unsigned char* __restrict__ state, int* __restrict__ edges_out,
+                                                               int* n_live) {
+    const int e = blockIdx.x * 256 + threadIdx.x;
+    bool live = false;
+    if (e < n_edges) {
+        const int u = edges[(size_t)e * 2], v = edges[(size_t)e * 2 + 1];
+        live = u >= 0 && v >= 0 && u < n_rows && v < n_rows && state[u] == ROW_FREE && state[v] == ROW_FREE;
+        edges_out[(size_t)e * 2] = live ? u : -1; edges_out[(size_t)e * 2 + 1] = live ? v : -1;
+    }
+    const int cnt = __popcll(__ballot(live));
+    if ((threadIdx.x & 63) == 0 && cnt) atomicAdd(n_live, cnt);
+}
+
 int check_models(const int* cam_model_host, int n_frames, const char* what) {
     for (int f = 0; f < n_frames; ++f)
         if (cam_model_host[f] < PRAM_CAM_SIMPLE_PINHOLE || cam_model_host[f] > PRAM_CAM_OPENCV) {
@@ -873,4 +921,23 @@ extern "C" int pram_tri_support(const double* norm, const float* keypoints, cons
     hipLaunchKernelGGL(tri_support_kernel, dim3(cdiv(n_edges, SUP_WAVES)), dim3(64 * SUP_WAVES), 0, (hipStream_t)stream, g, edges, n_edges,
                        min_tri_angle, max_reproj_error, min_support, support, edges_out);
     return pram_launch_status("pram_tri_support");
+}
+
+extern "C" int pram_tri_split(const int* trk_off, const int* trk_row, int n_tracks, int n_entries, const int* accept,
+                              const unsigned char* entry_keep, const int* edges, int n_edges, int n_rows, int first, unsigned char* state,
+                              int* edges_out, int* n_live, void* stream) {
+    PRAM_REQUIRE(trk_off && trk_row && accept && entry_keep && edges && state && edges_out && n_live, "pram_tri_split: null pointer");
+    PRAM_REQUIRE(aligned(trk_off, 4) && aligned(trk_row, 4) && aligned(accept, 4) && aligned(edges, 4) && aligned(edges_out, 4) &&
+                 aligned(n_live, 4), "pram_tri_split: misaligned pointer");
+    PRAM_REQUIRE(n_tracks >= 0 && n_entries >= 0 && n_entries <= MAX_ROWS && n_edges >= 0 && n_edges < MAX_ROWS && n_rows >= 0 && n_rows <= MAX_ROWS &&
+                 (first == 0 || first == 1),
+                 "pram_tri_split: needs n_tracks >= 0, 0 <= n_entries <= 2^30, 0 <= n_edges < 2^30, 0 <= n_rows <= 2^30, first 0 or 1");
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(tri_split_init_kernel, dim3(cdiv(first && n_rows > 0 ? n_rows : 1, 256)), dim3(256), 0, st, state, n_rows, first, n_live);
+    if (n_tracks && n_entries && n_rows)
+        hipLaunchKernelGGL(tri_split_mark_kernel, dim3(cdiv(n_entries, 256)), dim3(256), 0, st, trk_off, trk_row, n_tracks, n_entries, accept,
+                           entry_keep, n_rows, state);
+    if (n_edges)
+        hipLaunchKernelGGL(tri_split_filter_kernel, dim3(cdiv(n_edges, 256)), dim3(256), 0, st, edges, n_edges, n_rows, state, edges_out, n_live);
+    return pram_launch_status("pram_tri_split");
 }

@@ -16,6 +16,16 @@ passes verification by construction, and a single one joins two real tracks.  It
 profiles/triangulation_support.md has what it does to a simulated map and which value to use.  :func:`track_conflicts` counts,
 per track, the frames seen twice: the sign that components are glued.
 
+After stage 4 an optional number of further rounds (``split_rounds`` of :func:`triangulate_map`, :func:`split_edges`) takes apart
+what stayed glued: sequential RANSAC over the match graph.  Every row has a state: TAKEN (a kept entry of an accepted track),
+FREE (an entry of an accepted track that fell out as an outlier) or DEAD (everything else: rows of no track, and rows of a track
+that was not accepted, which would come back identical).  A round keeps the edges of round 0 whose two ends are FREE, runs the
+components, the tracks and stage 4 on them again, and its accepted tracks are further points.  A TAKEN or DEAD row never
+returns, so every round with a track uses up two FREE rows at least; the rounds end at ``split_rounds``, or sooner when no edge
+or no track is left.  It is off by default (``split_rounds=0``); profiles/triangulation_split.md has what each round recovers on
+a simulated map, what it costs and which value to use.  It goes with stage 2b and does not replace it: one giant component
+gives about one point per round.
+
 The stages share one device-resident table of frames (:func:`frame_table`): the keypoints of all frames concatenated plus
 frame_off, as StoreBase lays them out; a "row" is a keypoint's index in that table.
 
@@ -27,7 +37,8 @@ Where this differs from the reference, on purpose:
     one of them at most: the hypothesis with most inliers wins and the other point's entries fall out as outliers.  Stage 2b
     removes most such matches before they join anything, where COLMAP accepts an observation only when it reprojects; a match
     that no third frame sees (a two-view track) cannot be confirmed and falls out with ``min_support`` >= 1, as it would later
-    at the reference's own min_obs / obs_thresh of 3.  A component that stays glued after the filter still yields one point.
+    at the reference's own min_obs / obs_thresh of 3.  A component that stays glued after the filter yields one point per
+    component per round: one with ``split_rounds=0``, and with further rounds the points that its outliers still support.
   * pixel offsets: verification reads the keypoints as stored (offset 0), triangulation adds 0.5, as in the reference
     (geometric_verification passes get_keypoints' array, import_features adds 0.5 for COLMAP).  The inconsistency is kept.
   * out-of-range indices: a match with a keypoint index outside its frame is dropped, where the reference would raise.
@@ -49,6 +60,7 @@ VERIFY_DEFAULTS = dict(max_error=4.0)      # geometric_verification's
 TRI_DEFAULTS = dict(trials=128, seed=0, min_tri_angle=1.5, max_reproj_error=4.0)      # degrees and pixels: COLMAP's
 DEFAULTS = {**VERIFY_DEFAULTS, **TRI_DEFAULTS}
 SUPPORT_DEFAULTS = dict(min_support=0)      # stage 2b's confirming third views per match; 0: the stage does not run
+SPLIT_DEFAULTS = dict(split_rounds=0)      # further rounds over the entries that fell out as outliers; 0: none
 CC_GROUP = 8      # rounds of the components enqueued per look at the done flag
 
 
@@ -237,6 +249,12 @@ def _min_support(p: dict) -> dict:
     return {**p, "min_support": int(p["min_support"])}
 
 
+def _split_rounds(p: dict) -> dict:
+    if int(p["split_rounds"]) != p["split_rounds"] or p["split_rounds"] < 0:
+        raise ValueError("split_rounds: an integer >= 0")
+    return {**p, "split_rounds": int(p["split_rounds"])}
+
+
 def adjacency(table: dict, edges) -> dict:
     """edges: int [n, 2] rows of the table (:func:`build_tracks`') -> on the host the rows' adjacency as stage 2b reads it:
     ``adj_off`` int32 [n_rows + 1], ``adj`` int32 [adj_off[-1]] (every row's neighbours ascending, one entry per edge, so a match
@@ -304,6 +322,33 @@ def triangulate_tracks(table: dict, tracks: dict, **params) -> dict:
 
 
 @torch.no_grad()
+def _split(table: dict, edges: torch.Tensor, n_edges: int, t: dict, out: dict, state) -> dict:
+    return ops.tri_split(t["trk_off"], t["trk_row"], t["n_tracks"], t["n_entries"], out["accept"], out["entry_keep"], edges, n_edges,
+                         table["n_rows"], state)
+
+
+def split_edges(table: dict, edges, tracks: dict, tri: dict, state=None) -> dict:
+    """The step between two rounds on its own.  edges: int [n, 2], the rows round 0's tracks were built from; tracks, tri: the last
+    round's :func:`build_tracks` and :func:`triangulate_tracks`; state: uint8 [n_rows] from the round before, None before round 1
+    (every row DEAD) -> on the host ``state`` uint8 [n_rows] (ops.TRI_ROW_FREE / TAKEN / DEAD) after marking the round's entries,
+    ``edges`` int32 [n, 2], (-1, -1) where an end is not FREE, and ``n_live``, the number of edges that stay."""
+    dev, n = table["keypoints"].device, table["n_rows"]
+    e = _edges(edges)
+    off = np.asarray(tracks["trk_off"], dtype=np.int32).reshape(-1)
+    T, E = off.shape[0] - 1, int(np.asarray(tracks["trk_row"]).shape[0])
+    t = {"trk_off": _up(off, dev), "trk_row": _up(np.asarray(tracks["trk_row"], dtype=np.int32).reshape(-1), dev), "n_tracks": T, "n_entries": E}
+    res = {"accept": _up(np.asarray(tri["accept"]).astype(np.int32).reshape(-1), dev),
+           "entry_keep": _up(np.asarray(tri["entry_keep"]).astype(np.uint8).reshape(-1), dev)}
+    if state is not None:
+        state = np.asarray(state, dtype=np.uint8).reshape(-1)
+        if state.shape[0] != n:
+            raise ValueError(f"state: expected {n} rows, got {state.shape[0]}")
+        state = _up(state, dev)
+    out = _split(table, _up(e, dev), e.shape[0], t, res, state)
+    return {"state": out["state"][:n].cpu().numpy(), "edges": out["edges"][:e.shape[0]].cpu().numpy(), "n_live": int(out["n_live"].item())}
+
+
+@torch.no_grad()
 def triangulate_map(frames: Sequence[dict], cameras: Sequence, poses, pairs, matches: Sequence, device, **params) -> dict:
     """frames, cameras, poses: :func:`frame_table`'s; pairs [Pn, 2] positions in ``frames`` and matches, per pair int [m, 2]:
     :func:`verify_matches`' (from :func:`pair_matches`, for instance) -> a dict:
@@ -317,25 +362,53 @@ def triangulate_map(frames: Sequence[dict], cameras: Sequence, poses, pairs, mat
     params: DEFAULTS and SUPPORT_DEFAULTS.  With ``min_support`` >= 1 the verified matches go through stage 2b
     (:func:`support_matches`) before the tracks, and the dict also holds ``support``: per processed pair an int32 array over its
     matches, -1 where verification had dropped the match.  The stages run back to back on the device; the results are read back
-    once, at the end."""
-    p = _min_support(_params("triangulate_map", params, {**DEFAULTS, **SUPPORT_DEFAULTS}))
+    once, at the end.
+    params also SPLIT_DEFAULTS.  With ``split_rounds`` = R >= 1 up to R further rounds run over the entries that fell out of
+    accepted tracks (the module docstring; :func:`split_edges` is the step between two rounds).  Round 0's points come first, so
+    the first of them and their tracks are what ``split_rounds=0`` gives, bit for bit; then round 1's accepted tracks in track
+    order, and so on.  The dict also holds ``point_round`` int32 [P] and ``split``: int64 arrays over the further rounds that were
+    begun, ``live_edges`` (the edges between FREE rows; a round that finds none ends the rounds), ``tracks`` and ``points``."""
+    p = _split_rounds(_min_support(_params("triangulate_map", params, {**DEFAULTS, **SUPPORT_DEFAULTS, **SPLIT_DEFAULTS})))
     table = frame_table(frames, cameras, poses, device)
     v = _verify(table, pairs, matches, p["max_error"])
     sup = _support(table, v["edges"], v["n_matches"], p) if p["min_support"] > 0 else None
-    t = _tracks(table, v["edges"] if sup is None else sup["edges"], v["n_matches"])
+    edges = v["edges"] if sup is None else sup["edges"]
+    t = _tracks(table, edges, v["n_matches"])
     out = _triangulate(table, t, p)
+    rounds, live, state = [(t, out)], [], None
+    for _ in range(p["split_rounds"]):      # every round on the device; of a round only its sizes are read
+        sp = _split(table, edges, v["n_matches"], t, out, state)
+        state = sp["state"]
+        live.append(int(sp["n_live"].item()))
+        if live[-1] == 0:
+            break
+        t = _tracks(table, sp["edges"], v["n_matches"])
+        if t["n_tracks"] == 0:
+            break
+        out = _triangulate(table, t, p)
+        rounds.append((t, out))
     # ---- the one read-back
-    T, E, Pn = t["n_tracks"], t["n_entries"], len(v["pair_index"])
-    accept, xyz, err = out["accept"][:T].cpu().numpy().astype(bool), out["xyz"][:T].cpu().numpy(), out["error"][:T].cpu().numpy()
-    keep = out["entry_keep"][:E].cpu().numpy().astype(bool)
-    off, frame, kpt, row = (t[k].cpu().numpy() for k in ("trk_off", "trk_frame", "trk_kpt", "trk_row"))
+    Pn = len(v["pair_index"])
+    host = []
+    for t, out in rounds:
+        T, E = t["n_tracks"], t["n_entries"]
+        accept, xyz, err = out["accept"][:T].cpu().numpy().astype(bool), out["xyz"][:T].cpu().numpy(), out["error"][:T].cpu().numpy()
+        keep = out["entry_keep"][:E].cpu().numpy().astype(bool)
+        off, frame, kpt, row = (t[k].cpu().numpy() for k in ("trk_off", "trk_frame", "trk_kpt", "trk_row"))
+        host.append(({"trk_off": off, "trk_row": row, "trk_frame": frame, "trk_kpt": kpt}, {"accept": accept, "xyz": xyz, "error": err, "entry_keep": keep}))
     count = v["count"][:Pn].cpu().numpy()
     frame_ids = np.array([f.get("id", i) for i, f in enumerate(frames)])
     n_m = np.diff(v["match_off"])
     with np.errstate(invalid="ignore", divide="ignore"):
         ratio = np.where(n_m > 0, count / n_m, np.nan)
-    res = map_tables(frame_ids, table["frame_off_host"], {"trk_off": off, "trk_row": row, "trk_frame": frame, "trk_kpt": kpt},
-                     {"accept": accept, "xyz": xyz, "error": err, "entry_keep": keep})
+    if p["split_rounds"] == 0:
+        res = map_tables(frame_ids, table["frame_off_host"], *host[0])
+    else:
+        res = split_tables(frame_ids, table["frame_off_host"], host)
+        K = len(live)      # the rounds begun; one that found no edge or no track has no tracks and no points
+        n_tracks = [rounds[r][0]["n_tracks"] if r < len(rounds) else 0 for r in range(1, K + 1)]
+        n_points = [int((res["point_round"] == r).sum()) for r in range(1, K + 1)]
+        res["split"] = {"live_edges": np.array(live, dtype=np.int64), "tracks": np.array(n_tracks, dtype=np.int64), "points": np.array(n_points, dtype=np.int64)}
     res.update(pair_index=v["pair_index"], inlier_ratio=ratio)
     if sup is not None:
         M, m_off = v["n_matches"], v["match_off"]
@@ -344,16 +417,16 @@ def triangulate_map(frames: Sequence[dict], cameras: Sequence, poses, pairs, mat
     return res
 
 
-def map_tables(frame_ids, frame_off, tracks: dict, tri: dict) -> dict:
+def map_tables(frame_ids, frame_off, tracks: dict, tri: dict, first_id: int = 1) -> dict:
     """The host's last step of :func:`triangulate_map`: the track table (:func:`build_tracks`) and the results
     (:func:`triangulate_tracks`) on the host -> point_ids, point3D_xyzs, track_error, tracks, point3D_frame_ids and frames as
-    triangulate_map documents them.  The accepted tracks become points 1, 2, ... in track order; a point's track holds its kept
-    entries in ascending row."""
+    triangulate_map documents them.  The accepted tracks become points first_id, first_id + 1, ... in track order; a point's
+    track holds its kept entries in ascending row."""
     frame_ids, fo = np.asarray(frame_ids), np.asarray(frame_off)
     off, row, frame, kpt = (np.asarray(tracks[k]) for k in ("trk_off", "trk_row", "trk_frame", "trk_kpt"))
     accept, keep, xyz = np.asarray(tri["accept"]).astype(bool), np.asarray(tri["entry_keep"]).astype(bool), np.asarray(tri["xyz"])
     which = np.nonzero(accept)[0]
-    ids = np.arange(1, which.shape[0] + 1, dtype=np.int64)
+    ids = np.arange(first_id, first_id + which.shape[0], dtype=np.int64)
     row_pid = np.full(int(fo[-1]), -1, dtype=np.int64)
     row_xyz = np.zeros((int(fo[-1]), 3), dtype=np.float64)
     out: Dict[int, tuple] = {}
@@ -364,3 +437,28 @@ def map_tables(frame_ids, frame_off, tracks: dict, tri: dict) -> dict:
     return {"point_ids": ids, "point3D_xyzs": xyz[which].reshape(-1, 3), "track_error": np.asarray(tri["error"])[which], "tracks": out,
             "point3D_frame_ids": {pid: t[0] for pid, t in out.items()},
             "frames": [{"point3D_ids": row_pid[fo[f]:fo[f + 1]], "xyzs": row_xyz[fo[f]:fo[f + 1]]} for f in range(len(fo) - 1)]}
+
+
+def split_tables(frame_ids, frame_off, rounds: Sequence) -> dict:
+    """:func:`map_tables` over several rounds.  rounds: per round (tracks, tri) on the host, round 0 first -> map_tables' dict with
+    the rounds' points numbered one after the other, plus ``point_round`` int32 [P].  A row that a round kept is in no later
+    round's table, so a keypoint has one point at most."""
+    fo = np.asarray(frame_off)
+    parts, nxt = [], 1
+    for tracks, tri in rounds:
+        parts.append(map_tables(frame_ids, fo, tracks, tri, first_id=nxt))
+        nxt += parts[-1]["point_ids"].shape[0]
+    res = {k: np.concatenate([q[k] for q in parts]) for k in ("point_ids", "point3D_xyzs", "track_error")}
+    res["tracks"] = {pid: t for q in parts for pid, t in q["tracks"].items()}
+    res["point3D_frame_ids"] = {pid: t[0] for pid, t in res["tracks"].items()}
+    n = int(fo[-1])
+    row_pid = np.concatenate([f["point3D_ids"] for f in parts[0]["frames"]] + [np.zeros(0, dtype=np.int64)])
+    row_xyz = np.concatenate([f["xyzs"] for f in parts[0]["frames"]] + [np.zeros((0, 3))])
+    for q in parts[1:]:
+        pid = np.concatenate([f["point3D_ids"] for f in q["frames"]] + [np.zeros(0, dtype=np.int64)])
+        has = pid >= 1
+        row_pid[has], row_xyz[has] = pid[has], np.concatenate([f["xyzs"] for f in q["frames"]] + [np.zeros((0, 3))])[has]
+    assert row_pid.shape[0] == n
+    res["frames"] = [{"point3D_ids": row_pid[fo[f]:fo[f + 1]], "xyzs": row_xyz[fo[f]:fo[f + 1]]} for f in range(len(fo) - 1)]
+    res["point_round"] = np.repeat(np.arange(len(parts)), [q["point_ids"].shape[0] for q in parts]).astype(np.int32)
+    return res

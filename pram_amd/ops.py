@@ -2414,6 +2414,32 @@ def tri_support(norm: torch.Tensor, keypoints: torch.Tensor, table: torch.Tensor
     return out
 
 
+TRI_ROW_FREE, TRI_ROW_TAKEN, TRI_ROW_DEAD = 0, 1, 2      # include/pram_hip.h
+
+
+def tri_split(trk_off: torch.Tensor, trk_row: torch.Tensor, n_tracks: int, n_entries: int, accept: torch.Tensor, entry_keep: torch.Tensor,
+              edges: torch.Tensor, n_edges: int, n_rows: int, state: Optional[torch.Tensor] = None) -> dict:
+    """One round's track table (tri_tracks) and results (tri_triangulate's accept and entry_keep) and the edges the first round's
+    tracks came from -> state uint8 [n_rows] (TRI_ROW_*; ``state`` updated in place, None: a new one that starts all DEAD), edges
+    int32 [n_edges, 2]: the edge where both ends are FREE, (-1, -1) elsewhere, and n_live int32 [1], the number of such edges, on
+    the device."""
+    L = _lib.load()
+    _tri_chk(((trk_off, "trk_off", torch.int32), (trk_row, "trk_row", torch.int32), (accept, "accept", torch.int32),
+              (entry_keep, "entry_keep", torch.uint8), (edges, "edges", torch.int32)))
+    T, E, m, n = int(n_tracks), int(n_entries), int(n_edges), int(n_rows)
+    assert trk_off.numel() >= T + 1 and trk_row.numel() >= E and accept.numel() >= T and entry_keep.numel() >= E and edges.numel() >= 2 * m
+    dev = edges.device
+    first = state is None
+    if first:
+        state = torch.empty(max(n, 1), device=dev, dtype=torch.uint8)
+    _tri_chk(((state, "state", torch.uint8),))
+    assert state.numel() >= n
+    out = {"state": state, "edges": torch.empty(max(m, 1), 2, device=dev, dtype=torch.int32), "n_live": torch.empty(1, device=dev, dtype=torch.int32)}
+    _lib.check(L.pram_tri_split(_p(trk_off), _p(trk_row), T, E, _p(accept), _p(entry_keep), _p(edges), m, n, int(first), _p(state),
+                                _p(out["edges"]), _p(out["n_live"]), _st()), "pram_tri_split")
+    return out
+
+
 # ---- statistical outlier removal (csrc/knn.hip; pram_amd/localization/outliers.py drives these) -------------------------------
 KNN_TILE, KNN_MAX_K, SOR_BLOCK = 1024, 32, 1024      # include/pram_hip.h
 SOR_MEAN, SOR_STD, SOR_THRESHOLD, SOR_NV = 0, 1, 2, 3      # entries of the statistics
