@@ -1,6 +1,7 @@
 // Building blocks the localisation glue kernels share (candidates.hip, refine.hip, projref.hip, track.hip, extras.hip): the
 // columns of the plan table, the match list and its row copies, ordered compaction inside a workgroup, the search over the sorted
-// point ids, and the covisible list of the frame a localisation kept.
+// point ids, and the covisible list of the frame a localisation kept.  Two of them serve every file that searches or walks a CSR
+// table (kmeans.hip and triangulate.hip too): the one bisection, first_true, and clamped_range.
 #pragma once
 #include "common.h"
 
@@ -96,14 +97,26 @@ __device__ __forceinline__ int chunk_offset_n(int n, int* wsum, int& total) {
     return woff + incl - n;
 }
 
-// first index i of the ascending ids [n] with ids[i] >= id (n if none); 32 steps cover every n an int holds
-__device__ __forceinline__ int lower_bound_i64(const long long* __restrict__ ids, int n, long long id) {
-    int lo = 0, hi = n;
+// The one bisection: the first index i in [lo, hi) at which the monotone predicate holds (false ... false true ... true), hi if
+// it holds nowhere; pred is called with indices of [lo, hi) only.  32 steps cover every range an int holds.
+template <class Pred>
+__device__ __forceinline__ int first_true(int lo, int hi, Pred pred) {
     for (int it = 0; it < 32 && lo < hi; ++it) {
         const int mid = lo + ((hi - lo) >> 1);
-        if (ids[mid] < id) lo = mid + 1; else hi = mid;
+        if (pred(mid)) hi = mid; else lo = mid + 1;
     }
     return lo;
+}
+
+// first index i of the ascending ids [n] with ids[i] >= id (n if none)
+__device__ __forceinline__ int lower_bound_i64(const long long* __restrict__ ids, int n, long long id) {
+    return first_true(0, n, [&](int i) { return ids[i] >= id; });
+}
+
+// a CSR range (off[i], off[i + 1]) cut into a table of n entries: 0 <= beg <= end <= n, whatever the offsets hold
+__device__ __forceinline__ void clamped_range(int o0, int o1, int n, int& beg, int& end) {
+    beg = o0 < 0 ? 0 : (o0 > n ? n : o0);
+    end = o1 < beg ? beg : (o1 > n ? n : o1);
 }
 
 // the frame the localisation kept for query b (-1: not located, disabled, or a frame the store does not hold), and its covisible

@@ -408,11 +408,7 @@ __global__ __launch_bounds__(256) void km_pp_select_kernel(int n, int nb, int nt
     if (tid < ntr_next) {
         const double v = rand[tid] * pots[s_win];
         const double* __restrict__ r = pp.run + (size_t)s_win * (nb + 1);
-        int lo = 0, hi = nb;
-        for (int it = 0; it < 32 && lo < hi; ++it) {
-            const int mid = lo + ((hi - lo) >> 1);
-            if (r[mid + 1] < v) lo = mid + 1; else hi = mid;
-        }
+        const int lo = first_true(0, nb, [&](int b) { return !(r[b + 1] < v); });      // the first block whose running sum reaches v
         pp.tv[tid] = v;
         pp.blk[tid] = lo < nb ? lo : -1;
         pp.cand[tid] = n - 1;

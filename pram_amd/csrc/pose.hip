@@ -44,13 +44,8 @@ __global__ __launch_bounds__(256) void pose_prepare_kernel(const float* __restri
 }
 
 // ---------------------------------------------------------------- hypotheses: sampler + P3P (Grunert's quartic)
-struct V3 { double x, y, z; };
-__device__ __forceinline__ V3 sub(V3 a, V3 b) { return {a.x - b.x, a.y - b.y, a.z - b.z}; }
-__device__ __forceinline__ double dot(V3 a, V3 b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
-__device__ __forceinline__ V3 cross(V3 a, V3 b) { return {a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x}; }
 __device__ __forceinline__ V3 scale(V3 a, double s) { return {a.x * s, a.y * s, a.z * s}; }
 __device__ __forceinline__ V3 divs(V3 a, double s) { return {a.x / s, a.y / s, a.z / s}; }
-__device__ __forceinline__ bool fin(double x) { return isfinite(x); }
 
 __device__ __forceinline__ V3 bearing(const double* __restrict__ pt) {
     const double x = pt[0], y = pt[1];

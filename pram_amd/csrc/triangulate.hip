@@ -14,14 +14,9 @@ constexpr int GN_STEPS = PRAM_TRI_GN_STEPS;
 constexpr int FC = PRAM_TRI_FRAME_COLS;      // R [9] row-major, t [3], C = -R^T t [3], mean focal length
 constexpr int SCAN = 256;                    // rows per block of the scan over labels
 
-// the frame f with frame_off[f] <= r < frame_off[f + 1] (frames may be empty); 32 steps cover every n_frames an int holds
+// the frame f with frame_off[f] <= r < frame_off[f + 1] (frames may be empty), never beyond n_frames - 1
 __device__ __forceinline__ int frame_of_row(const int* __restrict__ frame_off, int n_frames, int r) {
-    int lo = 0, hi = n_frames - 1;
-    for (int it = 0; it < 32 && lo < hi; ++it) {
-        const int mid = lo + ((hi - lo) >> 1);
-        if (frame_off[mid + 1] <= r) lo = mid + 1; else hi = mid;
-    }
-    return lo;
+    return first_true(0, n_frames - 1, [&](int f) { return frame_off[f + 1] > r; });
 }
 
 // ---------------------------------------------------------------- the frame table
@@ -79,9 +74,8 @@ __global__ __launch_bounds__(256) void tri_verify_kernel(const double* __restric
     __shared__ int wsum[4];
     const int p = blockIdx.x, tid = threadIdx.x;
     const int f0 = pairs[(size_t)p * 2], f1 = pairs[(size_t)p * 2 + 1];
-    int m0 = m_off[p], m1 = m_off[p + 1];
-    m0 = m0 < 0 ? 0 : (m0 > n_matches ? n_matches : m0);
-    m1 = m1 < m0 ? m0 : (m1 > n_matches ? n_matches : m1);
+    int m0, m1;
+    clamped_range(m_off[p], m_off[p + 1], n_matches, m0, m1);
     const bool okp = f0 >= 0 && f0 < n_frames && f1 >= 0 && f1 < n_frames;      // uniform
     int r0 = 0, r1 = 0, n0 = 0, n1 = 0;
     double E[9], th0 = 0.0, th1 = 0.0;
@@ -176,9 +170,70 @@ __global__ void tri_cc_end_kernel(int* __restrict__ state) {
     state[2] += 1;
 }
 
-// ---------------------------------------------------------------- tracks: counts, a scan over labels, a cursor fill, a sort per track
-struct TrackWs { int* size; int* tidx; int* eoff; int* cursor; int* bsum; };
+// ---------------------------------------------------------------- the two-level exclusive scan the tracks and the adjacency share
+// A user U names its NV running sums: terms() makes them of a position's count, local[q] takes sum q, and finish() is what thread
+// 0 of level 2 does with the totals.  Level 1 leaves position x's offset inside its block at local[q][x] and the block's total
+// at bsum[blk * NV + q]; level 2 (one workgroup) turns the totals into the blocks' bases in place.  scan_offset() is how both
+// users read the result.  The workspace: per row a count and a fill cursor (adjacent: one memset clears both), the blocks' sums,
+// then what only the user has.
+struct ScanWs { int* count; int* cursor; int* bsum; int* rest; };
 
+struct TrackScan {      // of a label's size: is it a track, and its entries; the totals are the table's sizes and trk_off's last entry
+    static constexpr int NV = 2;
+    int* local[2]; int* sizes; int* trk_off;
+    __device__ static void terms(int s, int* v) { v[0] = s >= 2 ? 1 : 0; v[1] = s >= 2 ? s : 0; }
+    __device__ void finish(const int* total) const { sizes[0] = total[0]; sizes[1] = total[1]; trk_off[total[0]] = total[1]; }
+};
+
+struct AdjScan {      // a row's degree; segments = n_rows is what the sort reads as its number of lists
+    static constexpr int NV = 1;
+    int* local[1]; int* segments; int n_rows;
+    __device__ static void terms(int s, int* v) { v[0] = s; }
+    __device__ void finish(const int*) const { segments[0] = n_rows; }
+};
+
+// positions 0 .. n_out - 1; a position beyond n_in counts 0 (the adjacency's last stands for the total)
+template <class U>
+__global__ __launch_bounds__(SCAN) void tri_scan_blocks_kernel(const int* __restrict__ count, int n_in, int n_out, U u, int* __restrict__ bsum) {
+    __shared__ int wsum[4];
+    const int x = blockIdx.x * SCAN + threadIdx.x;
+    int v[U::NV];
+    U::terms(x < n_in ? count[x] : 0, v);
+#pragma unroll
+    for (int q = 0; q < U::NV; ++q) {
+        int total;
+        const int o = chunk_offset_n<4>(v[q], wsum, total);
+        if (x < n_out) u.local[q][x] = o;
+        if (threadIdx.x == 0) bsum[(size_t)blockIdx.x * U::NV + q] = total;
+    }
+}
+
+template <class U>
+__global__ __launch_bounds__(256) void tri_scan_totals_kernel(int* __restrict__ bsum, int n_blocks, U u) {
+    __shared__ int wsum[4];
+    int base[U::NV];
+#pragma unroll
+    for (int q = 0; q < U::NV; ++q) base[q] = 0;
+    for (int c0 = 0; c0 < n_blocks; c0 += 256) {
+        const int i = c0 + threadIdx.x;
+#pragma unroll
+        for (int q = 0; q < U::NV; ++q) {
+            int total;
+            const int o = chunk_offset_n<4>(i < n_blocks ? bsum[(size_t)i * U::NV + q] : 0, wsum, total);
+            if (i < n_blocks) bsum[(size_t)i * U::NV + q] = base[q] + o;
+            base[q] += total;
+        }
+    }
+    if (threadIdx.x == 0) u.finish(base);
+}
+
+// sum q at position x: the offset inside its block + the block's base
+template <int NV>
+__device__ __forceinline__ int scan_offset(const int* local, const int* bsum, int x, int q) {
+    return local[x] + bsum[(size_t)(x / SCAN) * NV + q];
+}
+
+// ---------------------------------------------------------------- tracks: counts, the scan over labels, a cursor fill, a sort per track
 __global__ __launch_bounds__(256) void tri_count_kernel(const int* __restrict__ label, int n_rows, int* __restrict__ size) {
     const int x = blockIdx.x * 256 + threadIdx.x;
     if (x >= n_rows) return;
@@ -186,45 +241,16 @@ __global__ __launch_bounds__(256) void tri_count_kernel(const int* __restrict__ 
     if (l >= 0 && l < n_rows) atomicAdd(&size[l], 1);
 }
 
-// block-local exclusive scans of (is a track, its entries) over the labels, and the block's totals
-__global__ __launch_bounds__(SCAN) void tri_scan_blocks_kernel(TrackWs ws, int n_rows) {
-    __shared__ int wsum[4];
-    const int x = blockIdx.x * SCAN + threadIdx.x;
-    const int s = x < n_rows ? ws.size[x] : 0;
-    const int a = s >= 2 ? 1 : 0, b = s >= 2 ? s : 0;
-    int ta, tb;
-    const int oa = chunk_offset_n<4>(a, wsum, ta);
-    const int ob = chunk_offset_n<4>(b, wsum, tb);
-    if (x < n_rows) { ws.tidx[x] = oa; ws.eoff[x] = ob; }
-    if (threadIdx.x == 0) { ws.bsum[(size_t)blockIdx.x * 2] = ta; ws.bsum[(size_t)blockIdx.x * 2 + 1] = tb; }
-}
-
-// one workgroup: the block totals -> their exclusive scan in place; sizes = (tracks, entries); trk_off's last entry
-__global__ __launch_bounds__(256) void tri_scan_totals_kernel(TrackWs ws, int n_blocks, int* __restrict__ sizes, int* __restrict__ trk_off) {
-    __shared__ int wsum[4];
-    int base_a = 0, base_b = 0;
-    for (int c0 = 0; c0 < n_blocks; c0 += 256) {
-        const int i = c0 + threadIdx.x;
-        const int a = i < n_blocks ? ws.bsum[(size_t)i * 2] : 0, b = i < n_blocks ? ws.bsum[(size_t)i * 2 + 1] : 0;
-        int ta, tb;
-        const int oa = chunk_offset_n<4>(a, wsum, ta);
-        const int ob = chunk_offset_n<4>(b, wsum, tb);
-        if (i < n_blocks) { ws.bsum[(size_t)i * 2] = base_a + oa; ws.bsum[(size_t)i * 2 + 1] = base_b + ob; }
-        base_a += ta; base_b += tb;
-    }
-    if (threadIdx.x == 0) { sizes[0] = base_a; sizes[1] = base_b; trk_off[base_a] = base_b; }
-}
-
-__global__ __launch_bounds__(256) void tri_fill_kernel(const int* __restrict__ label, TrackWs ws, int n_rows, int* __restrict__ trk_off,
+__global__ __launch_bounds__(256) void tri_fill_kernel(const int* __restrict__ label, ScanWs ws, TrackScan u, int n_rows,
                                                        int* __restrict__ trk_label, int* __restrict__ trk_row) {
     const int x = blockIdx.x * 256 + threadIdx.x;
     if (x >= n_rows) return;
     const int l = label[x];
-    if (l < 0 || l >= n_rows || ws.size[l] < 2) return;
-    const int t = ws.tidx[l] + ws.bsum[(size_t)(l / SCAN) * 2], eo = ws.eoff[l] + ws.bsum[(size_t)(l / SCAN) * 2 + 1];
+    if (l < 0 || l >= n_rows || ws.count[l] < 2) return;
+    const int t = scan_offset<2>(u.local[0], ws.bsum, l, 0), eo = scan_offset<2>(u.local[1], ws.bsum, l, 1);
     const int pos = atomicAdd(&ws.cursor[l], 1);
     if (eo + pos < n_rows) trk_row[eo + pos] = x;
-    if (x == l) { trk_off[t] = eo; trk_label[t] = l; }
+    if (x == l) { u.trk_off[t] = eo; trk_label[t] = l; }
 }
 
 // One wave per track: a bitonic network in its flip form (every comparator ascending, so the positions beyond the track's length
@@ -232,9 +258,8 @@ __global__ __launch_bounds__(256) void tri_fill_kernel(const int* __restrict__ l
 __global__ __launch_bounds__(64) void tri_sort_kernel(const int* __restrict__ sizes, const int* __restrict__ trk_off, int* trk_row, int n_rows) {
     const int t = blockIdx.x, lane = threadIdx.x;
     if (t >= sizes[0]) return;
-    int beg = trk_off[t], end = trk_off[t + 1];
-    beg = beg < 0 ? 0 : (beg > n_rows ? n_rows : beg);
-    end = end < beg ? beg : (end > n_rows ? n_rows : end);
+    int beg, end;
+    clamped_range(trk_off[t], trk_off[t + 1], n_rows, beg, end);
     const int L = end - beg;
     int* a = trk_row + beg;
     int N2 = 1;
@@ -266,51 +291,37 @@ __global__ __launch_bounds__(256) void tri_derive_kernel(const int* __restrict__
     trk_frame[e] = f; trk_kpt[e] = r - frame_off[f];
 }
 
-// ---------------------------------------------------------------- triangulate: one wave per track
-struct TriArgs {
-    const double* norm; const float* kpts; const double* table; const int* cam_model; const double* cam_params;
-    const int* trk_row; const int* trk_frame; int n_frames, n_rows;
+// ---------------------------------------------------------------- the observation model: keypoint (row) r seen in frame f
+// What stage 2b and stage 4 compute of an observation, once, so that the two agree to the bit.  A caller passes a row and a
+// frame the tables hold.
+struct Obs {
+    const double* norm; const float* kpts; const double* table; const int* cam_model; const double* cam_params; int n_frames, n_rows;
 };
 
-struct V3 { double x, y, z; };
-__device__ __forceinline__ V3 sub(V3 a, V3 b) { return {a.x - b.x, a.y - b.y, a.z - b.z}; }
-__device__ __forceinline__ double dot(V3 a, V3 b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
-__device__ __forceinline__ V3 cross(V3 a, V3 b) { return {a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x}; }
-__device__ __forceinline__ double angle(V3 a, V3 b) { const V3 c = cross(a, b); return atan2(sqrt(dot(c, c)), dot(a, b)); }
-__device__ __forceinline__ bool fin(double x) { return isfinite(x); }
-
-// entry e names a row and a frame the tables hold (a caller's own track table may not)
-__device__ __forceinline__ bool entry_ok(const TriArgs& g, int e) {
-    const int r = g.trk_row[e], f = g.trk_frame[e];
-    return r >= 0 && r < g.n_rows && f >= 0 && f < g.n_frames;
-}
-
-__device__ __forceinline__ V3 entry_centre(const TriArgs& g, int e) {
-    const double* T = g.table + (size_t)g.trk_frame[e] * FC;
+__device__ __forceinline__ V3 obs_centre(const Obs& g, int f) {
+    const double* T = g.table + (size_t)f * FC;
     return {T[12], T[13], T[14]};
 }
 
 // the observation's unit ray in world coordinates: R^T (u, v, 1) / |(u, v, 1)|
-__device__ __forceinline__ V3 entry_ray(const TriArgs& g, int e) {
-    const double* T = g.table + (size_t)g.trk_frame[e] * FC;
-    const size_t r = (size_t)g.trk_row[e];
-    const double u = g.norm[r * 2], v = g.norm[r * 2 + 1];
+__device__ __forceinline__ V3 obs_ray(const Obs& g, int r, int f) {
+    const double* T = g.table + (size_t)f * FC;
+    const double u = g.norm[(size_t)r * 2], v = g.norm[(size_t)r * 2 + 1];
     const double n = sqrt(u * u + v * v + 1.0);
     const double x = u / n, y = v / n, z = 1.0 / n;
     return {T[0] * x + T[3] * y + T[6] * z, T[1] * x + T[4] * y + T[7] * z, T[2] * x + T[5] * y + T[8] * z};
 }
 
-__device__ __forceinline__ double entry_depth(const TriArgs& g, int e, V3 X) {
-    const double* T = g.table + (size_t)g.trk_frame[e] * FC;
+__device__ __forceinline__ double obs_depth(const Obs& g, int f, V3 X) {
+    const double* T = g.table + (size_t)f * FC;
     return T[6] * X.x + T[7] * X.y + T[8] * X.z + T[11];
 }
 
-// pixel residual of X in entry e through the full camera model; z: the depth; with_jac: J [2][3] = d residual / d X
-__device__ __forceinline__ void entry_residual(const TriArgs& g, int e, V3 X, double& z, double& r0, double& r1, bool with_jac, double* J) {
-    const int f = g.trk_frame[e];
+// pixel residual of X through the full camera model, against keypoint + 0.5; z: the depth; with_jac: J [2][3] = d residual / d X
+__device__ __forceinline__ void obs_residual(const Obs& g, int row, int f, V3 X, double& z, double& r0, double& r1, bool with_jac, double* J) {
     const double* T = g.table + (size_t)f * FC;
     const Cam c = cam_unify(g.cam_model[f], g.cam_params + (size_t)f * PRAM_POSE_CAM_PARAMS);
-    const size_t r = (size_t)g.trk_row[e];
+    const size_t r = (size_t)row;
     const double xc = T[0] * X.x + T[1] * X.y + T[2] * X.z + T[9];
     const double yc = T[3] * X.x + T[4] * X.y + T[5] * X.z + T[10];
     z = T[6] * X.x + T[7] * X.y + T[8] * X.z + T[11];
@@ -334,12 +345,21 @@ __device__ __forceinline__ void entry_residual(const TriArgs& g, int e, V3 X, do
 }
 
 // squared reprojection error and the inlier test: positive depth and error <= thr (NaN compares false)
-__device__ __forceinline__ bool entry_inlier(const TriArgs& g, int e, V3 X, double thr2, double& err2) {
-    if (!entry_ok(g, e)) { err2 = 0.0; return false; }
+__device__ __forceinline__ bool obs_inlier(const Obs& g, int r, int f, V3 X, double thr2, double& err2) {
     double z, r0, r1;
-    entry_residual(g, e, X, z, r0, r1, false, nullptr);
+    obs_residual(g, r, f, X, z, r0, r1, false, nullptr);
     err2 = r0 * r0 + r1 * r1;
     return z > 0.0 && err2 <= thr2;
+}
+
+// the midpoint of the closest points of two rays: stage 4's hypothesis, stage 2b's point
+__device__ __forceinline__ V3 ray_midpoint(V3 C1, V3 d1, V3 C2, V3 d2) {
+    const V3 w = sub(C1, C2);
+    const double a = dot(d1, d1), b = dot(d1, d2), c = dot(d2, d2), d = dot(d1, w), e = dot(d2, w);
+    const double den = a * c - b * b;
+    const double s = (b * e - c * d) / den, u = (a * e - b * d) / den;
+    return {0.5 * ((C1.x + s * d1.x) + (C2.x + u * d2.x)), 0.5 * ((C1.y + s * d1.y) + (C2.y + u * d2.y)),
+            0.5 * ((C1.z + s * d1.z) + (C2.z + u * d2.z))};
 }
 
 // A x = b for a symmetric A given as a00 a01 a02 a11 a12 a22, by Cholesky; false when a pivot is not positive or x is not finite
@@ -359,22 +379,29 @@ __device__ bool chol_solve3(const double* __restrict__ A, const double* __restri
     return fin(x[0]) && fin(x[1]) && fin(x[2]);
 }
 
-__device__ __forceinline__ int wave_sum_i32(int v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
+// ---------------------------------------------------------------- triangulate: one wave per track
+// entry e's row and frame; ok: the tables hold both (a caller's own track table may name neither)
+struct Entry { int r, f; bool ok; };
 
-__global__ __launch_bounds__(64) void tri_triangulate_kernel(TriArgs g, const int* __restrict__ trk_off, const int* __restrict__ trk_label,
+__global__ __launch_bounds__(64) void tri_triangulate_kernel(Obs g, const int* __restrict__ trk_off, const int* __restrict__ trk_label,
+                                                             const int* __restrict__ trk_row, const int* __restrict__ trk_frame,
                                                              int n_entries, int trials, unsigned long long seed, double min_angle,
                                                              double max_err, int* __restrict__ accept, double* __restrict__ xyz,
                                                              double* __restrict__ err, int* __restrict__ kept_n, int* __restrict__ best,
                                                              unsigned char* ent_keep, double* ent_err) {
     const int t = blockIdx.x, lane = threadIdx.x;
-    int beg = trk_off[t], end = trk_off[t + 1];
-    beg = beg < 0 ? 0 : (beg > n_entries ? n_entries : beg);
-    end = end < beg ? beg : (end > n_entries ? n_entries : end);
+    int beg, end;
+    clamped_range(trk_off[t], trk_off[t + 1], n_entries, beg, end);
     const int L = end - beg;
+    const auto entry = [&](int e) -> Entry {
+        const int r = trk_row[e], f = trk_frame[e];
+        return {r, f, r >= 0 && r < g.n_rows && f >= 0 && f < g.n_frames};
+    };
+    const auto inlier = [&](int e, V3 X, double thr2, double& err2) {
+        const Entry en = entry(e);
+        err2 = 0.0;
+        return en.ok && obs_inlier(g, en.r, en.f, X, thr2, err2);
+    };
     const double thr2 = max_err * max_err;
     const long long all = (long long)L * (L - 1) / 2;
     const bool exhaustive = all <= (long long)trials;
@@ -397,22 +424,17 @@ __global__ __launch_bounds__(64) void tri_triangulate_kernel(TriArgs g, const in
             b += b >= a;
             i = a < b ? a : b; j = a < b ? b : a;
         }
-        const int ei = beg + i, ej = beg + j;
-        if (!entry_ok(g, ei) || !entry_ok(g, ej) || g.trk_frame[ei] == g.trk_frame[ej]) continue;
-        const V3 C1 = entry_centre(g, ei), C2 = entry_centre(g, ej), d1 = entry_ray(g, ei), d2 = entry_ray(g, ej);
+        const Entry ei = entry(beg + i), ej = entry(beg + j);
+        if (!ei.ok || !ej.ok || ei.f == ej.f) continue;
+        const V3 C1 = obs_centre(g, ei.f), C2 = obs_centre(g, ej.f), d1 = obs_ray(g, ei.r, ei.f), d2 = obs_ray(g, ej.r, ej.f);
         if (!(angle(d1, d2) >= min_angle)) continue;
-        const V3 w = sub(C1, C2);
-        const double a = dot(d1, d1), b = dot(d1, d2), c = dot(d2, d2), d = dot(d1, w), e = dot(d2, w);
-        const double den = a * c - b * b;
-        const double s = (b * e - c * d) / den, u = (a * e - b * d) / den;
-        const V3 X = {0.5 * ((C1.x + s * d1.x) + (C2.x + u * d2.x)), 0.5 * ((C1.y + s * d1.y) + (C2.y + u * d2.y)),
-                      0.5 * ((C1.z + s * d1.z) + (C2.z + u * d2.z))};
-        if (!(entry_depth(g, ei, X) > 0.0) || !(entry_depth(g, ej, X) > 0.0)) continue;
+        const V3 X = ray_midpoint(C1, d1, C2, d2);
+        if (!(obs_depth(g, ei.f, X) > 0.0) || !(obs_depth(g, ej.f, X) > 0.0)) continue;
         int cnt = 0;
         double sse = 0.0;
         for (int k = lane; k < L; k += 64) {
             double e2;
-            const bool in = entry_inlier(g, beg + k, X, thr2, e2);
+            const bool in = inlier(beg + k, X, thr2, e2);
             cnt += in;
             sse += in ? e2 : 0.0;
         }
@@ -437,10 +459,11 @@ __global__ __launch_bounds__(64) void tri_triangulate_kernel(TriArgs g, const in
         for (int q = 0; q < 9; ++q) acc[q] = 0.0;
         for (int k = lane; k < L; k += 64) {
             double e2;
-            const bool in = entry_inlier(g, beg + k, bX, thr2, e2);
+            const bool in = inlier(beg + k, bX, thr2, e2);
             ent_keep[beg + k] = in;
             if (!in) continue;
-            const V3 dd = entry_ray(g, beg + k), C = entry_centre(g, beg + k);
+            const Entry en = entry(beg + k);
+            const V3 dd = obs_ray(g, en.r, en.f), C = obs_centre(g, en.f);
             const double m00 = 1.0 - dd.x * dd.x, m01 = -dd.x * dd.y, m02 = -dd.x * dd.z, m11 = 1.0 - dd.y * dd.y, m12 = -dd.y * dd.z,
                          m22 = 1.0 - dd.z * dd.z;
             acc[0] += m00; acc[1] += m01; acc[2] += m02; acc[3] += m11; acc[4] += m12; acc[5] += m22;
@@ -460,7 +483,7 @@ __global__ __launch_bounds__(64) void tri_triangulate_kernel(TriArgs g, const in
         for (int k = lane; k < L; k += 64) {
             if (!ent_keep[beg + k]) continue;
             double z, r0, r1, J[6];
-            entry_residual(g, beg + k, X, z, r0, r1, true, J);
+            obs_residual(g, trk_row[beg + k], trk_frame[beg + k], X, z, r0, r1, true, J);
             if (!(z > 1e-12) || !fin(r0 * r0 + r1 * r1)) continue;
             acc[0] += J[0] * J[0] + J[3] * J[3]; acc[1] += J[0] * J[1] + J[3] * J[4]; acc[2] += J[0] * J[2] + J[3] * J[5];
             acc[3] += J[1] * J[1] + J[4] * J[4]; acc[4] += J[1] * J[2] + J[4] * J[5]; acc[5] += J[2] * J[2] + J[5] * J[5];
@@ -475,7 +498,7 @@ __global__ __launch_bounds__(64) void tri_triangulate_kernel(TriArgs g, const in
     // ---- final marking at X, then one entry per frame: the smallest error, the lowest row on a tie (a frame's entries are adjacent)
     for (int k = lane; k < L; k += 64) {
         double e2;
-        const bool in = entry_inlier(g, beg + k, X, thr2, e2);
+        const bool in = inlier(beg + k, X, thr2, e2);
         ent_err[beg + k] = in ? sqrt(e2) : -1.0;
     }
     __syncthreads();
@@ -485,12 +508,12 @@ __global__ __launch_bounds__(64) void tri_triangulate_kernel(TriArgs g, const in
         const double mine = ent_err[beg + k];
         bool keep = mine >= 0.0;
         if (keep) {
-            const int f = g.trk_frame[beg + k];
-            for (int o = k - 1; o >= 0 && g.trk_frame[beg + o] == f; --o) {
+            const int f = trk_frame[beg + k];
+            for (int o = k - 1; o >= 0 && trk_frame[beg + o] == f; --o) {
                 const double other = ent_err[beg + o];
                 if (other >= 0.0 && other <= mine) { keep = false; break; }
             }
-            for (int o = k + 1; keep && o < L && g.trk_frame[beg + o] == f; ++o) {
+            for (int o = k + 1; keep && o < L && trk_frame[beg + o] == f; ++o) {
                 const double other = ent_err[beg + o];
                 if (other >= 0.0 && other < mine) keep = false;
             }
@@ -506,10 +529,10 @@ __global__ __launch_bounds__(64) void tri_triangulate_kernel(TriArgs g, const in
     bool found = false;
     for (int k = lane; k < L && !found; k += 64) {
         if (!ent_keep[beg + k]) continue;
-        const V3 vi = sub(X, entry_centre(g, beg + k));
+        const V3 vi = sub(X, obs_centre(g, trk_frame[beg + k]));
         for (int o = k + 1; o < L; ++o) {
             if (!ent_keep[beg + o]) continue;
-            if (angle(vi, sub(X, entry_centre(g, beg + o))) >= min_angle) { found = true; break; }
+            if (angle(vi, sub(X, obs_centre(g, trk_frame[beg + o]))) >= min_angle) { found = true; break; }
         }
     }
     const bool any = __any(found);
@@ -520,10 +543,9 @@ __global__ __launch_bounds__(64) void tri_triangulate_kernel(TriArgs g, const in
 }
 
 // ---------------------------------------------------------------- stage 2b: the rows' adjacency and every edge's third-view support
-// adjacency: degrees by integer atomics, an exclusive scan, a cursor fill, then tri_sort_kernel over adj_off, so that the table is
-// a function of the edge set alone.  An edge counts when both ends are rows and differ.
-struct AdjWs { int* deg; int* cursor; int* bsum; int* count; };
-
+// adjacency: degrees by integer atomics, the scan over rows 0 .. n_rows (straight into adj_off), a cursor fill, then
+// tri_sort_kernel over adj_off, so that the table is a function of the edge set alone.  An edge counts when both ends are rows
+// and differ.
 __device__ __forceinline__ bool edge_ok(int u, int v, int n_rows) { return u >= 0 && v >= 0 && u < n_rows && v < n_rows && u != v; }
 
 __global__ __launch_bounds__(256) void tri_adj_count_kernel(const int* __restrict__ edges, int n_edges, int n_rows, int* __restrict__ deg) {
@@ -535,39 +557,15 @@ __global__ __launch_bounds__(256) void tri_adj_count_kernel(const int* __restric
     atomicAdd(&deg[v], 1);
 }
 
-// block-local exclusive scans of the degrees over rows 0 .. n_rows (the last stands for the total), and the block's totals
-__global__ __launch_bounds__(SCAN) void tri_adj_scan_blocks_kernel(AdjWs ws, int n_rows, int* __restrict__ adj_off) {
-    __shared__ int wsum[4];
-    const int x = blockIdx.x * SCAN + threadIdx.x;
-    int total;
-    const int o = chunk_offset_n<4>(x < n_rows ? ws.deg[x] : 0, wsum, total);
-    if (x <= n_rows) adj_off[x] = o;
-    if (threadIdx.x == 0) ws.bsum[blockIdx.x] = total;
-}
-
-// one workgroup: the block totals -> their exclusive scan in place; count = n_rows, which the sort reads as its number of segments
-__global__ __launch_bounds__(256) void tri_adj_scan_totals_kernel(AdjWs ws, int n_blocks, int n_rows) {
-    __shared__ int wsum[4];
-    int base = 0;
-    for (int c0 = 0; c0 < n_blocks; c0 += 256) {
-        const int i = c0 + threadIdx.x;
-        int total;
-        const int o = chunk_offset_n<4>(i < n_blocks ? ws.bsum[i] : 0, wsum, total);
-        if (i < n_blocks) ws.bsum[i] = base + o;
-        base += total;
-    }
-    if (threadIdx.x == 0) ws.count[0] = n_rows;
-}
-
-__global__ __launch_bounds__(256) void tri_adj_offsets_kernel(AdjWs ws, const int* __restrict__ frame_off, int n_frames, int n_rows,
+__global__ __launch_bounds__(256) void tri_adj_offsets_kernel(ScanWs ws, const int* __restrict__ frame_off, int n_frames, int n_rows,
                                                               int* __restrict__ adj_off, int* __restrict__ row_frame) {
     const int x = blockIdx.x * 256 + threadIdx.x;
     if (x > n_rows) return;
-    adj_off[x] += ws.bsum[x / SCAN];
+    adj_off[x] = scan_offset<1>(adj_off, ws.bsum, x, 0);
     if (x < n_rows) row_frame[x] = frame_of_row(frame_off, n_frames, x);
 }
 
-__global__ __launch_bounds__(256) void tri_adj_fill_kernel(const int* __restrict__ edges, int n_edges, int n_rows, AdjWs ws,
+__global__ __launch_bounds__(256) void tri_adj_fill_kernel(const int* __restrict__ edges, int n_edges, int n_rows, ScanWs ws,
                                                            const int* __restrict__ adj_off, int* __restrict__ adj) {
     const int e = blockIdx.x * 256 + threadIdx.x;
     if (e >= n_edges) return;
@@ -578,64 +576,15 @@ __global__ __launch_bounds__(256) void tri_adj_fill_kernel(const int* __restrict
     if (pv >= 0 && pv < 2ll * n_edges) adj[pv] = u;
 }
 
-// support: what stage 4 computes of an entry, here of a row r of frame f (the same formulas in the same order)
-struct SupArgs {
-    const double* norm; const float* kpts; const double* table; const int* cam_model; const double* cam_params;
-    const int* adj_off; const int* adj; const int* row_frame; int n_frames, n_rows, n_adj;
-};
-
-__device__ __forceinline__ V3 row_centre(const SupArgs& g, int f) {
-    const double* T = g.table + (size_t)f * FC;
-    return {T[12], T[13], T[14]};
-}
-
-__device__ __forceinline__ V3 row_ray(const SupArgs& g, int r, int f) {
-    const double* T = g.table + (size_t)f * FC;
-    const double u = g.norm[(size_t)r * 2], v = g.norm[(size_t)r * 2 + 1];
-    const double n = sqrt(u * u + v * v + 1.0);
-    const double x = u / n, y = v / n, z = 1.0 / n;
-    return {T[0] * x + T[3] * y + T[6] * z, T[1] * x + T[4] * y + T[7] * z, T[2] * x + T[5] * y + T[8] * z};
-}
-
-// positive depth and a squared pixel error <= thr2 through the full camera model, against keypoint + 0.5 (NaN compares false)
-__device__ __forceinline__ bool row_inlier(const SupArgs& g, int r, int f, V3 X, double thr2) {
-    const double* T = g.table + (size_t)f * FC;
-    const Cam c = cam_unify(g.cam_model[f], g.cam_params + (size_t)f * PRAM_POSE_CAM_PARAMS);
-    const double xc = T[0] * X.x + T[1] * X.y + T[2] * X.z + T[9];
-    const double yc = T[3] * X.x + T[4] * X.y + T[5] * X.z + T[10];
-    const double z = T[6] * X.x + T[7] * X.y + T[8] * X.z + T[11];
-    const double u = xc / z, v = yc / z;
-    double ud, vd;
-    distort(c, u, v, ud, vd);
-    const double r0 = c.fx * ud + c.cx - ((double)g.kpts[(size_t)r * 2] + 0.5);
-    const double r1 = c.fy * vd + c.cy - ((double)g.kpts[(size_t)r * 2 + 1] + 0.5);
-    return z > 0.0 && r0 * r0 + r1 * r1 <= thr2;
-}
-
-// the midpoint of the closest points of two rays, as a hypothesis of stage 4
-__device__ __forceinline__ V3 ray_midpoint(V3 C1, V3 d1, V3 C2, V3 d2) {
-    const V3 w = sub(C1, C2);
-    const double a = dot(d1, d1), b = dot(d1, d2), c = dot(d2, d2), d = dot(d1, w), e = dot(d2, w);
-    const double den = a * c - b * b;
-    const double s = (b * e - c * d) / den, u = (a * e - b * d) / den;
-    return {0.5 * ((C1.x + s * d1.x) + (C2.x + u * d2.x)), 0.5 * ((C1.y + s * d1.y) + (C2.y + u * d2.y)),
-            0.5 * ((C1.z + s * d1.z) + (C2.z + u * d2.z))};
-}
-
-// row r's list in adj, its offsets clamped into the table
-__device__ __forceinline__ void adj_range(const SupArgs& g, int r, int& beg, int& len) {
-    int b = g.adj_off[r], e = g.adj_off[r + 1];
-    b = b < 0 ? 0 : (b > g.n_adj ? g.n_adj : b);
-    e = e < b ? b : (e > g.n_adj ? g.n_adj : e);
-    beg = b; len = e - b;
-}
+// the adjacency as the support reads it; n: the entries adj holds
+struct Adj { const int* off; const int* adj; const int* row_frame; int n; };
 
 constexpr int SUP_WAVES = 4;      // edges per workgroup
 
 // One wave per edge (u, v): the lanes stride over adj(u) followed by adj(v); a witness is a row of a third frame, counted once.
 // Of the pairs (u, v), (u, w), (v, w) the one whose rays meet under the largest angle (the first on a tie) gives X; w confirms the
 // edge when that angle reaches min_angle and u, v and w are inliers of X.  No LDS and no floating-point atomics.
-__global__ __launch_bounds__(64 * SUP_WAVES) void tri_support_kernel(SupArgs g, const int* __restrict__ edges, int n_edges, double min_angle,
+__global__ __launch_bounds__(64 * SUP_WAVES) void tri_support_kernel(Obs g, Adj a, const int* __restrict__ edges, int n_edges, double min_angle,
                                                                      double max_err, int min_support, int* __restrict__ support,
                                                                      int* __restrict__ edges_out) {
     const int e = blockIdx.x * SUP_WAVES + (threadIdx.x >> 6), lane = threadIdx.x & 63;
@@ -646,36 +595,33 @@ __global__ __launch_bounds__(64 * SUP_WAVES) void tri_support_kernel(SupArgs g, 
     bool ok = edge_ok(u, v, g.n_rows);
     int fu = -1, fv = -1;
     if (ok) {
-        fu = g.row_frame[u]; fv = g.row_frame[v];
+        fu = a.row_frame[u]; fv = a.row_frame[v];
         ok = fu >= 0 && fu < g.n_frames && fv >= 0 && fv < g.n_frames && fu != fv;
     }
     if (ok) {      // uniform over the wave
-        const V3 Cu = row_centre(g, fu), Cv = row_centre(g, fv), du = row_ray(g, u, fu), dv = row_ray(g, v, fv);
+        const V3 Cu = obs_centre(g, fu), Cv = obs_centre(g, fv), du = obs_ray(g, u, fu), dv = obs_ray(g, v, fv);
         const double a_uv = angle(du, dv);
-        int bu, nu, bv, nv;
-        adj_range(g, u, bu, nu);
-        adj_range(g, v, bv, nv);
+        int bu, eu, bv, ev;      // the two lists, their offsets cut into the table
+        clamped_range(a.off[u], a.off[u + 1], a.n, bu, eu);
+        clamped_range(a.off[v], a.off[v + 1], a.n, bv, ev);
+        const int nu = eu - bu, nv = ev - bv;
         const long long total = (long long)nu + nv;
         for (long long k = lane; k < total; k += 64) {
             int w;
             if (k < nu) {
-                w = g.adj[bu + (int)k];
-                if (k > 0 && g.adj[bu + (int)k - 1] == w) continue;
+                w = a.adj[bu + (int)k];
+                if (k > 0 && a.adj[bu + (int)k - 1] == w) continue;
             } else {
                 const int j = (int)(k - nu);
-                w = g.adj[bv + j];
-                if (j > 0 && g.adj[bv + j - 1] == w) continue;
-                int lo = 0, hi = nu;      // the first element of adj(u) that is not below w
-                for (int it = 0; it < 32 && lo < hi; ++it) {
-                    const int mid = lo + ((hi - lo) >> 1);
-                    if (g.adj[bu + mid] < w) lo = mid + 1; else hi = mid;
-                }
-                if (lo < nu && g.adj[bu + lo] == w) continue;
+                w = a.adj[bv + j];
+                if (j > 0 && a.adj[bv + j - 1] == w) continue;
+                const int lo = first_true(0, nu, [&](int i) { return a.adj[bu + i] >= w; });      // adj(u) holds w already
+                if (lo < nu && a.adj[bu + lo] == w) continue;
             }
             if (w < 0 || w >= g.n_rows || w == u || w == v) continue;
-            const int fw = g.row_frame[w];
+            const int fw = a.row_frame[w];
             if (fw < 0 || fw >= g.n_frames || fw == fu || fw == fv) continue;
-            const V3 Cw = row_centre(g, fw), dw = row_ray(g, w, fw);
+            const V3 Cw = obs_centre(g, fw), dw = obs_ray(g, w, fw);
             const double a_uw = angle(du, dw), a_vw = angle(dv, dw);
             int pick = 0;
             double best = a_uv;
@@ -683,7 +629,8 @@ __global__ __launch_bounds__(64 * SUP_WAVES) void tri_support_kernel(SupArgs g, 
             if (a_vw > best) { pick = 2; best = a_vw; }
             if (!(best >= min_angle)) continue;
             const V3 X = pick == 0 ? ray_midpoint(Cu, du, Cv, dv) : (pick == 1 ? ray_midpoint(Cu, du, Cw, dw) : ray_midpoint(Cv, dv, Cw, dw));
-            const bool iu = row_inlier(g, u, fu, X, thr2), iv = row_inlier(g, v, fv, X, thr2), iw = row_inlier(g, w, fw, X, thr2);
+            double e2;
+            const bool iu = obs_inlier(g, u, fu, X, thr2, e2), iv = obs_inlier(g, v, fv, X, thr2, e2), iw = obs_inlier(g, w, fw, X, thr2, e2);
             cnt += iu && iv && iw;
         }
     }
@@ -704,24 +651,19 @@ __global__ __launch_bounds__(256) void tri_split_init_kernel(unsigned char* __re
     if (x == 0) n_live[0] = 0;
 }
 
-__device__ __forceinline__ int clamp_off(int o, int n) { return o < 0 ? 0 : (o > n ? n : o); }
-
-// One thread per entry: its track is the last whose (clamped) offset is not beyond it; 32 steps cover every n_tracks an int
-// holds.  A row is in one track, so every byte has one writer.
+// One thread per entry: its track is the last whose offset is not beyond it, track 0 when none is (an offset cut into
+// [0, n_entries] compares with an entry as the offset itself does).  The search runs from the last track down, so the first
+// index that holds is the last such track.  A row is in one track, so every byte has one writer.
 __global__ __launch_bounds__(256) void tri_split_mark_kernel(const int* __restrict__ trk_off, const int* __restrict__ trk_row, int n_tracks,
                                                              int n_entries, const int* __restrict__ accept,
                                                              const unsigned char* __restrict__ entry_keep, int n_rows,
                                                              unsigned char* __restrict__ state) {
     const int e = blockIdx.x * 256 + threadIdx.x;
     if (e >= n_entries) return;
-    int lo = 0, hi = n_tracks - 1;
-    for (int it = 0; it < 32 && lo < hi; ++it) {
-        const int mid = lo + ((hi - lo + 1) >> 1);
-        if (clamp_off(trk_off[mid], n_entries) <= e) lo = mid; else hi = mid - 1;
-    }
-    const int beg = clamp_off(trk_off[lo], n_entries);
-    int end = clamp_off(trk_off[lo + 1], n_entries);
-    end = end < beg ? beg : end;
+    const int last = n_tracks - 1;
+    const int lo = last - first_true(0, last, [&](int j) { return trk_off[last - j] <= e; });
+    int beg, end;
+    clamped_range(trk_off[lo], trk_off[lo + 1], n_entries, beg, end);
     if (e < beg || e >= end) return;
     const int r = trk_row[e];
     if (r < 0 || r >= n_rows) return;
@@ -755,6 +697,21 @@ int check_models(const int* cam_model_host, int n_frames, const char* what) {
 constexpr int MAX_ROWS = 1 << 30;      // the sort's network doubles a length
 
 size_t align_up(size_t x) { return (x + 255) & ~(size_t)255; }
+
+// The scan's workspace for n_rows rows and n_bsum block sums, with rest_bytes behind for what only the user has.  Null: its size.
+size_t row_stride(int n_rows) { return align_up((size_t)(n_rows > 0 ? n_rows : 1) * sizeof(int)); }
+
+size_t carve_scan_ws(void* workspace, int n_rows, int n_bsum, size_t rest_bytes, ScanWs* ws) {
+    const size_t stride = row_stride(n_rows), bsum = align_up((size_t)n_bsum * sizeof(int));
+    char* w = static_cast<char*>(workspace);
+    if (ws) *ws = {reinterpret_cast<int*>(w), reinterpret_cast<int*>(w + stride), reinterpret_cast<int*>(w + 2 * stride),
+                   reinterpret_cast<int*>(w + 2 * stride + bsum)};
+    return 2 * stride + bsum + rest_bytes;
+}
+
+// the tracks scan over n_rows positions, two sums a block; the adjacency over n_rows + 1, one
+int track_blocks(int n_rows) { return cdiv(n_rows > 0 ? n_rows : 1, SCAN); }
+int adj_blocks(int n_rows) { return cdiv(n_rows + 1, SCAN); }
 
 }  // namespace
 
@@ -819,8 +776,7 @@ extern "C" int pram_tri_components(const int* edges, int n_edges, int n_rows, in
 
 extern "C" size_t pram_tri_tracks_workspace_bytes(int n_rows) {
     if (n_rows < 0 || n_rows > MAX_ROWS) return 0;
-    const size_t n = (size_t)(n_rows > 0 ? n_rows : 1);
-    return 4 * align_up(n * sizeof(int)) + align_up((size_t)cdiv((int)n, SCAN) * 2 * sizeof(int));
+    return carve_scan_ws(nullptr, n_rows, 2 * track_blocks(n_rows), 2 * row_stride(n_rows), nullptr);      // rest: the two sums' local offsets
 }
 
 extern "C" int pram_tri_tracks(const int* label, const int* frame_off, int n_frames, int n_rows, void* workspace, size_t workspace_bytes,
@@ -832,18 +788,17 @@ extern "C" int pram_tri_tracks(const int* label, const int* frame_off, int n_fra
                  "pram_tri_tracks: needs n_frames >= 0, 0 <= n_rows <= 2^30 (0 without frames)");
     PRAM_REQUIRE(workspace_bytes >= pram_tri_tracks_workspace_bytes(n_rows), "pram_tri_tracks: workspace too small");
     hipStream_t st = (hipStream_t)stream;
-    const size_t n = (size_t)(n_rows > 0 ? n_rows : 1), stride = align_up(n * sizeof(int));
-    char* w = static_cast<char*>(workspace);
-    TrackWs ws = {reinterpret_cast<int*>(w), reinterpret_cast<int*>(w + stride), reinterpret_cast<int*>(w + 2 * stride),
-                  reinterpret_cast<int*>(w + 3 * stride), reinterpret_cast<int*>(w + 4 * stride)};
-    const int nb = cdiv((int)n, SCAN);
-    if (hipMemsetAsync(ws.size, 0, stride, st) != hipSuccess || hipMemsetAsync(ws.cursor, 0, stride, st) != hipSuccess)
-        return pram_launch_status("pram_tri_tracks");
-    if (n_rows) hipLaunchKernelGGL(tri_count_kernel, dim3(cdiv(n_rows, 256)), dim3(256), 0, st, label, n_rows, ws.size);
-    hipLaunchKernelGGL(tri_scan_blocks_kernel, dim3(nb), dim3(SCAN), 0, st, ws, n_rows);
-    hipLaunchKernelGGL(tri_scan_totals_kernel, dim3(1), dim3(256), 0, st, ws, nb, sizes, trk_off);
+    const size_t stride = row_stride(n_rows);
+    const int nb = track_blocks(n_rows);
+    ScanWs ws;
+    carve_scan_ws(workspace, n_rows, 2 * nb, 2 * stride, &ws);
+    const TrackScan u = {{ws.rest, ws.rest + stride / sizeof(int)}, sizes, trk_off};
+    if (hipMemsetAsync(ws.count, 0, 2 * stride, st) != hipSuccess) return pram_launch_status("pram_tri_tracks");      // count and cursor
+    if (n_rows) hipLaunchKernelGGL(tri_count_kernel, dim3(cdiv(n_rows, 256)), dim3(256), 0, st, label, n_rows, ws.count);
+    hipLaunchKernelGGL(tri_scan_blocks_kernel<TrackScan>, dim3(nb), dim3(SCAN), 0, st, ws.count, n_rows, n_rows, u, ws.bsum);
+    hipLaunchKernelGGL(tri_scan_totals_kernel<TrackScan>, dim3(1), dim3(256), 0, st, ws.bsum, nb, u);
     if (n_rows >= 2) {
-        hipLaunchKernelGGL(tri_fill_kernel, dim3(cdiv(n_rows, 256)), dim3(256), 0, st, label, ws, n_rows, trk_off, trk_label, trk_row);
+        hipLaunchKernelGGL(tri_fill_kernel, dim3(cdiv(n_rows, 256)), dim3(256), 0, st, label, ws, u, n_rows, trk_label, trk_row);
         hipLaunchKernelGGL(tri_sort_kernel, dim3(n_rows / 2), dim3(64), 0, st, sizes, trk_off, trk_row, n_rows);
         hipLaunchKernelGGL(tri_derive_kernel, dim3(cdiv(n_rows, 256)), dim3(256), 0, st, sizes, trk_row, frame_off, n_frames, n_rows, trk_frame,
                            trk_kpt);
@@ -866,16 +821,15 @@ extern "C" int pram_tri_triangulate(const double* norm, const float* keypoints, 
                  max_reproj_error > 0.0,
                  "pram_tri_triangulate: needs n_tracks >= 0, n_entries >= 0, n_frames >= 0, n_rows >= 0, 1 <= trials <= 2^24, min_tri_angle >= 0, max_reproj_error > 0");
     if (n_tracks == 0) return PRAM_OK;
-    const TriArgs g = {norm, keypoints, table, cam_model, cam_params, trk_row, trk_frame, n_frames, n_rows};
-    hipLaunchKernelGGL(tri_triangulate_kernel, dim3(n_tracks), dim3(64), 0, (hipStream_t)stream, g, trk_off, trk_label, n_entries, trials, seed,
-                       min_tri_angle, max_reproj_error, accept, xyz, error, kept, best, entry_keep, entry_error);
+    const Obs g = {norm, keypoints, table, cam_model, cam_params, n_frames, n_rows};
+    hipLaunchKernelGGL(tri_triangulate_kernel, dim3(n_tracks), dim3(64), 0, (hipStream_t)stream, g, trk_off, trk_label, trk_row, trk_frame,
+                       n_entries, trials, seed, min_tri_angle, max_reproj_error, accept, xyz, error, kept, best, entry_keep, entry_error);
     return pram_launch_status("pram_tri_triangulate");
 }
 
 extern "C" size_t pram_tri_adjacency_workspace_bytes(int n_rows, int n_edges) {
     if (n_rows < 0 || n_rows > MAX_ROWS || n_edges < 0 || n_edges >= MAX_ROWS) return 0;
-    const size_t n = (size_t)(n_rows > 0 ? n_rows : 1);
-    return 2 * align_up(n * sizeof(int)) + align_up((size_t)cdiv(n_rows + 1, SCAN) * sizeof(int)) + align_up(sizeof(int));
+    return carve_scan_ws(nullptr, n_rows, adj_blocks(n_rows), align_up(sizeof(int)), nullptr);      // rest: the sort's number of lists
 }
 
 extern "C" int pram_tri_adjacency(const int* edges, int n_edges, const int* frame_off, int n_frames, int n_rows, void* workspace,
@@ -887,19 +841,18 @@ extern "C" int pram_tri_adjacency(const int* edges, int n_edges, const int* fram
                  "pram_tri_adjacency: needs 0 <= n_edges < 2^30, n_frames >= 0, 0 <= n_rows <= 2^30 (0 without frames)");
     PRAM_REQUIRE(workspace_bytes >= pram_tri_adjacency_workspace_bytes(n_rows, n_edges), "pram_tri_adjacency: workspace too small");
     hipStream_t st = (hipStream_t)stream;
-    const size_t n = (size_t)(n_rows > 0 ? n_rows : 1), stride = align_up(n * sizeof(int));
-    const int nb = cdiv(n_rows + 1, SCAN);
-    char* w = static_cast<char*>(workspace);
-    AdjWs ws = {reinterpret_cast<int*>(w), reinterpret_cast<int*>(w + stride), reinterpret_cast<int*>(w + 2 * stride),
-                reinterpret_cast<int*>(w + 2 * stride + align_up((size_t)nb * sizeof(int)))};
-    if (hipMemsetAsync(ws.deg, 0, 2 * stride, st) != hipSuccess) return pram_launch_status("pram_tri_adjacency");      // deg and cursor
-    if (n_edges && n_rows) hipLaunchKernelGGL(tri_adj_count_kernel, dim3(cdiv(n_edges, 256)), dim3(256), 0, st, edges, n_edges, n_rows, ws.deg);
-    hipLaunchKernelGGL(tri_adj_scan_blocks_kernel, dim3(nb), dim3(SCAN), 0, st, ws, n_rows, adj_off);
-    hipLaunchKernelGGL(tri_adj_scan_totals_kernel, dim3(1), dim3(256), 0, st, ws, nb, n_rows);
+    const int nb = adj_blocks(n_rows);
+    ScanWs ws;
+    carve_scan_ws(workspace, n_rows, nb, align_up(sizeof(int)), &ws);
+    const AdjScan u = {{adj_off}, ws.rest, n_rows};
+    if (hipMemsetAsync(ws.count, 0, 2 * row_stride(n_rows), st) != hipSuccess) return pram_launch_status("pram_tri_adjacency");      // count and cursor
+    if (n_edges && n_rows) hipLaunchKernelGGL(tri_adj_count_kernel, dim3(cdiv(n_edges, 256)), dim3(256), 0, st, edges, n_edges, n_rows, ws.count);
+    hipLaunchKernelGGL(tri_scan_blocks_kernel<AdjScan>, dim3(nb), dim3(SCAN), 0, st, ws.count, n_rows, n_rows + 1, u, ws.bsum);
+    hipLaunchKernelGGL(tri_scan_totals_kernel<AdjScan>, dim3(1), dim3(256), 0, st, ws.bsum, nb, u);
     hipLaunchKernelGGL(tri_adj_offsets_kernel, dim3(cdiv(n_rows + 1, 256)), dim3(256), 0, st, ws, frame_off, n_frames, n_rows, adj_off, row_frame);
     if (n_edges && n_rows) {
         hipLaunchKernelGGL(tri_adj_fill_kernel, dim3(cdiv(n_edges, 256)), dim3(256), 0, st, edges, n_edges, n_rows, ws, adj_off, adj);
-        hipLaunchKernelGGL(tri_sort_kernel, dim3(n_rows), dim3(64), 0, st, ws.count, adj_off, adj, 2 * n_edges);
+        hipLaunchKernelGGL(tri_sort_kernel, dim3(n_rows), dim3(64), 0, st, u.segments, adj_off, adj, 2 * n_edges);
     }
     return pram_launch_status("pram_tri_adjacency");
 }
@@ -917,8 +870,9 @@ extern "C" int pram_tri_support(const double* norm, const float* keypoints, cons
                  min_tri_angle >= 0.0 && max_reproj_error > 0.0,
                  "pram_tri_support: needs 0 <= n_edges < 2^30, n_frames >= 0, 0 <= n_rows <= 2^30, min_support >= 0, min_tri_angle >= 0, max_reproj_error > 0");
     if (n_edges == 0) return PRAM_OK;
-    const SupArgs g = {norm, keypoints, table, cam_model, cam_params, adj_off, adj, row_frame, n_frames, n_rows, 2 * n_edges};
-    hipLaunchKernelGGL(tri_support_kernel, dim3(cdiv(n_edges, SUP_WAVES)), dim3(64 * SUP_WAVES), 0, (hipStream_t)stream, g, edges, n_edges,
+    const Obs g = {norm, keypoints, table, cam_model, cam_params, n_frames, n_rows};
+    const Adj a = {adj_off, adj, row_frame, 2 * n_edges};
+    hipLaunchKernelGGL(tri_support_kernel, dim3(cdiv(n_edges, SUP_WAVES)), dim3(64 * SUP_WAVES), 0, (hipStream_t)stream, g, a, edges, n_edges,
                        min_tri_angle, max_reproj_error, min_support, support, edges_out);
     return pram_launch_status("pram_tri_support");
 }

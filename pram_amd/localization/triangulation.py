@@ -86,6 +86,25 @@ def _up(a: np.ndarray, device) -> torch.Tensor:
     return torch.from_numpy(a).to(device)
 
 
+def _int_param(p: dict, name: str) -> dict:
+    if int(p[name]) != p[name] or p[name] < 0:
+        raise ValueError(f"{name}: an integer >= 0")
+    return {**p, name: int(p[name])}
+
+
+def _inlier_ratio(count: np.ndarray, match_off: np.ndarray) -> np.ndarray:
+    n = np.diff(match_off)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        return np.where(n > 0, count / n, np.nan)
+
+
+def _track_table(tracks: dict, keys, dev) -> dict:
+    """A track table on the host (:func:`build_tracks`', or a caller's own) -> its arrays ``keys`` on the device and its sizes."""
+    t = {k: _up(np.asarray(tracks[k], dtype=np.int32).reshape(-1), dev) for k in keys}
+    t.update(n_tracks=np.asarray(tracks["trk_off"]).reshape(-1).shape[0] - 1, n_entries=int(np.asarray(tracks["trk_row"]).shape[0]))
+    return t
+
+
 # ------------------------------------------------------------------ host side: the match store and the pair list
 def pair_matches(match_store, pairs: Sequence) -> list:
     """pairs: (name0, name1) -> per pair what colmap_utils/io.py get_matches returns, (matches int64 [m, 2], scores [m] or None):
@@ -190,11 +209,8 @@ def verify_matches(table: dict, pairs, matches: Sequence, **params) -> dict:
     v = _verify(table, pairs, matches, p["max_error"])
     M, off = v["n_matches"], v["match_off"]
     keep, kept, count = v["keep"][:M].cpu().numpy().astype(bool), v["kept"][:M].cpu().numpy(), v["count"][:len(v["pair_index"])].cpu().numpy()
-    n = np.diff(off)
-    with np.errstate(invalid="ignore", divide="ignore"):
-        ratio = np.where(n > 0, count / n, np.nan)
     return {"pair_index": v["pair_index"], "keep": [keep[a:b] for a, b in zip(off[:-1], off[1:])],
-            "kept": [kept[a:a + c] for a, c in zip(off[:-1], count)], "inlier_ratio": ratio}
+            "kept": [kept[a:a + c] for a, c in zip(off[:-1], count)], "inlier_ratio": _inlier_ratio(count, off)}
 
 
 @torch.no_grad()
@@ -243,18 +259,6 @@ def _support(table: dict, edges: torch.Tensor, n_edges: int, p: dict) -> dict:
     return out
 
 
-def _min_support(p: dict) -> dict:
-    if int(p["min_support"]) != p["min_support"] or p["min_support"] < 0:
-        raise ValueError("min_support: an integer >= 0")
-    return {**p, "min_support": int(p["min_support"])}
-
-
-def _split_rounds(p: dict) -> dict:
-    if int(p["split_rounds"]) != p["split_rounds"] or p["split_rounds"] < 0:
-        raise ValueError("split_rounds: an integer >= 0")
-    return {**p, "split_rounds": int(p["split_rounds"])}
-
-
 def adjacency(table: dict, edges) -> dict:
     """edges: int [n, 2] rows of the table (:func:`build_tracks`') -> on the host the rows' adjacency as stage 2b reads it:
     ``adj_off`` int32 [n_rows + 1], ``adj`` int32 [adj_off[-1]] (every row's neighbours ascending, one entry per edge, so a match
@@ -271,8 +275,8 @@ def support_matches(table: dict, edges, **params) -> dict:
     rays the one under the largest angle gives a point, and the two ends and w all reproject to it within max_reproj_error, that
     angle being min_tri_angle at least), ``keep`` (bool, support >= min_support) and ``edges`` int32 [n, 2], (-1, -1) where keep is
     false.  params: min_support (1 here), min_tri_angle (degrees), max_reproj_error (pixels)."""
-    p = _min_support(_params("support_matches", params, dict(min_support=1, min_tri_angle=TRI_DEFAULTS["min_tri_angle"],
-                                                             max_reproj_error=TRI_DEFAULTS["max_reproj_error"])))
+    p = _int_param(_params("support_matches", params, dict(min_support=1, min_tri_angle=TRI_DEFAULTS["min_tri_angle"],
+                                                           max_reproj_error=TRI_DEFAULTS["max_reproj_error"])), "min_support")
     e = _edges(edges)
     out = _support(table, _up(e, table["keypoints"].device), e.shape[0], p)
     sup = out["support"][:e.shape[0]].cpu().numpy()
@@ -309,11 +313,8 @@ def triangulate_tracks(table: dict, tracks: dict, **params) -> dict:
     number), ``best`` (the winning hypothesis, -1: none), and per entry ``entry_keep`` (bool) and ``entry_error`` (pixels, -1 for
     an entry that is no inlier).  params: trials, seed, min_tri_angle (degrees), max_reproj_error (pixels)."""
     p = _params("triangulate_tracks", params, TRI_DEFAULTS)
-    dev = table["keypoints"].device
-    off = np.asarray(tracks["trk_off"], dtype=np.int32).reshape(-1)
-    T, E = off.shape[0] - 1, int(np.asarray(tracks["trk_row"]).shape[0])
-    t = {k: _up(np.asarray(tracks[k], dtype=np.int32).reshape(-1), dev) for k in ("trk_off", "trk_label", "trk_row", "trk_frame")}
-    t.update(n_tracks=T, n_entries=E)
+    t = _track_table(tracks, ("trk_off", "trk_label", "trk_row", "trk_frame"), table["keypoints"].device)
+    T, E = t["n_tracks"], t["n_entries"]
     out = _triangulate(table, t, p)
     res = {k: out[k][:T].cpu().numpy() for k in _TRI_KEYS}
     res["accept"] = res["accept"].astype(bool)
@@ -334,9 +335,7 @@ def split_edges(table: dict, edges, tracks: dict, tri: dict, state=None) -> dict
     ``edges`` int32 [n, 2], (-1, -1) where an end is not FREE, and ``n_live``, the number of edges that stay."""
     dev, n = table["keypoints"].device, table["n_rows"]
     e = _edges(edges)
-    off = np.asarray(tracks["trk_off"], dtype=np.int32).reshape(-1)
-    T, E = off.shape[0] - 1, int(np.asarray(tracks["trk_row"]).shape[0])
-    t = {"trk_off": _up(off, dev), "trk_row": _up(np.asarray(tracks["trk_row"], dtype=np.int32).reshape(-1), dev), "n_tracks": T, "n_entries": E}
+    t = _track_table(tracks, ("trk_off", "trk_row"), dev)
     res = {"accept": _up(np.asarray(tri["accept"]).astype(np.int32).reshape(-1), dev),
            "entry_keep": _up(np.asarray(tri["entry_keep"]).astype(np.uint8).reshape(-1), dev)}
     if state is not None:
@@ -368,7 +367,7 @@ def triangulate_map(frames: Sequence[dict], cameras: Sequence, poses, pairs, mat
     the first of them and their tracks are what ``split_rounds=0`` gives, bit for bit; then round 1's accepted tracks in track
     order, and so on.  The dict also holds ``point_round`` int32 [P] and ``split``: int64 arrays over the further rounds that were
     begun, ``live_edges`` (the edges between FREE rows; a round that finds none ends the rounds), ``tracks`` and ``points``."""
-    p = _split_rounds(_min_support(_params("triangulate_map", params, {**DEFAULTS, **SUPPORT_DEFAULTS, **SPLIT_DEFAULTS})))
+    p = _int_param(_int_param(_params("triangulate_map", params, {**DEFAULTS, **SUPPORT_DEFAULTS, **SPLIT_DEFAULTS}), "min_support"), "split_rounds")
     table = frame_table(frames, cameras, poses, device)
     v = _verify(table, pairs, matches, p["max_error"])
     sup = _support(table, v["edges"], v["n_matches"], p) if p["min_support"] > 0 else None
@@ -396,20 +395,15 @@ def triangulate_map(frames: Sequence[dict], cameras: Sequence, poses, pairs, mat
         keep = out["entry_keep"][:E].cpu().numpy().astype(bool)
         off, frame, kpt, row = (t[k].cpu().numpy() for k in ("trk_off", "trk_frame", "trk_kpt", "trk_row"))
         host.append(({"trk_off": off, "trk_row": row, "trk_frame": frame, "trk_kpt": kpt}, {"accept": accept, "xyz": xyz, "error": err, "entry_keep": keep}))
-    count = v["count"][:Pn].cpu().numpy()
     frame_ids = np.array([f.get("id", i) for i, f in enumerate(frames)])
-    n_m = np.diff(v["match_off"])
-    with np.errstate(invalid="ignore", divide="ignore"):
-        ratio = np.where(n_m > 0, count / n_m, np.nan)
-    if p["split_rounds"] == 0:
-        res = map_tables(frame_ids, table["frame_off_host"], *host[0])
-    else:
-        res = split_tables(frame_ids, table["frame_off_host"], host)
+    res, point_round = _tables(frame_ids, table["frame_off_host"], host)
+    if p["split_rounds"] > 0:
         K = len(live)      # the rounds begun; one that found no edge or no track has no tracks and no points
         n_tracks = [rounds[r][0]["n_tracks"] if r < len(rounds) else 0 for r in range(1, K + 1)]
-        n_points = [int((res["point_round"] == r).sum()) for r in range(1, K + 1)]
-        res["split"] = {"live_edges": np.array(live, dtype=np.int64), "tracks": np.array(n_tracks, dtype=np.int64), "points": np.array(n_points, dtype=np.int64)}
-    res.update(pair_index=v["pair_index"], inlier_ratio=ratio)
+        n_points = [int((point_round == r).sum()) for r in range(1, K + 1)]
+        res.update(point_round=point_round, split={"live_edges": np.array(live, dtype=np.int64), "tracks": np.array(n_tracks, dtype=np.int64),
+                                                   "points": np.array(n_points, dtype=np.int64)})
+    res.update(pair_index=v["pair_index"], inlier_ratio=_inlier_ratio(v["count"][:Pn].cpu().numpy(), v["match_off"]))
     if sup is not None:
         M, m_off = v["n_matches"], v["match_off"]
         support = np.where(v["keep"][:M].cpu().numpy().astype(bool), sup["support"][:M].cpu().numpy(), -1).astype(np.int32)
@@ -422,43 +416,38 @@ def map_tables(frame_ids, frame_off, tracks: dict, tri: dict, first_id: int = 1)
     (:func:`triangulate_tracks`) on the host -> point_ids, point3D_xyzs, track_error, tracks, point3D_frame_ids and frames as
     triangulate_map documents them.  The accepted tracks become points first_id, first_id + 1, ... in track order; a point's
     track holds its kept entries in ascending row."""
-    frame_ids, fo = np.asarray(frame_ids), np.asarray(frame_off)
-    off, row, frame, kpt = (np.asarray(tracks[k]) for k in ("trk_off", "trk_row", "trk_frame", "trk_kpt"))
-    accept, keep, xyz = np.asarray(tri["accept"]).astype(bool), np.asarray(tri["entry_keep"]).astype(bool), np.asarray(tri["xyz"])
-    which = np.nonzero(accept)[0]
-    ids = np.arange(first_id, first_id + which.shape[0], dtype=np.int64)
-    row_pid = np.full(int(fo[-1]), -1, dtype=np.int64)
-    row_xyz = np.zeros((int(fo[-1]), 3), dtype=np.float64)
-    out: Dict[int, tuple] = {}
-    for pid, ti in zip(ids.tolist(), which.tolist()):
-        e = np.arange(off[ti], off[ti + 1])[keep[off[ti]:off[ti + 1]]]
-        out[pid] = (frame_ids[frame[e]], kpt[e].astype(np.int64))
-        row_pid[row[e]], row_xyz[row[e]] = pid, xyz[ti]
-    return {"point_ids": ids, "point3D_xyzs": xyz[which].reshape(-1, 3), "track_error": np.asarray(tri["error"])[which], "tracks": out,
-            "point3D_frame_ids": {pid: t[0] for pid, t in out.items()},
-            "frames": [{"point3D_ids": row_pid[fo[f]:fo[f + 1]], "xyzs": row_xyz[fo[f]:fo[f + 1]]} for f in range(len(fo) - 1)]}
+    return _tables(frame_ids, frame_off, [(tracks, tri)], first_id)[0]
 
 
 def split_tables(frame_ids, frame_off, rounds: Sequence) -> dict:
     """:func:`map_tables` over several rounds.  rounds: per round (tracks, tri) on the host, round 0 first -> map_tables' dict with
     the rounds' points numbered one after the other, plus ``point_round`` int32 [P].  A row that a round kept is in no later
     round's table, so a keypoint has one point at most."""
-    fo = np.asarray(frame_off)
-    parts, nxt = [], 1
+    res, point_round = _tables(frame_ids, frame_off, rounds)
+    return {**res, "point_round": point_round}
+
+
+def _tables(frame_ids, frame_off, rounds: Sequence, first_id: int = 1) -> tuple:
+    """The one builder behind :func:`map_tables` and :func:`split_tables`: a single pass over the rounds' accepted tracks fills the
+    per-row point id and xyz -> (map_tables' dict, the points' round int32 [P])."""
+    frame_ids, fo = np.asarray(frame_ids), np.asarray(frame_off)
+    row_pid = np.full(int(fo[-1]), -1, dtype=np.int64)
+    row_xyz = np.zeros((int(fo[-1]), 3), dtype=np.float64)
+    out: Dict[int, tuple] = {}
+    ids, xyzs, errs, nxt = [], [], [], first_id
     for tracks, tri in rounds:
-        parts.append(map_tables(frame_ids, fo, tracks, tri, first_id=nxt))
-        nxt += parts[-1]["point_ids"].shape[0]
-    res = {k: np.concatenate([q[k] for q in parts]) for k in ("point_ids", "point3D_xyzs", "track_error")}
-    res["tracks"] = {pid: t for q in parts for pid, t in q["tracks"].items()}
-    res["point3D_frame_ids"] = {pid: t[0] for pid, t in res["tracks"].items()}
-    n = int(fo[-1])
-    row_pid = np.concatenate([f["point3D_ids"] for f in parts[0]["frames"]] + [np.zeros(0, dtype=np.int64)])
-    row_xyz = np.concatenate([f["xyzs"] for f in parts[0]["frames"]] + [np.zeros((0, 3))])
-    for q in parts[1:]:
-        pid = np.concatenate([f["point3D_ids"] for f in q["frames"]] + [np.zeros(0, dtype=np.int64)])
-        has = pid >= 1
-        row_pid[has], row_xyz[has] = pid[has], np.concatenate([f["xyzs"] for f in q["frames"]] + [np.zeros((0, 3))])[has]
-    assert row_pid.shape[0] == n
-    res["frames"] = [{"point3D_ids": row_pid[fo[f]:fo[f + 1]], "xyzs": row_xyz[fo[f]:fo[f + 1]]} for f in range(len(fo) - 1)]
-    res["point_round"] = np.repeat(np.arange(len(parts)), [q["point_ids"].shape[0] for q in parts]).astype(np.int32)
-    return res
+        off, row, frame, kpt = (np.asarray(tracks[k]) for k in ("trk_off", "trk_row", "trk_frame", "trk_kpt"))
+        accept, keep, xyz = np.asarray(tri["accept"]).astype(bool), np.asarray(tri["entry_keep"]).astype(bool), np.asarray(tri["xyz"])
+        which = np.nonzero(accept)[0]
+        ids.append(np.arange(nxt, nxt + which.shape[0], dtype=np.int64))
+        xyzs.append(xyz[which].reshape(-1, 3))
+        errs.append(np.asarray(tri["error"])[which])
+        nxt += which.shape[0]
+        for pid, ti in zip(ids[-1].tolist(), which.tolist()):
+            e = np.arange(off[ti], off[ti + 1])[keep[off[ti]:off[ti + 1]]]
+            out[pid] = (frame_ids[frame[e]], kpt[e].astype(np.int64))
+            row_pid[row[e]], row_xyz[row[e]] = pid, xyz[ti]
+    res = {"point_ids": np.concatenate(ids), "point3D_xyzs": np.concatenate(xyzs), "track_error": np.concatenate(errs), "tracks": out,
+           "point3D_frame_ids": {pid: t[0] for pid, t in out.items()},
+           "frames": [{"point3D_ids": row_pid[fo[f]:fo[f + 1]], "xyzs": row_xyz[fo[f]:fo[f + 1]]} for f in range(len(fo) - 1)]}
+    return res, np.repeat(np.arange(len(ids)), [i.shape[0] for i in ids]).astype(np.int32)

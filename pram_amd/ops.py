@@ -2245,12 +2245,31 @@ def kmeans_assign(x: torch.Tensor, centers: torch.Tensor):
 # ---- triangulation (csrc/triangulate.hip; pram_amd/localization/triangulation.py drives these) --------------------------------
 TRI_GN_STEPS, TRI_FRAME_COLS, TRI_CC_STATE_WORDS = 5, 16, 4      # include/pram_hip.h
 TRI_CC_DONE = 1      # the word of the components' state that says the labels are final
+TRI_ROW_FREE, TRI_ROW_TAKEN, TRI_ROW_DEAD = 0, 1, 2      # include/pram_hip.h
 
 
 def _tri_chk(items):
     for t, nm, dt in items:
         _chk(t, nm, dt)
         assert t.is_contiguous(), nm
+
+
+def _tri_views(norm, keypoints, table, cam_model, cam_params, n_frames: int, n_rows: int):
+    """The five tensors stage 2b and stage 4 read of the frame table, and their sizes."""
+    _tri_chk(((norm, "norm", torch.float64), (keypoints, "keypoints", torch.float32), (table, "table", torch.float64),
+              (cam_model, "cam_model", torch.int32), (cam_params, "cam_params", torch.float64)))
+    assert norm.numel() >= 2 * n_rows and keypoints.numel() >= 2 * n_rows and table.numel() >= TRI_FRAME_COLS * n_frames
+    assert cam_model.numel() >= n_frames and cam_params.numel() >= POSE_CAM_PARAMS * n_frames
+
+
+def _tri_workspace(need: int, refusal: str, workspace: Optional[torch.Tensor], device) -> torch.Tensor:
+    """need: what the entry's *_workspace_bytes returned (0: it refuses the sizes) -> ``workspace`` checked, or a new one."""
+    if need == 0:
+        raise _lib.PramHipError(refusal)
+    if workspace is None:
+        workspace = torch.empty(need, device=device, dtype=torch.uint8)
+    _chk(workspace, "workspace", torch.uint8)
+    return workspace
 
 
 def _tri_models(cam_model_host, n_frames: int):
@@ -2330,12 +2349,7 @@ def tri_tracks(label: torch.Tensor, frame_off: torch.Tensor, n_frames: int, n_ro
     F, n = int(n_frames), int(n_rows)
     assert label.numel() >= n and frame_off.numel() >= F + 1
     dev = label.device
-    need = int(L.pram_tri_tracks_workspace_bytes(n))
-    if need == 0:
-        raise _lib.PramHipError("pram_tri_tracks: more than 2^30 rows")
-    if workspace is None:
-        workspace = torch.empty(need, device=dev, dtype=torch.uint8)
-    _chk(workspace, "workspace", torch.uint8)
+    workspace = _tri_workspace(int(L.pram_tri_tracks_workspace_bytes(n)), "pram_tri_tracks: more than 2^30 rows", workspace, dev)
     i32 = lambda m: torch.empty(max(m, 1), device=dev, dtype=torch.int32)
     out = {"trk_off": i32(n // 2 + 2), "trk_label": i32(n // 2 + 1), "trk_row": i32(n), "trk_frame": i32(n), "trk_kpt": i32(n), "sizes": i32(2)}
     _lib.check(L.pram_tri_tracks(_p(label), _p(frame_off), F, n, _p(workspace), workspace.numel(), _p(out["trk_off"]), _p(out["trk_label"]),
@@ -2351,12 +2365,11 @@ def tri_triangulate(norm: torch.Tensor, keypoints: torch.Tensor, table: torch.Te
     [T, 3], error float64 [T], kept int32 [T], best int32 [T] (the winning hypothesis, -1: none), entry_keep uint8 [E], entry_error
     float64 [E].  min_tri_angle in radians."""
     L = _lib.load()
-    _tri_chk(((norm, "norm", torch.float64), (keypoints, "keypoints", torch.float32), (table, "table", torch.float64),
-              (cam_model, "cam_model", torch.int32), (cam_params, "cam_params", torch.float64), (trk_off, "trk_off", torch.int32),
-              (trk_label, "trk_label", torch.int32), (trk_row, "trk_row", torch.int32), (trk_frame, "trk_frame", torch.int32)))
     T, E, F, n = int(n_tracks), int(n_entries), int(n_frames), int(n_rows)
-    assert norm.numel() >= 2 * n and keypoints.numel() >= 2 * n and table.numel() >= TRI_FRAME_COLS * F and cam_model.numel() >= F
-    assert cam_params.numel() >= POSE_CAM_PARAMS * F and trk_off.numel() >= T + 1 and trk_label.numel() >= T and trk_row.numel() >= E and trk_frame.numel() >= E
+    _tri_views(norm, keypoints, table, cam_model, cam_params, F, n)
+    _tri_chk(((trk_off, "trk_off", torch.int32), (trk_label, "trk_label", torch.int32), (trk_row, "trk_row", torch.int32),
+              (trk_frame, "trk_frame", torch.int32)))
+    assert trk_off.numel() >= T + 1 and trk_label.numel() >= T and trk_row.numel() >= E and trk_frame.numel() >= E
     dev = norm.device
     new = lambda m, dt, *rest: torch.empty(max(m, 1), *rest, device=dev, dtype=dt)
     out = {"accept": new(T, torch.int32), "xyz": new(T, torch.float64, 3), "error": new(T, torch.float64), "kept": new(T, torch.int32),
@@ -2379,12 +2392,8 @@ def tri_adjacency(edges: torch.Tensor, n_edges: int, frame_off: torch.Tensor, n_
     m, F, n = int(n_edges), int(n_frames), int(n_rows)
     assert edges.numel() >= 2 * m and frame_off.numel() >= F + 1
     dev = edges.device
-    need = int(L.pram_tri_adjacency_workspace_bytes(n, m))
-    if need == 0:
-        raise _lib.PramHipError("pram_tri_adjacency: more than 2^30 rows or 2^30 - 1 edges")
-    if workspace is None:
-        workspace = torch.empty(need, device=dev, dtype=torch.uint8)
-    _chk(workspace, "workspace", torch.uint8)
+    workspace = _tri_workspace(int(L.pram_tri_adjacency_workspace_bytes(n, m)), "pram_tri_adjacency: more than 2^30 rows or 2^30 - 1 edges",
+                               workspace, dev)
     i32 = lambda k: torch.empty(max(k, 1), device=dev, dtype=torch.int32)
     out = {"adj_off": i32(n + 1), "adj": i32(2 * m), "row_frame": i32(n)}
     _lib.check(L.pram_tri_adjacency(_p(edges), m, _p(frame_off), F, n, _p(workspace), workspace.numel(), _p(out["adj_off"]), _p(out["adj"]),
@@ -2399,22 +2408,16 @@ def tri_support(norm: torch.Tensor, keypoints: torch.Tensor, table: torch.Tensor
     (the witnesses of third frames that confirm the edge) and edges int32 [n_edges, 2]: the edge where support >= min_support,
     (-1, -1) elsewhere.  min_tri_angle in radians."""
     L = _lib.load()
-    _tri_chk(((norm, "norm", torch.float64), (keypoints, "keypoints", torch.float32), (table, "table", torch.float64),
-              (cam_model, "cam_model", torch.int32), (cam_params, "cam_params", torch.float64), (edges, "edges", torch.int32),
-              (adj_off, "adj_off", torch.int32), (adj, "adj", torch.int32), (row_frame, "row_frame", torch.int32)))
     m, F, n = int(n_edges), int(n_frames), int(n_rows)
-    assert norm.numel() >= 2 * n and keypoints.numel() >= 2 * n and table.numel() >= TRI_FRAME_COLS * F and cam_model.numel() >= F
-    assert cam_params.numel() >= POSE_CAM_PARAMS * F and edges.numel() >= 2 * m and adj_off.numel() >= n + 1 and adj.numel() >= 2 * m
-    assert row_frame.numel() >= n
+    _tri_views(norm, keypoints, table, cam_model, cam_params, F, n)
+    _tri_chk(((edges, "edges", torch.int32), (adj_off, "adj_off", torch.int32), (adj, "adj", torch.int32), (row_frame, "row_frame", torch.int32)))
+    assert edges.numel() >= 2 * m and adj_off.numel() >= n + 1 and adj.numel() >= 2 * m and row_frame.numel() >= n
     dev = norm.device
     out = {"support": torch.empty(max(m, 1), device=dev, dtype=torch.int32), "edges": torch.empty(max(m, 1), 2, device=dev, dtype=torch.int32)}
     _lib.check(L.pram_tri_support(_p(norm), _p(keypoints), _p(table), _p(cam_model), _p(cam_params), _p(edges), m, _p(adj_off), _p(adj),
                                   _p(row_frame), F, n, float(min_tri_angle), float(max_reproj_error), int(min_support), _p(out["support"]),
                                   _p(out["edges"]), _st()), "pram_tri_support")
     return out
-
-
-TRI_ROW_FREE, TRI_ROW_TAKEN, TRI_ROW_DEAD = 0, 1, 2      # include/pram_hip.h
 
 
 def tri_split(trk_off: torch.Tensor, trk_row: torch.Tensor, n_tracks: int, n_entries: int, accept: torch.Tensor, entry_keep: torch.Tensor,

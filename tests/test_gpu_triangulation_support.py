@@ -71,6 +71,31 @@ def test_adjacency_edge_counts(TG, cases, n_edges):
     assert n_edges < 255 or 0 < SR.valid_edges(n, e).sum() < n_edges
 
 
+def test_tracks_and_adjacency_past_the_first_chunk_of_block_totals(TG, dev):
+    """65 793 rows are 258 blocks of 256 (the adjacency scans one position more): the scan's second level, one workgroup over the
+    block totals in chunks of 256, takes a second chunk, and one track and the tail of adj_off have their base there.  Only
+    frame_off matters to the two entries; the counts below are the restatement's, asserted so that a change of the inputs cannot
+    take the second chunk out of play."""
+    n, F = 256 * 256 + 257, 40
+    frame_off = np.linspace(0, n, F + 1).astype(int)
+    rng = np.random.RandomState(3)
+    edges = np.concatenate([rng.randint(0, n, size=(4000, 2)), [[n - 1, n - 2], [-1, 5], [7, n], [9, 9]]])
+    kp = np.random.RandomState(4).uniform(0.0, TR.WIDTH, size=(n, 2)).astype(np.float32)
+    frames = [{"keypoints": kp[a:b]} for a, b in zip(frame_off[:-1], frame_off[1:])]
+    poses = (np.tile([1.0, 0.0, 0.0, 0.0], (F, 1)), np.zeros((F, 3)))
+    table = TG.frame_table(frames, [TR.CAMERAS[1]] * F, poses, dev)
+    assert table["n_rows"] == n and np.array_equal(table["frame_off_host"], frame_off)
+    label = TR.components(n, edges)
+    want = {"label": label, **TR.tracks(label, frame_off)}
+    want_adj = SR.adjacency(n, edges, frame_off)
+    T, E = len(want["trk_label"]), len(want["trk_row"])
+    assert int(SR.valid_edges(n, edges).sum()) == 4001 and (T, E) == (3546, 7547) and int(np.diff(want["trk_off"]).max()) == 7
+    assert len(want_adj["adj"]) == 8002 and want["trk_label"][want["trk_label"] >= 256 * 256].tolist() == [65791]
+    got = TG.build_tracks(table, edges)
+    assert set(got) == set(want) and all(np.array_equal(got[k], want[k]) for k in want)
+    assert _adj_equal(TG.adjacency(table, edges), want_adj)
+
+
 @pytest.mark.parametrize("name", ["star", "glued", "tri", "sweep"])
 def test_support_equals_the_restatement_and_repeats(TG, cases, name):
     s, e, r, table = cases[name]

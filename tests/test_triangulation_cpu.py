@@ -42,7 +42,7 @@ def test_symbols_declared_and_exported(hip_lib):
     assert int(re.search(r"#define PRAM_POSE_UNDISTORT_STEPS (\d+)", header).group(1)) == PR.UNDISTORT_STEPS
     assert (ROOT / "pram_amd" / "csrc" / "triangulate.hip").exists()
     cam_h, pose = (ROOT / "pram_amd" / "csrc" / "camera.h").read_text(), (ROOT / "pram_amd" / "csrc" / "pose.hip").read_text()
-    for helper in ("struct Cam", "cam_unify(int model", "void distort(", "void distort_jac("):      # moved, not copied
+    for helper in ("struct Cam", "cam_unify(int model", "void distort(", "void distort_jac(", "struct V3"):      # moved, not copied
         assert helper in cam_h and helper not in pose, helper
 
 
