@@ -440,7 +440,7 @@ int pram_sfd2_conv1_x3_f32(const float* img, int batch, int h, int w, const void
 
 /* NCHW [b][3][h][w] -> NHWC4 [b][h][w][4] (zero 4th channel) */
 int pram_image_to_nhwc4_f32(const float* img, float* out, int batch, int h, int w, void* stream);
-/* NHWC [b][h][w][c] -> NCHW [b][c][h][w] (for the reference-layout dict entries) */
+/* NHWC [b][h][w][c] -> NCHW [b][c][h][w] (for the reference-layout dict entries); any extent = 0: PRAM_OK, nothing written */
 int pram_nhwc_to_nchw_f32(const float* in, float* out, int batch, int h, int w, int c, void* stream);
 
 /* softmax over 65 channels, drop dustbin, 8x8 depth-to-space (nets/sfd2.py:294-300; K2).
@@ -448,7 +448,8 @@ int pram_nhwc_to_nchw_f32(const float* in, float* out, int batch, int h, int w, 
 int pram_score_map_f32(const float* logits, float* score, int batch, int hc, int wc, void* stream);
 
 /* simple_nms (nets/sfd2.py:20-35; K3): 1 + 2 suppression rounds, window 2r+1 (r <= 4), exact equality.
- * workspace: pram_simple_nms_workspace_bytes (four fp32 images per frame). */
+ * workspace: pram_simple_nms_workspace_bytes (four fp32 images per frame); its contents on entry do not matter.
+ * batch, h or w = 0: returns PRAM_OK, launches and writes nothing. */
 size_t pram_simple_nms_workspace_bytes(int batch, int h, int w);
 int pram_simple_nms_f32(const float* score, float* nms, int batch, int h, int w, int radius,
                         void* workspace, void* stream);
@@ -461,7 +462,9 @@ size_t pram_select_keypoints_workspace_bytes(int batch, int h, int w, int max_ke
  * semantics), >= 0 = every image uses that image's count (reference tests element 0).
  * kpts [b][max_keypoints][2] (x,y) fp32, scores [b][max_keypoints], counts [b].
  * max_keypoints > 0: up to 8192 the top-k is sorted in LDS, beyond that in the workspace (the reference has no bound,
- * nets/sfd2.py:38-50); >= h*w = keep all (the reference's max_keypoints < 0, nets/sfd2.py:324: row-major order, never sorted). */
+ * nets/sfd2.py:38-50); >= h*w = keep all (the reference's max_keypoints < 0, nets/sfd2.py:324: row-major order, never sorted).
+ * Rows of kpts / scores at and beyond counts[b] are not written.  batch, h or w = 0: returns PRAM_OK, launches and writes nothing,
+ * counts included (there is no pixel to count). */
 int pram_select_keypoints_f32(const float* nms, int batch, int h, int w, float conf_th,
                               int min_keypoints, int border, int max_keypoints, int fallback_ref,
                               float* kpts, float* scores, int* counts, void* workspace, void* stream);
@@ -508,7 +511,10 @@ int pram_sample_rows_f32(const float* rowmap, const int* pix2row, int batch, int
 int pram_l2norm_rows_f32(float* x, int rows, int cols, void* stream);
 
 /* score lookup of ResNet4x.sample (nets/sfd2.py:367): out[b][i] = score_map[b*map_stride + y_i*w + x_i]
- * (map_stride = 0 reproduces the reference's score_map[0, ...]) */
+ * (map_stride = 0 reproduces the reference's score_map[0, ...]).  kpts [b][n_max][2], out [b][n_max]; lens [b] or NULL: frame b
+ * has min(lens[b], n_max) live keypoints (a negative length: none), the rows of out beyond them are not written.  A keypoint
+ * outside the map — x < 0, x >= w, y < 0, y >= h, tested on the float coordinates before the truncation, so a NaN is outside
+ * too — scores 0; nothing is read for it. */
 int pram_score_lookup_f32(const float* score_map, long long map_stride, int h, int w, const float* kpts,
                           const int* lens, int batch, int n_max, float* out, void* stream);
 

@@ -1127,7 +1127,8 @@ extern "C" int pram_image_to_nhwc4_f32(const float* img, float* out, int batch, 
 
 extern "C" int pram_nhwc_to_nchw_f32(const float* in, float* out, int batch, int h, int w, int c, void* stream) {
     PRAM_REQUIRE(in && out, "pram_nhwc_to_nchw_f32: null pointer");
-    if (batch == 0) return PRAM_OK;
+    PRAM_REQUIRE(batch >= 0 && h >= 0 && w >= 0 && c >= 0, "pram_nhwc_to_nchw_f32: negative extent");
+    if (batch == 0 || h == 0 || w == 0 || c == 0) return PRAM_OK;      // nothing to do: a zero-sized grid is not a launch
     hipLaunchKernelGGL(nhwc_to_nchw_kernel, dim3(cdiv(h * w, 32), cdiv(c, 32), batch), dim3(256), 0, (hipStream_t)stream, in,
                        out, h * w, c);
     return pram_launch_status("pram_nhwc_to_nchw_f32");

@@ -571,16 +571,23 @@ __global__ __launch_bounds__(256) void l2norm_rows_kernel(float* __restrict__ x,
     }
 }
 
+// out[b][n] for the live keypoints only (live_keypoints: lens[b] clamped to n_max, a negative length = no rows); a keypoint outside
+// the map (NaN included: it fails every comparison) scores 0 — the coordinates are tested as floats, before the truncation.
 __global__ void score_lookup_kernel(const float* __restrict__ sm, long long map_stride, int h, int w,
                                     const float* __restrict__ kpts, const int* __restrict__ lens, int n_max,
                                     float* __restrict__ out) {
     const int b = blockIdx.y;
     const int n = blockIdx.x * blockDim.x + threadIdx.x;
-    const int len = lens ? lens[b] : n_max;
+    const int len = live_keypoints(lens, b, n_max);
     if (n >= len) return;
-    const long long x = (long long)kpts[((size_t)b * n_max + n) * 2];       // .long() truncation
-    const long long y = (long long)kpts[((size_t)b * n_max + n) * 2 + 1];
-    out[(size_t)b * n_max + n] = sm[b * map_stride + y * w + x];
+    const float fx = kpts[((size_t)b * n_max + n) * 2], fy = kpts[((size_t)b * n_max + n) * 2 + 1];
+    const bool inside = fx >= 0.f && fx < (float)w && fy >= 0.f && fy < (float)h;
+    float v = 0.f;
+    if (inside) {
+        const long long x = (long long)fx, y = (long long)fy;       // .long() truncation
+        v = sm[b * map_stride + y * w + x];
+    }
+    out[(size_t)b * n_max + n] = v;
 }
 
 }  // namespace
@@ -600,7 +607,8 @@ extern "C" int pram_simple_nms_f32(const float* score, float* nms, int batch, in
     PRAM_REQUIRE(score && nms && workspace, "pram_simple_nms_f32: null pointer");
     PRAM_REQUIRE(radius >= 0 && radius <= NMS_RMAX, "pram_simple_nms_f32: radius %d > %d", radius, NMS_RMAX);
     PRAM_REQUIRE(score != nms, "pram_simple_nms_f32: in-place is not supported");
-    if (batch == 0) return PRAM_OK;
+    PRAM_REQUIRE(batch >= 0 && h >= 0 && w >= 0, "pram_simple_nms_f32: negative extent");
+    if (batch == 0 || h == 0 || w == 0) return PRAM_OK;      // nothing to do: a zero-sized grid is not a launch
     hipStream_t st = (hipStream_t)stream;
     float* ws = (float*)workspace;
     switch (radius) {
@@ -653,7 +661,8 @@ extern "C" int pram_select_keypoints_f32(const float* nms, int batch, int h, int
     PRAM_REQUIRE(max_keypoints > 0, "pram_select_keypoints_f32: max_keypoints=%d must be positive (>= h*w = keep all)", max_keypoints);
     PRAM_REQUIRE(fallback_ref < batch, "pram_select_keypoints_f32: fallback_ref out of range");
     PRAM_REQUIRE(conf_th > 0.f, "pram_select_keypoints_f32: conf_th must be positive");
-    if (batch == 0) return PRAM_OK;
+    PRAM_REQUIRE(batch >= 0 && h >= 0 && w >= 0, "pram_select_keypoints_f32: negative extent");
+    if (batch == 0 || h == 0 || w == 0) return PRAM_OK;      // no pixels: nothing is launched, nothing written (counts included)
     hipStream_t st = (hipStream_t)stream;
     SelWs ws = sel_carve(workspace, batch, h, w, max_keypoints, nullptr);
     if (hipMemsetAsync(ws.cnt_hi, 0, (size_t)batch * 4, st) != hipSuccess) {
