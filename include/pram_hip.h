@@ -1238,6 +1238,50 @@ size_t pram_sor_workspace_bytes(long long n);
 int pram_sor_select(const double* avg, long long n, double std_ratio, void* workspace, size_t workspace_bytes, double* stats,
                     unsigned char* mask, int* inlier_idx, int* count, void* stream);
 
+/* ---- localisation against retrieved database frames (csrc/retrieval.hip; pram_amd/localization/retrieval.py drives these) -----
+ * The reference's offline localizer (localization/pose_estimator.py): every (query, retrieved frame) pair is a plan row of the
+ * candidate stage — all keypoints of the query against the frame's rows that carry a 3D point.  The store adds valid_rows [n_valid]
+ * / valid_off [n_frames + 1]: per frame the rows (indices into the concatenated arrays, original order) whose point id is not -1
+ * and is in the point table pt_ids.  pram_cand_gather and pram_cand_correspond run on pram_retr_plan's table unchanged when they
+ * are handed valid_rows as sel_rows; pram_refine_merge with init_on all 0 stacks a query's slots; pram_pose_* solve either the
+ * stack (seg_k = 1) or every pair (seg_k = n_db).  Every entry refuses (PRAM_E_ARG) a null or misaligned pointer and a negative
+ * size; nothing waits for the stream and nothing is allocated. */
+
+/* retrieval [batch][n_db] store frame indices (-1 padded), counts [batch] query keypoints, enable [batch] or null -> plan
+ * [PRAM_CAND_PLAN_COLS][batch * n_db].  A live slot: query b, sid -1, frame, semantic 0, lens0 = counts[b], lens1 = the frame's valid
+ * rows, tok_off -1, row0 = frame_off[frame], sel_off = valid_off[frame], order = slot.  An empty pair (frame -1, both lengths 0,
+ * row0 0, sel_off -1): a slot < 0 or >= n_frames, a frame without valid rows (pose_estimator.py:65-66), counts[b] <= 0, enable[b]
+ * == 0.  The covisibility stage is planned by the same entry: its retrieval list is pram_covis_topk's.  Needs n_db > 0. */
+int pram_retr_plan(const int* retrieval, const int* counts, const int* enable, const int* frame_off, const int* valid_off,
+                   int batch, int n_db, int n_frames, int n_valid, int* plan, void* stream);
+
+/* Per pair, the rows of pram_cand_correspond's list [pairs][t0] whose point has obs_th observations or more
+ * (pose_estimator.py:122), in their order, into m_* [pairs][t0]; m_count [pairs].  Observations of a point: pt_off[i + 1] - pt_off[i]
+ * (duplicates counted), 0 for an id pt_ids does not hold; obs_th <= 0 keeps every row.  Rows beyond m_count are not written.  The
+ * output must not be the input. */
+int pram_retr_filter(const long long* r_kpt_ids, const float* r_kpts, const float* r_ref_kpts, const long long* r_point3d_ids,
+                     const double* r_xyz, const int* r_sids, const int* r_count, int pairs, int t0, const long long* pt_ids,
+                     const int* pt_off, int n_points, int obs_th, long long* m_kpt_ids, float* m_kpts, float* m_ref_kpts,
+                     long long* m_point3d_ids, double* m_xyz, int* m_sids, int* m_count, void* stream);
+
+/* pose_estimator_iterative's choice among a query's slots (pose_estimator.py:429-556, 558) from the per-pair success, num_inliers
+ * and filtered count [batch][n_db]: walk the slots in order, pass over count < 8 or success == 0, remember as best the strictly
+ * largest num_inliers above 0 (the first wins a tie), accept the first slot with num_inliers >= inlier_th; with none accepted
+ * the best is taken when its num_inliers >= min_best_inliers.  chosen [batch][3] = (kept slot or -1, status 1 accepted / 2 best
+ * taken / 0 failed, best slot met up to the end of the walk or -1).  Needs n_db > 0. */
+int pram_retr_select(const int* success, const int* num_inliers, const int* count, int batch, int n_db, int inlier_th,
+                     int min_best_inliers, int* chosen, void* stream);
+
+/* get_covisibility_frames (pose_estimator.py:18-42) for n store frames at once: for every valid row of frames[s], every entry of
+ * its point's frame list counts once (duplicates counted), the frame itself only with include_self != 0.  best_frames
+ * [n][k] (-1 padded), best_counts [n][k] (0 padded), n_found [n]; order: count descending, then store frame index ascending, at the
+ * cut too.  A frames[s] outside [0, n_frames) finds nothing.  hist [n][n_frames] int32 is the caller's workspace, zeroed by the
+ * entry.  Needs k >= 1 (k may exceed n_frames) and n_frames >= 1. */
+int pram_covis_topk(const int* frames, int n, const int* valid_off, const int* valid_rows, const long long* point3d_ids, int n_rows,
+                    int n_valid, const long long* pt_ids, const int* pt_off, const int* pt_frames, int n_points, int n_entries,
+                    int n_frames, int k, int include_self, int* hist, int* best_frames, int* best_counts, int* n_found,
+                    void* stream);
+
 #ifdef __cplusplus
 }
 #endif

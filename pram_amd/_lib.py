@@ -150,6 +150,10 @@ _SIGS = {
     "pram_knn_mean_distance": (I, [P, LL, I, P, P]),
     "pram_sor_workspace_bytes": (SZ, [LL]),
     "pram_sor_select": (I, [P, LL, C.c_double, P, SZ, P, P, P, P, P]),
+    "pram_retr_plan": (I, [P, P, P, P, P, I, I, I, I, P, P]),
+    "pram_retr_filter": (I, [P, P, P, P, P, P, P, I, I, P, P, I, I, P, P, P, P, P, P, P, P]),
+    "pram_retr_select": (I, [P, P, P, I, I, I, I, P, P]),
+    "pram_covis_topk": (I, [P, I, P, P, P, I, I, P, P, P, I, I, I, I, I, P, P, P, P, P]),
 }
 
 

@@ -2483,3 +2483,79 @@ def sor_select(avg: torch.Tensor, std_ratio: float, workspace: Optional[torch.Te
                                  _p(out["inlier_idx"]), _p(out["count"]), _st()), "pram_sor_select")
     out["mask"], out["inlier_idx"] = out["mask"][:n], out["inlier_idx"][:n]
     return out
+
+
+# ---- localisation against retrieved database frames (csrc/retrieval.hip; pram_amd/localization/retrieval.py drives these) ----
+COVIS_WORKSPACE_BYTES = 64 << 20      # the histogram [n, n_frames] of one covis_topk call stays under this: longer lists go in chunks
+
+
+def retr_plan(retrieval: torch.Tensor, counts: torch.Tensor, store, enable: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """retrieval int32 [B, n_db] (store frame indices, -1 padded), counts int32 [B], ``store``: the device tables of a DatabaseStore
+    -> plan int32 [CAND_PLAN_COLS, B * n_db] whose sel_off points into valid_rows."""
+    L = _lib.load()
+    for t, nm in ((retrieval, "retrieval"), (counts, "counts")) + (((enable, "enable"),) if enable is not None else ()):
+        _chk(t, nm, torch.int32)
+        assert t.is_contiguous(), nm
+    assert retrieval.dim() == 2 and counts.numel() == retrieval.shape[0] and (enable is None or enable.numel() == counts.numel())
+    B, n_db = retrieval.shape
+    plan = torch.empty(CAND_PLAN_COLS, B * n_db, device=retrieval.device, dtype=torch.int32)
+    s = store
+    _lib.check(L.pram_retr_plan(_p(retrieval), _p(counts), _p(enable), _p(s["frame_off"]), _p(s["valid_off"]), B, n_db, int(s["n_frames"]),
+                                int(s["n_valid"]), _p(plan), _st()), "pram_retr_plan")
+    return plan
+
+
+def retr_filter(cor: dict, store, obs_th: int, out: Optional[dict] = None) -> dict:
+    """cor: cand_correspond's dict -> the same lists [P, t0, ...] holding, per pair and in order, the rows whose point has obs_th
+    observations or more, and their count.  ``out``: buffers to write into (the tests pre-fill them)."""
+    L = _lib.load()
+    P, t0 = _cor_chk(cor, "correspondences")
+    if out is None:
+        out = _cor_alloc(P, t0, cor["count"].device)
+    else:
+        assert _cor_chk(out, "out") == (P, t0)
+    s = store
+    _lib.check(L.pram_retr_filter(*[_p(cor[k]) for k in MATCH_KEYS], _p(cor["count"]), P, t0, _p(s["pt_ids"]), _p(s["pt_off"]), int(s["n_points"]),
+                                  int(obs_th), *[_p(out[k]) for k in MATCH_KEYS], _p(out["count"]), _st()), "pram_retr_filter")
+    return out
+
+
+def retr_select(success: torch.Tensor, num_inliers: torch.Tensor, count: torch.Tensor, n_db: int, inlier_th: int, min_best_inliers: int) -> torch.Tensor:
+    """success / num_inliers / count int32 [B * n_db] -> int32 [B, 3]: kept slot (-1 none), status (1 accepted, 2 best taken, 0
+    failed), best slot (-1 none)."""
+    L = _lib.load()
+    for t, nm in ((success, "success"), (num_inliers, "num_inliers"), (count, "count")):
+        _chk(t, nm, torch.int32)
+        assert t.is_contiguous() and t.numel() == success.numel(), nm
+    n_db = int(n_db)
+    assert n_db >= 1 and success.numel() % n_db == 0
+    B = success.numel() // n_db
+    chosen = torch.empty(B, 3, device=success.device, dtype=torch.int32)
+    _lib.check(L.pram_retr_select(_p(success), _p(num_inliers), _p(count), B, n_db, int(inlier_th), int(min_best_inliers), _p(chosen), _st()),
+               "pram_retr_select")
+    return chosen
+
+
+def covis_topk(frames: torch.Tensor, store, k: int, include_self: bool = False, workspace: Optional[torch.Tensor] = None):
+    """frames int32 [n] (store frame indices), ``store``: the device tables of a DatabaseStore -> (best_frames int32 [n, k] (-1
+    padded), best_counts int32 [n, k], n_found int32 [n]).  workspace: int32 [>= min(n, chunk) * n_frames], dirty or not; the
+    frames go through the entry in chunks whose histogram stays under COVIS_WORKSPACE_BYTES."""
+    L = _lib.load()
+    _chk(frames, "frames", torch.int32)
+    assert frames.dim() == 1 and frames.is_contiguous()
+    n, k, s, dev = frames.numel(), int(k), store, frames.device
+    F = max(int(s["n_frames"]), 1)
+    chunk = max(1, min(max(n, 1), COVIS_WORKSPACE_BYTES // (4 * F)))
+    if workspace is None:
+        workspace = torch.empty(chunk * F, device=dev, dtype=torch.int32)
+    _chk(workspace, "workspace", torch.int32)
+    assert workspace.is_contiguous() and workspace.numel() >= chunk * F
+    best_f, best_c = torch.empty(max(n, 1), max(k, 1), device=dev, dtype=torch.int32), torch.empty(max(n, 1), max(k, 1), device=dev, dtype=torch.int32)
+    n_found = torch.empty(max(n, 1), device=dev, dtype=torch.int32)
+    for a in range(0, max(n, 1), chunk):
+        m = min(chunk, n - a)
+        _lib.check(L.pram_covis_topk(_p(frames[a:]) if n else _p(n_found), m, _p(s["valid_off"]), _p(s["valid_rows"]), _p(s["point3D_ids"]), int(s["n_rows"]),
+                                     int(s["n_valid"]), _p(s["pt_ids"]), _p(s["pt_off"]), _p(s["pt_frames"]), int(s["n_points"]), int(s["n_pt_entries"]),
+                                     int(s["n_frames"]), k, int(bool(include_self)), _p(workspace), _p(best_f[a:]), _p(best_c[a:]), _p(n_found[a:]), _st()),
+                   "pram_covis_topk")
+    return best_f[:n], best_c[:n], n_found[:n]
