@@ -1199,6 +1199,64 @@ int pram_tri_split(const int* trk_off, const int* trk_row, int n_tracks, int n_e
                    const unsigned char* entry_keep, const int* edges, int n_edges, int n_rows, int first, unsigned char* state,
                    int* edges_out, int* n_live, void* stream);
 
+/* ---- two-view geometry without poses (csrc/twoview.hip; pram_amd/localization/twoview.py drives these) ------------------------
+ * The other branch of the reference's triangulation.main (estimation_and_geometric_verification, pycolmap.verify_matches): per
+ * pair an essential matrix by RANSAC over five-point samples, the mask of the matches that agree with it and the relative pose it
+ * decomposes to.  NOT COLMAP's estimator: a fixed trial budget, the calibrated case only, no local optimisation (DESIGN.md 4.24
+ * lists the deviations).  float64; profiles/twoview_timing.md has the time of every stage.
+ *
+ * The entries read the triangulation's frame table and match layout: norm [n_rows][2] is pram_tri_normalize with the offset 0.5,
+ * frame_off [n_frames + 1], pairs [n_pairs][2] frame indices, match_off [n_pairs + 1] and matches [n_matches][2] the matches as
+ * CSR, cam_model [n_frames] / cam_params [n_frames][PRAM_POSE_CAM_PARAMS] the cameras (a model id outside PRAM_CAM_* reads as
+ * SIMPLE_PINHOLE; pram_tri_normalize has refused it before).  Index rules, in every entry: match_off is clamped into
+ * [0, n_matches]; a pair naming a frame outside [0, n_frames) has no usable match; a match with an index outside its frame is
+ * never dereferenced, is no inlier of anything, and a sample that draws it yields no hypothesis.  E is row-major with
+ * x1^T E x0 = 0 for x0 = (u0, v0, 1) of frame 0 and x1 of frame 1.  Every entry refuses (PRAM_E_ARG) a null or misaligned pointer
+ * (float64 8 bytes, int32 4), n_pairs > 65535, trials outside [1, 2^20] and a negative size; none waits for the stream. */
+#define PRAM_TWOVIEW_MAX_SOL 10        /* real solutions of a five-point sample */
+
+/* One lane per (pair, trial), the trial's working set in LDS ([element][lane], 141312 bytes of dynamic LDS per wave).  Sampler:
+ * key = sm64(sm64(seed) ^ ((first_pair + p) << 32 | trial)) with splitmix64's output function sm64 (pram_pose_hypotheses');
+ * pick k = 0 .. 4 is mulhi64(sm64(key + k), n - k), n the pair's clamped match count, then stepped over the earlier picks in
+ * ascending order (+1 for every earlier pick <= it): five distinct indices below n.  first_pair is the position of pairs[0] among
+ * all processed pairs, so a batch cut into chunks draws what the whole batch draws.  Solver: the null space of the 5 x 9
+ * epipolar system by Gauss-Jordan with complete pivoting (rank-deficient when a pivot falls below 1e-10 of the first), the ten
+ * cubic constraints det E = 0 and 2 E E^T E - tr(E E^T) E = 0 as a 10 x 20 matrix in Nister's column order, Gauss-Jordan with
+ * partial pivoting, the degree-10 polynomial det B(z) of the hidden variable z, its real roots in ascending order by 48
+ * bisection steps each on the Sturm count inside the Cauchy bound, 4 Newton steps on det B(z), (x, y) from the null vector of
+ * B(z).  A root is kept when E is finite and |det E| and every entry of 2 E E^T E - tr(E E^T) E are <= 1e-6 at |E|_F = 1.
+ * E [n_pairs][trials][PRAM_TWOVIEW_MAX_SOL][9]: Frobenius-normalised, the kept roots first, zeros behind; n_sol
+ * [n_pairs][trials]; fives [n_pairs][trials][5] (may be NULL): the sampled match indices, -1 when n < 5.  n_sol = 0 for n < 5, a
+ * sample naming an unusable match, a rank-deficient sample (duplicates) and a chain that is not finite. */
+int pram_twoview_hypotheses(const double* norm, const int* frame_off, const int* pairs, const int* match_off, const int* matches,
+                            int n_frames, int n_pairs, int n_matches, int first_pair, int trials, unsigned long long seed,
+                            double* E, int* n_sol, int* fives, void* stream);
+
+/* Every slot against every match of its pair: the squared Sampson error on the normalised plane, an inlier when it is <=
+ * (max_error * 0.5 * (1 / f0 + 1 / f1))^2 with f the mean focal length of each frame's camera; no cheirality.  h_inliers
+ * [n_pairs][trials][PRAM_TWOVIEW_MAX_SOL] (-1 for a slot >= n_sol), h_resid (same shape): the sum of the inliers' errors; best
+ * [n_pairs]: the slot with most inliers, then the smaller sum, then the smaller index (-1: no slot).  The matches go through LDS
+ * in chunks of 768 whatever their number; sums are per lane in ascending order and combined by the wave's butterfly. */
+int pram_twoview_score(const double* norm, const int* frame_off, const int* pairs, const int* match_off, const int* matches,
+                       const int* cam_model, const double* cam_params, int n_frames, int n_pairs, int n_matches, const double* E,
+                       const int* n_sol, int trials, double max_error, int* h_inliers, double* h_resid, int* best, void* stream);
+
+/* One workgroup per pair.  The best E is decomposed into its four (R, t) (t: the largest cross product of two columns; R =
+ * cof(E') -+ [t]x E', E' = sqrt(2) E, re-orthonormalised to det R = +1), the one with most inliers at positive depth in both
+ * frames is taken (lowest index on a tie), refined by refine_iters Levenberg-Marquardt iterations over 5 parameters (a left
+ * axis-angle increment on R, two tangent directions of the unit sphere for t; Cauchy weights of scale 1 pixel on the signed
+ * Sampson distance; pram_pose_refine's damping and acceptance rule), inliers marked again, refined again; a refined model with
+ * fewer inliers than the hypothesis had is dropped for the hypothesis.  success [n_pairs]: the pair has 5 matches at least, some
+ * trial gave a solution and the final support is >= max(min_num_inliers, min_inlier_ratio * count).  E_out [n_pairs][9]
+ * (Frobenius norm 1), qvec [n_pairs][4] (w, x, y, z; w >= 0), tvec [n_pairs][3] (unit; frame 1 from frame 0), num_inliers,
+ * num_front [n_pairs] (the inliers at positive depth in both frames); keep / kept / edges / count: pram_tri_verify's outputs
+ * under the final E.  A failed pair has zeros everywhere, keeps no match and has count 0. */
+int pram_twoview_finish(const double* norm, const int* frame_off, const int* pairs, const int* match_off, const int* matches,
+                        const int* cam_model, const double* cam_params, int n_frames, int n_pairs, int n_matches, const double* E,
+                        const int* h_inliers, const int* best, int trials, double max_error, double min_inlier_ratio,
+                        int min_num_inliers, int refine_iters, double* E_out, double* qvec, double* tvec, int* num_inliers,
+                        int* num_front, int* success, unsigned char* keep, int* kept, int* edges, int* count, void* stream);
+
 /* ---- statistical outlier removal of a map's points (csrc/knn.hip; pram_amd/localization/outliers.py drives these) -------------
  * What RecMap.remove_statics_outlier (recmap.py:43-61) takes from Open3D's PointCloud::RemoveStatisticalOutliers, written from
  * knowledge of its source and NOT pinned to it (Open3D was never run beside this).  x [n][3] float64.

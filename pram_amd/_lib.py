@@ -147,6 +147,9 @@ _SIGS = {
     "pram_tri_adjacency": (I, [P, I, P, I, I, P, SZ, P, P, P, P]),
     "pram_tri_support": (I, [P, P, P, P, P, P, I, P, P, P, I, I, C.c_double, C.c_double, I, P, P, P]),
     "pram_tri_split": (I, [P, P, I, I, P, P, P, I, I, I, P, P, P, P]),
+    "pram_twoview_hypotheses": (I, [P, P, P, P, P, I, I, I, I, I, C.c_ulonglong, P, P, P, P]),
+    "pram_twoview_score": (I, [P, P, P, P, P, P, P, I, I, I, P, P, I, C.c_double, P, P, P, P]),
+    "pram_twoview_finish": (I, [P, P, P, P, P, P, P, I, I, I, P, P, P, I, C.c_double, C.c_double, I, I, P, P, P, P, P, P, P, P, P, P, P]),
     "pram_knn_mean_distance": (I, [P, LL, I, P, P]),
     "pram_sor_workspace_bytes": (SZ, [LL]),
     "pram_sor_select": (I, [P, LL, C.c_double, P, SZ, P, P, P, P, P]),

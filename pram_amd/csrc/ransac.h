@@ -1,0 +1,97 @@
+// What the RANSAC stages share (pose.hip, twoview.hip): the ranking rule and the kernel that picks a pair's best slot by it, the
+// 6 x 6 damped Cholesky of the Levenberg-Marquardt step and the rotation-to-quaternion conversion.
+#pragma once
+#include "camera.h"
+
+// better(a, b): most inliers, then smaller residual sum, then smaller index
+__device__ __forceinline__ bool better(int ca, double ra, int ia, int cb, double rb, int ib) {
+    if (ca != cb) return ca > cb;
+    if (ra != rb) return ra < rb;
+    return ia < ib;
+}
+
+// one workgroup per pair: the best slot by the ranking rule (-1 if no slot holds a hypothesis)
+static __global__ __launch_bounds__(256) void ransac_pick_kernel(const int* __restrict__ h_inl, const double* __restrict__ h_res, int slots,
+                                                        int* __restrict__ best) {
+    __shared__ int sc[4], si[4];
+    __shared__ double sr[4];
+    const int p = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int* hc = h_inl + (size_t)p * slots;
+    const double* hr = h_res + (size_t)p * slots;
+    int bc = -1, bi = 0x7fffffff;
+    double br = 0.0;
+    for (int i = tid; i < slots; i += 256) {
+        const int c = hc[i];
+        const double r = hr[i];
+        if (c >= 0 && better(c, r, i, bc, br, bi)) { bc = c; br = r; bi = i; }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const int oc = __shfl_xor(bc, o, 64), oi = __shfl_xor(bi, o, 64);
+        const double orr = __shfl_xor(br, o, 64);
+        if (oc >= 0 && better(oc, orr, oi, bc, br, bi)) { bc = oc; br = orr; bi = oi; }
+    }
+    if (lane == 0) { sc[wave] = bc; sr[wave] = br; si[wave] = bi; }
+    __syncthreads();
+    if (tid == 0) {
+        for (int w = 1; w < 4; ++w)
+            if (sc[w] >= 0 && better(sc[w], sr[w], si[w], bc, br, bi)) { bc = sc[w]; br = sr[w]; bi = si[w]; }
+        best[p] = bc >= 0 ? bi : -1;
+    }
+}
+
+// (H + lam diag(H)) x = -g by Cholesky; false when a pivot is not positive or the step is not finite.  H: 21 upper-triangle values.
+static __device__ bool chol_solve6(const double* __restrict__ Hu, const double* __restrict__ g, double lam, double* x) {
+    double M[6][6], L[6][6];
+    int e = 0;
+    for (int a = 0; a < 6; ++a)
+        for (int c = a; c < 6; ++c) { M[a][c] = Hu[e]; M[c][a] = Hu[e]; ++e; }
+    for (int a = 0; a < 6; ++a) M[a][a] = M[a][a] + lam * M[a][a];
+    for (int i = 0; i < 6; ++i)
+        for (int k = 0; k <= i; ++k) {
+            double s = 0.0;
+            for (int j = 0; j < k; ++j) s += L[i][j] * L[k][j];
+            s = M[i][k] - s;
+            if (i == k) {
+                if (!(s > 0.0)) return false;
+                L[i][i] = sqrt(s);
+            } else {
+                L[i][k] = s / L[k][k];
+            }
+        }
+    double y[6];
+    for (int i = 0; i < 6; ++i) {
+        double s = 0.0;
+        for (int j = 0; j < i; ++j) s += L[i][j] * y[j];
+        y[i] = (-g[i] - s) / L[i][i];
+    }
+    bool okx = true;
+    for (int i = 5; i >= 0; --i) {
+        double s = 0.0;
+        for (int j = i + 1; j < 6; ++j) s += L[j][i] * x[j];
+        x[i] = (y[i] - s) / L[i][i];
+        okx = okx && fin(x[i]);
+    }
+    return okx;
+}
+
+static __device__ void rot_to_qvec(const double* __restrict__ R, double* __restrict__ qv) {
+    const double tr = R[0] + R[4] + R[8];
+    double q0, q1, q2, q3;
+    if (tr > 0.0) {
+        const double s = sqrt(tr + 1.0) * 2.0;
+        q0 = 0.25 * s; q1 = (R[7] - R[5]) / s; q2 = (R[2] - R[6]) / s; q3 = (R[3] - R[1]) / s;
+    } else if (R[0] > R[4] && R[0] > R[8]) {
+        const double s = sqrt(1.0 + R[0] - R[4] - R[8]) * 2.0;
+        q0 = (R[7] - R[5]) / s; q1 = 0.25 * s; q2 = (R[1] + R[3]) / s; q3 = (R[2] + R[6]) / s;
+    } else if (R[4] > R[8]) {
+        const double s = sqrt(1.0 + R[4] - R[0] - R[8]) * 2.0;
+        q0 = (R[2] - R[6]) / s; q1 = (R[1] + R[3]) / s; q2 = 0.25 * s; q3 = (R[5] + R[7]) / s;
+    } else {
+        const double s = sqrt(1.0 + R[8] - R[0] - R[4]) * 2.0;
+        q0 = (R[3] - R[1]) / s; q1 = (R[2] + R[6]) / s; q2 = (R[5] + R[7]) / s; q3 = 0.25 * s;
+    }
+    const double nrm = sqrt(q0 * q0 + q1 * q1 + q2 * q2 + q3 * q3);
+    const double sg = q0 / nrm < 0.0 ? -1.0 : 1.0;
+    qv[0] = sg * (q0 / nrm); qv[1] = sg * (q1 / nrm); qv[2] = sg * (q2 / nrm); qv[3] = sg * (q3 / nrm);
+}

@@ -42,7 +42,9 @@ Where this differs from the reference, on purpose:
   * pixel offsets: verification reads the keypoints as stored (offset 0), triangulation adds 0.5, as in the reference
     (geometric_verification passes get_keypoints' array, import_features adds 0.5 for COLMAP).  The inconsistency is kept.
   * out-of-range indices: a match with a keypoint index outside its frame is dropped, where the reference would raise.
-  * estimation_and_geometric_verification, the unknown-pose RANSAC of pycolmap.verify_matches, is not built.
+  * estimation_and_geometric_verification, the unknown-pose RANSAC of pycolmap.verify_matches, is localization/twoview.py
+    (DESIGN.md 4.24): ``estimate_two_view_geometries=True`` of :func:`triangulate_map` puts it in the place of stage 2.  It is
+    not COLMAP's estimator; that module's docstring lists the deviations.
   * the COLMAP database and model files are not written.
   * of a frame's several inliers in one track the one with the smallest error stays (the lowest row on a tie); COLMAP keeps
     whichever observation its search met first."""
@@ -61,6 +63,7 @@ TRI_DEFAULTS = dict(trials=128, seed=0, min_tri_angle=1.5, max_reproj_error=4.0)
 DEFAULTS = {**VERIFY_DEFAULTS, **TRI_DEFAULTS}
 SUPPORT_DEFAULTS = dict(min_support=0)      # stage 2b's confirming third views per match; 0: the stage does not run
 SPLIT_DEFAULTS = dict(split_rounds=0)      # further rounds over the entries that fell out as outliers; 0: none
+TWOVIEW_MAP_DEFAULTS = dict(estimate_two_view_geometries=False, twoview=None)      # stage 2 by twoview.py, and its parameters
 CC_GROUP = 8      # rounds of the components enqueued per look at the done flag
 
 
@@ -366,10 +369,23 @@ def triangulate_map(frames: Sequence[dict], cameras: Sequence, poses, pairs, mat
     accepted tracks (the module docstring; :func:`split_edges` is the step between two rounds).  Round 0's points come first, so
     the first of them and their tracks are what ``split_rounds=0`` gives, bit for bit; then round 1's accepted tracks in track
     order, and so on.  The dict also holds ``point_round`` int32 [P] and ``split``: int64 arrays over the further rounds that were
-    begun, ``live_edges`` (the edges between FREE rows; a round that finds none ends the rounds), ``tracks`` and ``points``."""
-    p = _int_param(_int_param(_params("triangulate_map", params, {**DEFAULTS, **SUPPORT_DEFAULTS, **SPLIT_DEFAULTS}), "min_support"), "split_rounds")
+    begun, ``live_edges`` (the edges between FREE rows; a round that finds none ends the rounds), ``tracks`` and ``points``.
+    params also TWOVIEW_MAP_DEFAULTS.  With ``estimate_two_view_geometries=True`` (the reference's flag of the same name) stage 2
+    is twoview.estimate_two_view's estimator instead of the test against the known poses: a pair's matches are kept when they
+    agree with an essential matrix estimated from the matches themselves, so a pose that is off by more than ``max_error`` pixels
+    no longer costs the pair its matches; the poses are still what stage 4 triangulates with.  ``twoview``: a dict of
+    twoview.TWOVIEW_DEFAULTS' parameters (``max_error`` defaults to this call's).  The stages after it run on its edges as they
+    are, and the dict also holds ``two_view``: ``E``, ``qvec``, ``tvec``, ``num_inliers``, ``num_front`` and ``success`` per
+    processed pair, and ``keep``, per pair the mask over its matches."""
+    p = _params("triangulate_map", params, {**DEFAULTS, **SUPPORT_DEFAULTS, **SPLIT_DEFAULTS, **TWOVIEW_MAP_DEFAULTS})
+    p = _int_param(_int_param(p, "min_support"), "split_rounds")
+    if p["estimate_two_view_geometries"]:
+        from pram_amd.localization import twoview
+        tv = twoview._twoview_params("triangulate_map: twoview", {"max_error": p["max_error"], **(p["twoview"] or {})})
+    elif p["twoview"] is not None:
+        raise ValueError("twoview: parameters of estimate_two_view_geometries=True")
     table = frame_table(frames, cameras, poses, device)
-    v = _verify(table, pairs, matches, p["max_error"])
+    v = twoview._estimate(table, pairs, matches, tv) if p["estimate_two_view_geometries"] else _verify(table, pairs, matches, p["max_error"])
     sup = _support(table, v["edges"], v["n_matches"], p) if p["min_support"] > 0 else None
     edges = v["edges"] if sup is None else sup["edges"]
     t = _tracks(table, edges, v["n_matches"])
@@ -404,6 +420,9 @@ def triangulate_map(frames: Sequence[dict], cameras: Sequence, poses, pairs, mat
         res.update(point_round=point_round, split={"live_edges": np.array(live, dtype=np.int64), "tracks": np.array(n_tracks, dtype=np.int64),
                                                    "points": np.array(n_points, dtype=np.int64)})
     res.update(pair_index=v["pair_index"], inlier_ratio=_inlier_ratio(v["count"][:Pn].cpu().numpy(), v["match_off"]))
+    if p["estimate_two_view_geometries"]:
+        keep = v["keep"][:v["n_matches"]].cpu().numpy().astype(bool)
+        res["two_view"] = {**twoview._pair_results(v), "keep": [keep[a:b] for a, b in zip(v["match_off"][:-1], v["match_off"][1:])]}
     if sup is not None:
         M, m_off = v["n_matches"], v["match_off"]
         support = np.where(v["keep"][:M].cpu().numpy().astype(bool), sup["support"][:M].cpu().numpy(), -1).astype(np.int32)

@@ -2443,6 +2443,105 @@ def tri_split(trk_off: torch.Tensor, trk_row: torch.Tensor, n_tracks: int, n_ent
     return out
 
 
+# ---- two-view geometry without poses (csrc/twoview.hip; pram_amd/localization/twoview.py drives these) ------------------------
+TWOVIEW_MAX_SOL = 10      # PRAM_TWOVIEW_MAX_SOL
+TWOVIEW_TRIAL_BYTES = TWOVIEW_MAX_SOL * (9 * 8 + 4 + 8) + 4      # hypotheses, counts, residual sums and n_sol of one trial
+
+
+def _twoview_views(norm, frame_off, pairs, match_off, matches, n_frames: int, n_pairs: int, n_matches: int):
+    """The five tensors every two-view entry reads of the frame table and the match CSR, and their sizes."""
+    _tri_chk(((norm, "norm", torch.float64), (frame_off, "frame_off", torch.int32), (pairs, "pairs", torch.int32),
+              (match_off, "match_off", torch.int32), (matches, "matches", torch.int32)))
+    assert frame_off.numel() >= n_frames + 1 and pairs.numel() >= 2 * n_pairs and match_off.numel() >= n_pairs + 1 and matches.numel() >= 2 * n_matches
+
+
+def _twoview_cams(cam_model, cam_params, n_frames: int):
+    _tri_chk(((cam_model, "cam_model", torch.int32), (cam_params, "cam_params", torch.float64)))
+    assert cam_model.numel() >= n_frames and cam_params.numel() >= POSE_CAM_PARAMS * n_frames
+
+
+def twoview_hypotheses(norm: torch.Tensor, frame_off: torch.Tensor, pairs: torch.Tensor, match_off: torch.Tensor, matches: torch.Tensor,
+                       n_frames: int, n_pairs: int, n_matches: int, first_pair: int = 0, trials: int = 1024, seed: int = 0,
+                       return_fives: bool = False) -> dict:
+    """norm: tri_normalize with offset 0.5; pairs int32 [Pn, 2]; the matches as CSR (match_off int32 [Pn + 1], matches int32 [M, 2])
+    -> E float64 [Pn, trials, TWOVIEW_MAX_SOL, 9] (the kept roots of every five-point sample first, zeros behind), n_sol int32
+    [Pn, trials] and, with return_fives, fives int32 [Pn, trials, 5].  first_pair: the position of pairs[0] among all processed
+    pairs (the sampler's key)."""
+    L = _lib.load()
+    F, Pn, M, T = int(n_frames), int(n_pairs), int(n_matches), int(trials)
+    _twoview_views(norm, frame_off, pairs, match_off, matches, F, Pn, M)
+    dev = norm.device
+    out = {"E": torch.empty(max(Pn, 1), T, TWOVIEW_MAX_SOL, 9, device=dev, dtype=torch.float64),
+           "n_sol": torch.empty(max(Pn, 1), T, device=dev, dtype=torch.int32)}
+    if return_fives:
+        out["fives"] = torch.empty(max(Pn, 1), T, 5, device=dev, dtype=torch.int32)
+    _lib.check(L.pram_twoview_hypotheses(_p(norm), _p(frame_off), _p(pairs), _p(match_off), _p(matches), F, Pn, M, int(first_pair), T,
+                                         int(seed) & 0xFFFFFFFFFFFFFFFF, _p(out["E"]), _p(out["n_sol"]), _p(out["fives"]) if return_fives else None,
+                                         _st()), "pram_twoview_hypotheses")
+    return out
+
+
+def twoview_score(norm: torch.Tensor, frame_off: torch.Tensor, pairs: torch.Tensor, match_off: torch.Tensor, matches: torch.Tensor,
+                  cam_model: torch.Tensor, cam_params: torch.Tensor, n_frames: int, n_pairs: int, n_matches: int, E: torch.Tensor,
+                  n_sol: torch.Tensor, max_error: float = 4.0) -> dict:
+    """E float64 [Pn, trials, TWOVIEW_MAX_SOL, 9] and n_sol int32 [Pn, trials] (twoview_hypotheses') -> h_inliers int32
+    [Pn, trials, TWOVIEW_MAX_SOL] (-1 for an empty slot), h_resid float64 (same shape), best int32 [Pn] (-1: no slot)."""
+    L = _lib.load()
+    F, Pn, M = int(n_frames), int(n_pairs), int(n_matches)
+    _twoview_views(norm, frame_off, pairs, match_off, matches, F, Pn, M)
+    _twoview_cams(cam_model, cam_params, F)
+    _tri_chk(((E, "E", torch.float64), (n_sol, "n_sol", torch.int32)))
+    assert E.dim() == 4 and tuple(E.shape[2:]) == (TWOVIEW_MAX_SOL, 9) and E.shape[0] >= Pn and tuple(n_sol.shape) == tuple(E.shape[:2])
+    T, dev = int(E.shape[1]), norm.device
+    out = {"h_inliers": torch.empty(max(Pn, 1), T, TWOVIEW_MAX_SOL, device=dev, dtype=torch.int32),
+           "h_resid": torch.empty(max(Pn, 1), T, TWOVIEW_MAX_SOL, device=dev, dtype=torch.float64),
+           "best": torch.empty(max(Pn, 1), device=dev, dtype=torch.int32)}
+    _lib.check(L.pram_twoview_score(_p(norm), _p(frame_off), _p(pairs), _p(match_off), _p(matches), _p(cam_model), _p(cam_params), F, Pn, M,
+                                    _p(E), _p(n_sol), T, float(max_error), _p(out["h_inliers"]), _p(out["h_resid"]), _p(out["best"]), _st()),
+               "pram_twoview_score")
+    return out
+
+
+_TWOVIEW_PAIR_OUT = (("E", torch.float64, (9,)), ("qvec", torch.float64, (4,)), ("tvec", torch.float64, (3,)), ("num_inliers", torch.int32, ()),
+                     ("num_front", torch.int32, ()), ("success", torch.int32, ()), ("count", torch.int32, ()))
+_TWOVIEW_MATCH_OUT = (("keep", torch.uint8, ()), ("kept", torch.int32, (2,)), ("edges", torch.int32, (2,)))
+
+
+def twoview_outputs(n_pairs: int, n_matches: int, device) -> dict:
+    """What twoview_finish writes, allocated: E float64 [Pn, 9], qvec [Pn, 4], tvec [Pn, 3], num_inliers / num_front / success /
+    count int32 [Pn], and tri_verify's keep uint8 [M], kept int32 [M, 2], edges int32 [M, 2]."""
+    out = {k: torch.empty(max(int(n_pairs), 1), *sh, device=device, dtype=dt) for k, dt, sh in _TWOVIEW_PAIR_OUT}
+    out.update({k: torch.empty(max(int(n_matches), 1), *sh, device=device, dtype=dt) for k, dt, sh in _TWOVIEW_MATCH_OUT})
+    return out
+
+
+def twoview_finish(norm: torch.Tensor, frame_off: torch.Tensor, pairs: torch.Tensor, match_off: torch.Tensor, matches: torch.Tensor,
+                   cam_model: torch.Tensor, cam_params: torch.Tensor, n_frames: int, n_pairs: int, n_matches: int, E: torch.Tensor,
+                   h_inliers: torch.Tensor, best: torch.Tensor, max_error: float = 4.0, min_inlier_ratio: float = 0.1,
+                   min_num_inliers: int = 15, refine_iters: int = 20, out: Optional[dict] = None) -> dict:
+    """The best slot of every pair (twoview_score's) decomposed, refined and scored again -> twoview_outputs' dict.  ``out``: that
+    dict with the per-pair tensors cut to this call's pairs and the per-match tensors whole (match_off indexes them), so that a
+    caller walks a long pair list in chunks; None allocates it."""
+    L = _lib.load()
+    F, Pn, M = int(n_frames), int(n_pairs), int(n_matches)
+    _twoview_views(norm, frame_off, pairs, match_off, matches, F, Pn, M)
+    _twoview_cams(cam_model, cam_params, F)
+    _tri_chk(((E, "E", torch.float64), (h_inliers, "h_inliers", torch.int32), (best, "best", torch.int32)))
+    assert E.dim() == 4 and tuple(E.shape[2:]) == (TWOVIEW_MAX_SOL, 9) and E.shape[0] >= Pn and tuple(h_inliers.shape) == tuple(E.shape[:3])
+    assert best.numel() >= Pn
+    if out is None:
+        out = twoview_outputs(Pn, M, norm.device)
+    _tri_chk(tuple((out[k], k, dt) for k, dt, _ in _TWOVIEW_PAIR_OUT + _TWOVIEW_MATCH_OUT))
+    assert all(out[k].numel() >= Pn * (sh[0] if sh else 1) for k, _, sh in _TWOVIEW_PAIR_OUT)
+    assert all(out[k].numel() >= M * (sh[0] if sh else 1) for k, _, sh in _TWOVIEW_MATCH_OUT)
+    _lib.check(L.pram_twoview_finish(_p(norm), _p(frame_off), _p(pairs), _p(match_off), _p(matches), _p(cam_model), _p(cam_params), F, Pn, M,
+                                     _p(E), _p(h_inliers), _p(best), int(E.shape[1]), float(max_error), float(min_inlier_ratio),
+                                     int(min_num_inliers), int(refine_iters), _p(out["E"]), _p(out["qvec"]), _p(out["tvec"]),
+                                     _p(out["num_inliers"]), _p(out["num_front"]), _p(out["success"]), _p(out["keep"]), _p(out["kept"]),
+                                     _p(out["edges"]), _p(out["count"]), _st()), "pram_twoview_finish")
+    return out
+
+
 # ---- statistical outlier removal (csrc/knn.hip; pram_amd/localization/outliers.py drives these) -------------------------------
 KNN_TILE, KNN_MAX_K, SOR_BLOCK = 1024, 32, 1024      # include/pram_hip.h
 SOR_MEAN, SOR_STD, SOR_THRESHOLD, SOR_NV = 0, 1, 2, 3      # entries of the statistics
