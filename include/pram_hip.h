@@ -1340,6 +1340,77 @@ int pram_covis_topk(const int* frames, int n, const int* valid_off, const int* v
                     int n_frames, int k, int include_self, int* hist, int* best_frames, int* best_counts, int* n_found,
                     void* stream);
 
+/* ---- bundle adjustment (csrc/bundle.hip): a map's poses refined with its points --------------------------------------------
+ * Levenberg-Marquardt over the frames' poses (cam_from_world, the tangent of pram_pose_refine: R <- exp([w]x) R, t <- t + d) and
+ * the points (additive), intrinsics constant, under the robust cost of pram_pose_refine at scale loss_scale: per observation
+ * s = |r|^2 / loss_scale^2, cost log1p(s), weight 1 / (1 + s); the residual goes through the full camera model against keypoint
+ * + 0.5.  The reduced camera system of the Schur complement is solved by conjugate gradients with the block-Jacobi preconditioner,
+ * matrix-free.  Damping is pram_pose_refine's, H + lam diag(H), on the point blocks and on the frame blocks.  NOT Ceres / COLMAP's
+ * bundle adjuster: DESIGN.md 4.25 lists the deviations and every fixed summation order.  float64; no floating-point atomics.
+ *
+ * The tables.  An observation is a row (keypoint) with a point: obs_row / obs_frame / obs_point [n_obs] in ascending row, so that
+ * frame f's observations are frm_off[f] .. frm_off[f + 1] (frm_off [n_frames + 1]); pt_off [n_points + 1] / pt_obs [n_obs] is the
+ * CSR of observation indices per point, ascending.  frozen [n_frames]: six bits per frame, bit a freezes tangent parameter a
+ * (0..2 rotation, 3..5 translation): its Jacobian column is zero and its diagonal 1, so its step is exactly 0.  A frame without
+ * observations is frozen.  table [n_frames][PRAM_TRI_FRAME_COLS] is pram_tri_frames' and xyz [n_points][3] the points.
+ * pram_ba_begin checks every index of the tables on the device before any kernel reads through it: a table that fails ends the
+ * run with PRAM_BA_REASON_TABLES and nothing else is written.
+ *
+ * The state record lives in the workspace: float64 [PRAM_BA_STATE_F64] and int32 [PRAM_BA_STATE_I32 + 2 * max_iters]; behind the
+ * fixed words the CG iterations of every LM iteration, then its accept flag.  Every kernel reads it; once `done` is set (or, for
+ * the CG kernels, the solve has stopped) the launches still enqueued return at once, so a caller enqueues LM iterations in groups
+ * and reads PRAM_BA_SI_DONE once per group.  pram_ba_layout gives the byte offsets of the workspace's arrays
+ * [PRAM_BA_ARRAYS + 1] (the last is the total) in the order of bundle.hip's enum: tests and the timing tool read the stages there.
+ *
+ * pram_ba_begin fills `context` [PRAM_BA_CONTEXT_BYTES] (HOST memory: the pointers and sizes of the problem), copies table and
+ * xyz into the workspace and computes the initial cost; the problem's arrays and the workspace must outlive the context.
+ * pram_ba_iterate enqueues n_iters LM iterations of at most cg_iters CG iterations each (a CG solve stops at
+ * |r| <= cg_tol |b|); stages: PRAM_BA_STAGE_ALL, or single stages for tests and timing.  A step is accepted when the cost falls
+ * (a NaN cost rejects), lam x 0.1 on accept (not below 1e-15), x 10 on reject; the run ends at max_iters iterations or at an
+ * accepted relative decrease of the cost below ftol.  A point whose damped block has a pivot that is not positive, or fewer than
+ * two observations of weight above 0, stays where it is.  An observation with depth <= 1e-12 or a residual that is not finite
+ * has weight 0.  pram_ba_finish writes the poses (a frame that never moved keeps qvec_in / tvec_in bit for bit), the points and
+ * the filter: obs_keep [n_obs] (depth > 0 and reprojection error <= max_reproj_error), obs_error [n_obs] (pixels), pt_keep
+ * [n_points] (two kept observations at least and a largest angle between the rays of two of them of min_tri_angle radians or
+ * more), pt_error [n_points] (the mean error of the kept), pt_angle [n_points] (that largest angle, -1 without a pair), pt_kept
+ * [n_points], counts [2] = (observations of weight 0 at the final state, observations not kept).  Limits: n_frames <= 2^24,
+ * n_points <= 2^28, n_obs <= 2^26, max_iters <= 4096, cg_iters <= 65536; workspace 256-byte aligned. */
+#define PRAM_BA_OBS_DOUBLES 20         /* per observation: sqrt(w) J_c [2][6], sqrt(w) J_p [2][3], sqrt(w) r [2] */
+#define PRAM_BA_BLOCK 64               /* frames per block of the sums over frames */
+#define PRAM_BA_ARRAYS 25
+#define PRAM_BA_CONTEXT_BYTES 512
+#define PRAM_BA_STATE_F64 16
+#define PRAM_BA_STATE_I32 16
+#define PRAM_BA_SD_COST 0
+#define PRAM_BA_SD_LAM 2
+#define PRAM_BA_SD_COST0 9
+#define PRAM_BA_SI_DONE 0
+#define PRAM_BA_SI_REASON 1
+#define PRAM_BA_SI_LM_ITER 2
+#define PRAM_BA_SI_ACCEPTED 3
+#define PRAM_BA_SI_CG_FAIL 9
+#define PRAM_BA_REASON_MAX_ITERS 1
+#define PRAM_BA_REASON_FTOL 2
+#define PRAM_BA_REASON_TABLES 3
+#define PRAM_BA_STAGE_LINEARISE 1
+#define PRAM_BA_STAGE_BLOCKS 2
+#define PRAM_BA_STAGE_CG_INIT 4
+#define PRAM_BA_STAGE_CG 8
+#define PRAM_BA_STAGE_STEP 16
+#define PRAM_BA_STAGE_ALL 31
+
+size_t pram_ba_workspace_bytes(int n_frames, int n_points, int n_obs, int max_iters);
+int pram_ba_layout(int n_frames, int n_points, int n_obs, int max_iters, size_t* offsets);
+int pram_ba_begin(const float* keypoints, const int* cam_model, const double* cam_params, const int* cam_model_host,
+                  const double* table, const double* xyz, const int* obs_row, const int* obs_frame, const int* obs_point,
+                  const int* frm_off, const int* pt_off, const int* pt_obs, const int* frozen, int n_frames, int n_points,
+                  int n_obs, int n_rows, int max_iters, double loss_scale, double lam0, double cg_tol, double ftol,
+                  void* workspace, size_t workspace_bytes, void* context, void* stream);
+int pram_ba_iterate(const void* context, int n_iters, int cg_iters, int stages, void* stream);
+int pram_ba_finish(const void* context, const double* qvec_in, const double* tvec_in, double max_reproj_error, double min_tri_angle,
+                   double* qvec, double* tvec, double* xyz, unsigned char* obs_keep, double* obs_error, int* pt_keep,
+                   double* pt_error, double* pt_angle, int* pt_kept, int* counts, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

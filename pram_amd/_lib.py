@@ -150,6 +150,11 @@ _SIGS = {
     "pram_twoview_hypotheses": (I, [P, P, P, P, P, I, I, I, I, I, C.c_ulonglong, P, P, P, P]),
     "pram_twoview_score": (I, [P, P, P, P, P, P, P, I, I, I, P, P, I, C.c_double, P, P, P, P]),
     "pram_twoview_finish": (I, [P, P, P, P, P, P, P, I, I, I, P, P, P, I, C.c_double, C.c_double, I, I, P, P, P, P, P, P, P, P, P, P, P]),
+    "pram_ba_workspace_bytes": (SZ, [I, I, I, I]),
+    "pram_ba_layout": (I, [I, I, I, I, P]),
+    "pram_ba_begin": (I, [P, P, P, P, P, P, P, P, P, P, P, P, P, I, I, I, I, I, C.c_double, C.c_double, C.c_double, C.c_double, P, SZ, P, P]),
+    "pram_ba_iterate": (I, [P, I, I, I, P]),
+    "pram_ba_finish": (I, [P, P, P, C.c_double, C.c_double, P, P, P, P, P, P, P, P, P, P, P]),
     "pram_knn_mean_distance": (I, [P, LL, I, P, P]),
     "pram_sor_workspace_bytes": (SZ, [LL]),
     "pram_sor_select": (I, [P, LL, C.c_double, P, SZ, P, P, P, P, P]),

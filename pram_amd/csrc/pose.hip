@@ -276,8 +276,6 @@ __global__ __launch_bounds__(256) void pose_score_kernel(const double* __restric
 // ---------------------------------------------------------------- refine: LM on the inliers, re-score, refine, final state
 constexpr int LM_VALS = 28;      // cost, 21 of J^T W J (upper triangle, row-major), 6 of J^T W r
 
-struct Pose { double R[9], t[3]; };
-
 __device__ __forceinline__ bool row_inlier(const Pose& q, const double* __restrict__ pt, const double* __restrict__ X, double thr2) {
     const double xc = q.R[0] * X[0] + q.R[1] * X[1] + q.R[2] * X[2] + q.t[0];
     const double yc = q.R[3] * X[0] + q.R[4] * X[1] + q.R[5] * X[2] + q.t[1];
@@ -352,27 +350,6 @@ __device__ void lm_pass(const Pose& q, const Cam& cam, const float* __restrict__
     __syncthreads();
     if (tid < LM_VALS) tot[tid] = ((wred[0][tid] + wred[1][tid]) + wred[2][tid]) + wred[3][tid];
     __syncthreads();
-}
-
-// R <- exp([w]x) R, t <- t + d
-__device__ void pose_update(const Pose& q, const double* __restrict__ d, Pose& o) {
-    const double th = sqrt(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
-    double E[9];
-    if (th < 1e-12) {
-        E[0] = 1.0; E[1] = -d[2]; E[2] = d[1]; E[3] = d[2]; E[4] = 1.0; E[5] = -d[0]; E[6] = -d[1]; E[7] = d[0]; E[8] = 1.0;
-    } else {
-        const double kx = d[0] / th, ky = d[1] / th, kz = d[2] / th;
-        const double K[9] = {0.0, -kz, ky, kz, 0.0, -kx, -ky, kx, 0.0};
-        const double sn = sin(th), cs = 1.0 - cos(th);
-        for (int a = 0; a < 3; ++a)
-            for (int c = 0; c < 3; ++c) {
-                const double kk = K[a * 3] * K[c] + K[a * 3 + 1] * K[3 + c] + K[a * 3 + 2] * K[6 + c];
-                E[a * 3 + c] = (a == c ? 1.0 : 0.0) + sn * K[a * 3 + c] + cs * kk;
-            }
-    }
-    for (int a = 0; a < 3; ++a)
-        for (int c = 0; c < 3; ++c) o.R[a * 3 + c] = E[a * 3] * q.R[c] + E[a * 3 + 1] * q.R[3 + c] + E[a * 3 + 2] * q.R[6 + c];
-    o.t[0] = q.t[0] + d[3]; o.t[1] = q.t[1] + d[4]; o.t[2] = q.t[2] + d[5];
 }
 
 struct LmShared {

@@ -1,5 +1,6 @@
 // What the RANSAC stages share (pose.hip, twoview.hip): the ranking rule and the kernel that picks a pair's best slot by it, the
-// 6 x 6 damped Cholesky of the Levenberg-Marquardt step and the rotation-to-quaternion conversion.
+// 6 x 6 damped Cholesky of the Levenberg-Marquardt step and the rotation-to-quaternion conversion.  bundle.hip takes the
+// Cholesky, the conversion and the pose tangent (Pose, pose_update) from here.
 #pragma once
 #include "camera.h"
 
@@ -73,6 +74,29 @@ static __device__ bool chol_solve6(const double* __restrict__ Hu, const double* 
         okx = okx && fin(x[i]);
     }
     return okx;
+}
+
+// The pose tangent of the Levenberg-Marquardt steps (pose.hip, bundle.hip): R <- exp([w]x) R, t <- t + d
+struct Pose { double R[9], t[3]; };
+
+static __device__ void pose_update(const Pose& q, const double* __restrict__ d, Pose& o) {
+    const double th = sqrt(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
+    double E[9];
+    if (th < 1e-12) {
+        E[0] = 1.0; E[1] = -d[2]; E[2] = d[1]; E[3] = d[2]; E[4] = 1.0; E[5] = -d[0]; E[6] = -d[1]; E[7] = d[0]; E[8] = 1.0;
+    } else {
+        const double kx = d[0] / th, ky = d[1] / th, kz = d[2] / th;
+        const double K[9] = {0.0, -kz, ky, kz, 0.0, -kx, -ky, kx, 0.0};
+        const double sn = sin(th), cs = 1.0 - cos(th);
+        for (int a = 0; a < 3; ++a)
+            for (int c = 0; c < 3; ++c) {
+                const double kk = K[a * 3] * K[c] + K[a * 3 + 1] * K[3 + c] + K[a * 3 + 2] * K[6 + c];
+                E[a * 3 + c] = (a == c ? 1.0 : 0.0) + sn * K[a * 3 + c] + cs * kk;
+            }
+    }
+    for (int a = 0; a < 3; ++a)
+        for (int c = 0; c < 3; ++c) o.R[a * 3 + c] = E[a * 3] * q.R[c] + E[a * 3 + 1] * q.R[3 + c] + E[a * 3 + 2] * q.R[6 + c];
+    o.t[0] = q.t[0] + d[3]; o.t[1] = q.t[1] + d[4]; o.t[2] = q.t[2] + d[5];
 }
 
 static __device__ void rot_to_qvec(const double* __restrict__ R, double* __restrict__ qv) {

@@ -139,7 +139,18 @@ def remove_statistical_outliers(model: dict, device, nb_neighbors: int = 20, std
     if keep.shape != ids.shape:
         raise ValueError(f"model: {ids.shape[0]} point_ids, {keep.shape[0]} point3D_xyzs")
     info = _info(r, ids)
-    gone = set(info["removed_ids"].tolist())
+    out = restrict_model(model, keep)
+    out.update(info)
+    return out
+
+
+def restrict_model(model: dict, keep: np.ndarray) -> dict:
+    """model: triangulate_map's dict; keep: bool over ``point_ids`` -> the dict restricted to the kept points, as
+    :func:`remove_statistical_outliers` documents it (bundle.bundle_adjust cleans its result the same way).  The input is not
+    modified."""
+    ids = np.asarray(model["point_ids"])
+    removed = ids[~keep]
+    gone = set(removed.tolist())
     out = dict(model)
     out["point_ids"], out["point3D_xyzs"] = ids[keep], np.asarray(model["point3D_xyzs"])[keep]
     if "track_error" in model:
@@ -151,8 +162,7 @@ def remove_statistical_outliers(model: dict, device, nb_neighbors: int = 20, std
         frames = []
         for f in model["frames"]:
             pid = np.asarray(f["point3D_ids"])
-            lost = np.isin(pid, info["removed_ids"])
+            lost = np.isin(pid, removed)
             frames.append({**f, "point3D_ids": np.where(lost, -1, pid), "xyzs": np.where(lost[:, None], 0.0, np.asarray(f["xyzs"]))})
         out["frames"] = frames
-    out.update(info)
     return out

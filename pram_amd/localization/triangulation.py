@@ -32,7 +32,7 @@ frame_off, as StoreBase lays them out; a "row" is a keypoint's index in that tab
 Where this differs from the reference, on purpose:
   * not COLMAP's triangulator.  A track is a connected component of the verified matches, not a transitive correspondence
     search from a seed observation; there is no Merge, Complete or Retriangulate and no bundle adjustment beyond a point-only
-    refit (the poses are given and stay).  The trial budget is fixed (every pair of a track's entries up to ``trials`` of them,
+    refit (the poses are given and stay; localization/bundle.py refines them with the points afterwards).  The trial budget is fixed (every pair of a track's entries up to ``trials`` of them,
     else ``trials`` sampled pairs) instead of confidence-driven.  A component that wrong matches glued from two real points yields
     one of them at most: the hypothesis with most inliers wins and the other point's entries fall out as outliers.  Stage 2b
     removes most such matches before they join anything, where COLMAP accepts an observation only when it reprojects; a match

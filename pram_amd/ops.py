@@ -2658,3 +2658,90 @@ def covis_topk(frames: torch.Tensor, store, k: int, include_self: bool = False, 
                                      int(s["n_frames"]), k, int(bool(include_self)), _p(workspace), _p(best_f[a:]), _p(best_c[a:]), _p(n_found[a:]), _st()),
                    "pram_covis_topk")
     return best_f[:n], best_c[:n], n_found[:n]
+
+
+# ---- bundle adjustment (csrc/bundle.hip; pram_amd/localization/bundle.py drives these) ----------------------------------------
+BA_OBS_DOUBLES, BA_BLOCK, BA_CONTEXT_BYTES, BA_STATE_F64, BA_STATE_I32 = 20, 64, 512, 16, 16      # include/pram_hip.h
+BA_SD_COST, BA_SD_LAM, BA_SD_COST0 = 0, 2, 9      # words of the state's float64 part
+BA_SI_DONE, BA_SI_REASON, BA_SI_LM_ITER, BA_SI_ACCEPTED, BA_SI_CG_FAIL = 0, 1, 2, 3, 9      # and of its int32 part
+BA_REASONS = {0: "running", 1: "max_iters", 2: "ftol", 3: "tables"}      # PRAM_BA_REASON_*
+BA_STAGE_LINEARISE, BA_STAGE_BLOCKS, BA_STAGE_CG_INIT, BA_STAGE_CG, BA_STAGE_STEP, BA_STAGE_ALL = 1, 2, 4, 8, 16, 31
+# the workspace's arrays in bundle.hip's order: name, dtype, columns (0: the count comes with the sizes)
+BA_ARRAYS = (("table", torch.float64, "F", 16), ("table_cand", torch.float64, "F", 16), ("xyz", torch.float64, "P", 3), ("xyz_cand", torch.float64, "P", 3),
+             ("jac", torch.float64, "O", 20), ("v_inv", torch.float64, "P", 6), ("g_p", torch.float64, "P", 3), ("y_p", torch.float64, "P", 3),
+             ("s_block", torch.float64, "F", 21), ("diag_u", torch.float64, "F", 6), ("b", torch.float64, "F", 6), ("cg_x", torch.float64, "F", 6),
+             ("cg_r", torch.float64, "F", 6), ("cg_z", torch.float64, "F", 6), ("cg_p", torch.float64, "F", 6), ("cg_q", torch.float64, "F", 6),
+             ("frame_dot", torch.float64, "F2", 1), ("frame_cost", torch.float64, "F", 1), ("partials", torch.float64, "B2", 1),
+             ("state_f64", torch.float64, "SD", 1), ("state_i32", torch.int32, "SI", 1), ("point_ok", torch.int32, "P", 1),
+             ("moved", torch.int32, "F", 1), ("frozen", torch.int32, "F", 1), ("obs_ok", torch.uint8, "O", 1))
+
+
+def ba_begin(keypoints: torch.Tensor, cam_model: torch.Tensor, cam_params: torch.Tensor, cam_model_host, table: torch.Tensor, xyz: torch.Tensor,
+             obs_row: torch.Tensor, obs_frame: torch.Tensor, obs_point: torch.Tensor, frm_off: torch.Tensor, pt_off: torch.Tensor,
+             pt_obs: torch.Tensor, frozen: torch.Tensor, n_points: int, n_obs: int, n_rows: int, max_iters: int, loss_scale: float = 1.0,
+             lam0: float = 1e-3, cg_tol: float = 1e-2, ftol: float = 1e-6) -> dict:
+    """The problem of pram_ba_begin (include/pram_hip.h has the tables) -> a dict that holds the context, the workspace, the
+    tensors the context points to (so that they outlive it) and ``views``: the workspace's arrays by BA_ARRAYS' names.  The initial
+    cost is enqueued; nothing is read back."""
+    import ctypes
+    L = _lib.load()
+    F, Pn, O, n, K = len(cam_model_host), int(n_points), int(n_obs), int(n_rows), int(max_iters)
+    i32 = (("cam_model", cam_model), ("obs_row", obs_row), ("obs_frame", obs_frame), ("obs_point", obs_point), ("frm_off", frm_off),
+           ("pt_off", pt_off), ("pt_obs", pt_obs), ("frozen", frozen))
+    _tri_chk(((keypoints, "keypoints", torch.float32), (cam_params, "cam_params", torch.float64), (table, "table", torch.float64),
+              (xyz, "xyz", torch.float64)) + tuple((t, nm, torch.int32) for nm, t in i32))
+    if F < 1 or Pn < 1 or O < 1 or n < 1:
+        raise _lib.PramHipError("ba_begin: needs one frame, one point, one observation and one keypoint at least")
+    assert keypoints.numel() >= 2 * n and cam_model.numel() >= F and cam_params.numel() >= POSE_CAM_PARAMS * F and table.numel() >= TRI_FRAME_COLS * F
+    assert xyz.numel() >= 3 * Pn and min(obs_row.numel(), obs_frame.numel(), obs_point.numel(), pt_obs.numel()) >= O
+    assert frm_off.numel() >= F + 1 and pt_off.numel() >= Pn + 1 and frozen.numel() >= F
+    need = int(L.pram_ba_workspace_bytes(F, Pn, O, K))
+    if need == 0:
+        raise _lib.PramHipError("pram_ba_begin: sizes beyond 2^24 frames, 2^28 points, 2^26 observations or 4096 iterations")
+    dev = keypoints.device
+    workspace = torch.empty(need, device=dev, dtype=torch.uint8)
+    offsets = (ctypes.c_size_t * (len(BA_ARRAYS) + 1))()
+    _lib.check(L.pram_ba_layout(F, Pn, O, K, ctypes.addressof(offsets)), "pram_ba_layout")
+    count = {"F": F, "P": Pn, "O": O, "F2": 2 * F, "B2": 2 * ((F + BA_BLOCK - 1) // BA_BLOCK), "SD": BA_STATE_F64, "SI": BA_STATE_I32 + 2 * K}
+    views = {}
+    for (name, dt, cnt, cols), a in zip(BA_ARRAYS, offsets):
+        nbytes = count[cnt] * cols * torch.empty(0, dtype=dt).element_size()
+        v = workspace[a:a + nbytes].view(dt)
+        views[name] = v.view(count[cnt], cols) if cols > 1 else v
+    host = _tri_models(cam_model_host, F)
+    context = ctypes.create_string_buffer(BA_CONTEXT_BYTES)
+    _lib.check(L.pram_ba_begin(_p(keypoints), _p(cam_model), _p(cam_params), ctypes.addressof(host), _p(table), _p(xyz), _p(obs_row), _p(obs_frame),
+                               _p(obs_point), _p(frm_off), _p(pt_off), _p(pt_obs), _p(frozen), F, Pn, O, n, K, float(loss_scale), float(lam0),
+                               float(cg_tol), float(ftol), _p(workspace), workspace.numel(), ctypes.addressof(context), _st()), "pram_ba_begin")
+    return {"context": context, "workspace": workspace, "views": views, "n_frames": F, "n_points": Pn, "n_obs": O, "max_iters": K,
+            "keep": (keypoints, cam_model, cam_params, table, xyz, obs_row, obs_frame, obs_point, frm_off, pt_off, pt_obs, frozen)}
+
+
+def ba_iterate(problem: dict, n_iters: int, cg_iters: int, stages: int = BA_STAGE_ALL):
+    """Enqueues n_iters Levenberg-Marquardt iterations of at most cg_iters conjugate-gradient iterations each on ``problem``
+    (ba_begin's); ``stages``: BA_STAGE_* bits, for the tests and the timing tool.  Nothing is read back: the caller looks at
+    problem["views"]["state_i32"][BA_SI_DONE] once per group of iterations."""
+    import ctypes
+    L = _lib.load()
+    _lib.check(L.pram_ba_iterate(ctypes.addressof(problem["context"]), int(n_iters), int(cg_iters), int(stages), _st()), "pram_ba_iterate")
+
+
+def ba_finish(problem: dict, qvec: torch.Tensor, tvec: torch.Tensor, max_reproj_error: float = 4.0, min_tri_angle: float = 0.026179938779914945) -> dict:
+    """qvec float64 [F, 4], tvec float64 [F, 3]: the poses the problem's table was made from -> the refined qvec / tvec (a frame
+    that never moved keeps its input bit for bit), xyz float64 [P, 3], obs_keep uint8 [O], obs_error float64 [O], pt_keep int32 [P],
+    pt_error / pt_angle float64 [P], pt_kept int32 [P] and counts int32 [2] (weight-0 observations at the final state, observations
+    not kept).  min_tri_angle in radians."""
+    import ctypes
+    L = _lib.load()
+    F, Pn, O = problem["n_frames"], problem["n_points"], problem["n_obs"]
+    _tri_chk(((qvec, "qvec", torch.float64), (tvec, "tvec", torch.float64)))
+    assert qvec.numel() >= 4 * F and tvec.numel() >= 3 * F
+    dev = qvec.device
+    new = lambda m, dt, *rest: torch.empty(m, *rest, device=dev, dtype=dt)
+    out = {"qvec": new(F, torch.float64, 4), "tvec": new(F, torch.float64, 3), "xyz": new(Pn, torch.float64, 3), "obs_keep": new(O, torch.uint8),
+           "obs_error": new(O, torch.float64), "pt_keep": new(Pn, torch.int32), "pt_error": new(Pn, torch.float64),
+           "pt_angle": new(Pn, torch.float64), "pt_kept": new(Pn, torch.int32), "counts": new(2, torch.int32)}
+    _lib.check(L.pram_ba_finish(ctypes.addressof(problem["context"]), _p(qvec), _p(tvec), float(max_reproj_error), float(min_tri_angle),
+                                _p(out["qvec"]), _p(out["tvec"]), _p(out["xyz"]), _p(out["obs_keep"]), _p(out["obs_error"]), _p(out["pt_keep"]),
+                                _p(out["pt_error"]), _p(out["pt_angle"]), _p(out["pt_kept"]), _p(out["counts"]), _st()), "pram_ba_finish")
+    return out
