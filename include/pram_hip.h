@@ -1411,6 +1411,66 @@ int pram_ba_finish(const void* context, const double* qvec_in, const double* tve
                    double* qvec, double* tvec, double* xyz, unsigned char* obs_keep, double* obs_error, int* pt_keep,
                    double* pt_error, double* pt_angle, int* pt_kept, int* counts, void* stream);
 
+/* ---- incremental mapping (csrc/mapper.hip; pram_amd/localization/mapper.py drives these) ---------------------------------------
+ * The glue that turns pram_twoview_*, pram_pose_*, pram_tri_* and pram_ba_* into a mapper that needs no poses: a seed pair, then
+ * rounds of registration against the points so far, triangulation and adjustment.  NOT COLMAP's incremental mapper: every
+ * eligible frame of a round is registered at once, the model is re-triangulated in full and adjusted globally every round, the
+ * budgets are fixed (DESIGN.md 4.26 lists the deviations).  The entries read the triangulation's frame table (frame_off
+ * [n_frames + 1], keypoints [n_rows][2], norm [n_rows][2] = pram_tri_normalize with the offset 0.5), the match CSR and
+ * pram_twoview_finish's outputs, and pram_tri_adjacency's table.  A "row" is a keypoint's index in the frame table, a "point" an
+ * index into the current model's xyz [n_points][3].  Index rules, in every entry: an offset pair is clamped into its table; a frame,
+ * row or point outside its table is never dereferenced and yields nothing.  float64 where a coordinate is involved, integer sums
+ * only, no floating-point atomics; the result of every entry is a function of its inputs alone.  Every entry refuses (PRAM_E_ARG)
+ * a null or misaligned pointer (float64 and the workspace 8 bytes, int32 4), a negative size and a workspace that is too small;
+ * none waits for the stream and none allocates. */
+#define PRAM_MAP_MAX_LINKS 8           /* distinct points a keypoint may bring to its frame's correspondences */
+
+/* Seed scores, one workgroup per processed pair.  kept / count: pram_twoview_finish's (pair p's kept matches stand at
+ * kept[match_off[p] ..], count[p] of them); qvec [n_pairs][4], tvec [n_pairs][3], success [n_pairs]: its relative poses (frame 1
+ * from frame 0).  Per kept match: d0 the unit ray of frame 0, d1 = R^T times the unit ray of frame 1, X the midpoint of the two
+ * rays from the centres 0 and -R^T t, formed as pram_tri_triangulate forms a hypothesis; the match counts when X has positive
+ * depth in both frames; its angle is atan2(|d0 x d1|, d0 . d1).  n_tri [n_pairs]: the matches that count; tri_angle [n_pairs]: the
+ * LOWER median of their angles, element (n_tri - 1) / 2 in ascending order, found by bisection on the doubles' bit patterns (64
+ * counting passes over the workspace's word per match; no sort), 0 for n_tri = 0.  A pair with success == 0 has n_tri 0. */
+size_t pram_map_pair_angles_workspace_bytes(int n_matches);
+int pram_map_pair_angles(const double* norm, const int* frame_off, const int* pairs, const int* match_off, const int* kept,
+                         const int* count, const double* qvec, const double* tvec, const int* success, int n_frames, int n_pairs,
+                         int n_matches, void* workspace, size_t workspace_bytes, int* n_tri, double* tri_angle, void* stream);
+
+/* One workgroup.  seed [1]: among the pairs with success != 0, n_tri >= min_num_inliers and tri_angle >= min_tri_angle (radians) the
+ * one with the largest n_tri, the lowest position on a tie; -1 when none is eligible. */
+int pram_map_seed(const int* success, const int* n_tri, const double* tri_angle, int n_pairs, int min_num_inliers,
+                  double min_tri_angle, int* seed, void* stream);
+
+/* 2D-3D correspondences of the frames that are not registered, one workgroup per frame: a count pass, the offsets, a fill pass.
+ * adj_off [n_rows + 1] / adj [n_adj] / row_frame [n_rows]: pram_tri_adjacency's; registered [n_frames] uint8; row_point [n_rows]:
+ * the row's point in the current model or -1.  For every row u of an unregistered frame: the distinct row_point[v] in
+ * [0, n_points) over the v of adj(u) whose frame is registered, ascending, the PRAM_MAP_MAX_LINKS smallest of them.  n_corr
+ * [n_frames] (0 for a registered frame), corr_off [n_frames + 1], corr_row / corr_point [capacity] ordered by (row, point); a
+ * position at or beyond capacity is not written (n_corr and corr_off still say what there is).  dropped [n_frames]: per frame the
+ * entries of its rows' adjacency lists whose point is beyond the kept ones (an entry, not a distinct point: a point linked twice
+ * counts twice). */
+int pram_map_correspond(const int* adj_off, const int* adj, const int* row_frame, int n_adj, const int* frame_off,
+                        const unsigned char* registered, const int* row_point, int n_frames, int n_rows, int n_points, int capacity,
+                        int* n_corr, int* corr_off, int* dropped, int* corr_row, int* corr_point, void* stream);
+
+/* One workgroup.  The unregistered frames with n_corr >= max(min_corr, 1) and tries < max_reg_trials, ordered by (n_corr descending,
+ * frame ascending), at most round_frames of them (0: all): chosen [n_frames] (-1 padded), chosen_count [n_frames] (0 padded),
+ * n_chosen [1].  Selection rounds on a packed key, as pram_covis_topk. */
+int pram_map_choose(const int* n_corr, const unsigned char* registered, const int* tries, int n_frames, int min_corr,
+                    int max_reg_trials, int round_frames, int* chosen, int* chosen_count, int* n_chosen, void* stream);
+
+/* The chosen frames' correspondences as pram_pose_* take them: matched_keypoints [n_chosen][t0][2] (the keypoints as stored),
+ * matched_xyzs [n_chosen][t0][3], counts [n_chosen] = min(n_corr, t0); rows beyond t0 are dropped in table order and counted in
+ * cut [n_chosen]; the rows behind counts are zero.  A chosen frame outside [0, n_frames) has count 0. */
+int pram_map_pack(const int* chosen, int n_chosen, const int* corr_off, const int* corr_row, const int* corr_point, int n_corr_total,
+                  const float* keypoints, const double* xyz, int n_frames, int n_rows, int n_points, int t0,
+                  float* matched_keypoints, double* matched_xyzs, int* counts, int* cut, void* stream);
+
+/* One thread per edge: edges_out [n_edges][2] is the edge when the frames of both ends are registered, (-1, -1) otherwise. */
+int pram_map_live_edges(const int* edges, int n_edges, const int* row_frame, const unsigned char* registered, int n_frames,
+                        int n_rows, int* edges_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

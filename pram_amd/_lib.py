@@ -155,6 +155,13 @@ _SIGS = {
     "pram_ba_begin": (I, [P, P, P, P, P, P, P, P, P, P, P, P, P, I, I, I, I, I, C.c_double, C.c_double, C.c_double, C.c_double, P, SZ, P, P]),
     "pram_ba_iterate": (I, [P, I, I, I, P]),
     "pram_ba_finish": (I, [P, P, P, C.c_double, C.c_double, P, P, P, P, P, P, P, P, P, P, P]),
+    "pram_map_pair_angles_workspace_bytes": (SZ, [I]),
+    "pram_map_pair_angles": (I, [P, P, P, P, P, P, P, P, P, I, I, I, P, SZ, P, P, P]),
+    "pram_map_seed": (I, [P, P, P, I, I, C.c_double, P, P]),
+    "pram_map_correspond": (I, [P, P, P, I, P, P, P, I, I, I, I, P, P, P, P, P, P]),
+    "pram_map_choose": (I, [P, P, P, I, I, I, I, P, P, P, P]),
+    "pram_map_pack": (I, [P, I, P, P, P, I, P, P, I, I, I, I, P, P, P, P, P]),
+    "pram_map_live_edges": (I, [P, I, P, P, I, I, P, P]),
     "pram_knn_mean_distance": (I, [P, LL, I, P, P]),
     "pram_sor_workspace_bytes": (SZ, [LL]),
     "pram_sor_select": (I, [P, LL, C.c_double, P, SZ, P, P, P, P, P]),

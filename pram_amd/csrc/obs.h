@@ -65,6 +65,16 @@ __device__ __forceinline__ bool obs_inlier(const Obs& g, int r, int f, V3 X, dou
     return z > 0.0 && err2 <= thr2;
 }
 
+// the midpoint of the closest points of two rays: stage 4's hypothesis, stage 2b's point, the mapper's seed score
+__device__ __forceinline__ V3 ray_midpoint(V3 C1, V3 d1, V3 C2, V3 d2) {
+    const V3 w = sub(C1, C2);
+    const double a = dot(d1, d1), b = dot(d1, d2), c = dot(d2, d2), d = dot(d1, w), e = dot(d2, w);
+    const double den = a * c - b * b;
+    const double s = (b * e - c * d) / den, u = (a * e - b * d) / den;
+    return {0.5 * ((C1.x + s * d1.x) + (C2.x + u * d2.x)), 0.5 * ((C1.y + s * d1.y) + (C2.y + u * d2.y)),
+            0.5 * ((C1.z + s * d1.z) + (C2.z + u * d2.z))};
+}
+
 // A x = b for a symmetric A given as a00 a01 a02 a11 a12 a22, by Cholesky; false when a pivot is not positive or x is not finite
 static __device__ bool chol_solve3(const double* __restrict__ A, const double* __restrict__ b, double* x) {
     if (!(A[0] > 0.0)) return false;

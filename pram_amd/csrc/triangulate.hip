@@ -290,17 +290,6 @@ __global__ __launch_bounds__(256) void tri_derive_kernel(const int* __restrict__
     trk_frame[e] = f; trk_kpt[e] = r - frame_off[f];
 }
 
-// ---------------------------------------------------------------- the observation model (obs.h) and what stage 4 adds to it
-// the midpoint of the closest points of two rays: stage 4's hypothesis, stage 2b's point
-__device__ __forceinline__ V3 ray_midpoint(V3 C1, V3 d1, V3 C2, V3 d2) {
-    const V3 w = sub(C1, C2);
-    const double a = dot(d1, d1), b = dot(d1, d2), c = dot(d2, d2), d = dot(d1, w), e = dot(d2, w);
-    const double den = a * c - b * b;
-    const double s = (b * e - c * d) / den, u = (a * e - b * d) / den;
-    return {0.5 * ((C1.x + s * d1.x) + (C2.x + u * d2.x)), 0.5 * ((C1.y + s * d1.y) + (C2.y + u * d2.y)),
-            0.5 * ((C1.z + s * d1.z) + (C2.z + u * d2.z))};
-}
-
 // ---------------------------------------------------------------- triangulate: one wave per track
 // entry e's row and frame; ok: the tables hold both (a caller's own track table may name neither)
 struct Entry { int r, f; bool ok; };

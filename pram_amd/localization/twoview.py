@@ -21,7 +21,7 @@ Where this differs from the reference, on purpose:
   * only the calibrated configuration is estimated: no fundamental matrix, no homography, and no classification of a pair as
     planar, panoramic or watermark.
   * a pure rotation leaves the translation undetermined: ``qvec`` and the mask are still meaningful, ``tvec`` is not, and
-    ``num_front`` does not say so.
+    ``num_front`` does not say so; mapper.initial_pairs' ``tri_angle`` does.
   * no local optimisation inside the loop: the best hypothesis is refined once the loop is over.
   * out-of-range indices: a match with a keypoint index outside its frame is no inlier and a sample that draws it yields no
     hypothesis, where the reference would raise."""

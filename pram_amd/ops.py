@@ -2745,3 +2745,110 @@ def ba_finish(problem: dict, qvec: torch.Tensor, tvec: torch.Tensor, max_reproj_
                                 _p(out["qvec"]), _p(out["tvec"]), _p(out["xyz"]), _p(out["obs_keep"]), _p(out["obs_error"]), _p(out["pt_keep"]),
                                 _p(out["pt_error"]), _p(out["pt_angle"]), _p(out["pt_kept"]), _p(out["counts"]), _st()), "pram_ba_finish")
     return out
+
+
+# ---- incremental mapping (csrc/mapper.hip; pram_amd/localization/mapper.py drives these) --------------------------------------
+MAP_MAX_LINKS = 8      # PRAM_MAP_MAX_LINKS
+
+
+def map_pair_angles(norm: torch.Tensor, frame_off: torch.Tensor, pairs: torch.Tensor, match_off: torch.Tensor, kept: torch.Tensor,
+                    count: torch.Tensor, qvec: torch.Tensor, tvec: torch.Tensor, success: torch.Tensor, n_frames: int, n_pairs: int,
+                    n_matches: int, workspace: Optional[torch.Tensor] = None) -> dict:
+    """norm: tri_normalize with offset 0.5; pairs / match_off: the match CSR; kept int32 [M, 2], count, qvec [Pn, 4], tvec [Pn, 3],
+    success int32 [Pn]: twoview_finish's -> n_tri int32 [Pn] (the kept matches whose midpoint lies in front of both cameras) and
+    tri_angle float64 [Pn] (the lower median of their angles, radians; 0 for n_tri = 0)."""
+    L = _lib.load()
+    F, Pn, M = int(n_frames), int(n_pairs), int(n_matches)
+    _twoview_views(norm, frame_off, pairs, match_off, kept, F, Pn, M)
+    _tri_chk(((count, "count", torch.int32), (qvec, "qvec", torch.float64), (tvec, "tvec", torch.float64), (success, "success", torch.int32)))
+    assert count.numel() >= Pn and qvec.numel() >= 4 * Pn and tvec.numel() >= 3 * Pn and success.numel() >= Pn
+    dev = norm.device
+    workspace = _tri_workspace(int(L.pram_map_pair_angles_workspace_bytes(M)), "pram_map_pair_angles: a negative number of matches", workspace, dev)
+    out = {"n_tri": torch.empty(max(Pn, 1), device=dev, dtype=torch.int32), "tri_angle": torch.empty(max(Pn, 1), device=dev, dtype=torch.float64)}
+    _lib.check(L.pram_map_pair_angles(_p(norm), _p(frame_off), _p(pairs), _p(match_off), _p(kept), _p(count), _p(qvec), _p(tvec), _p(success),
+                                      F, Pn, M, _p(workspace), workspace.numel(), _p(out["n_tri"]), _p(out["tri_angle"]), _st()),
+               "pram_map_pair_angles")
+    return out
+
+
+def map_seed(success: torch.Tensor, n_tri: torch.Tensor, tri_angle: torch.Tensor, n_pairs: int, min_num_inliers: int,
+             min_tri_angle: float) -> torch.Tensor:
+    """-> int32 [1]: the eligible pair (success, n_tri >= min_num_inliers, tri_angle >= min_tri_angle in radians) with the largest
+    n_tri, the lowest position on a tie; -1 when none is eligible.  On the device."""
+    L = _lib.load()
+    Pn = int(n_pairs)
+    _tri_chk(((success, "success", torch.int32), (n_tri, "n_tri", torch.int32), (tri_angle, "tri_angle", torch.float64)))
+    assert success.numel() >= Pn and n_tri.numel() >= Pn and tri_angle.numel() >= Pn
+    seed = torch.empty(1, device=success.device, dtype=torch.int32)
+    _lib.check(L.pram_map_seed(_p(success), _p(n_tri), _p(tri_angle), Pn, int(min_num_inliers), float(min_tri_angle), _p(seed), _st()),
+               "pram_map_seed")
+    return seed
+
+
+def map_correspond(adj_off: torch.Tensor, adj: torch.Tensor, row_frame: torch.Tensor, n_adj: int, frame_off: torch.Tensor,
+                   registered: torch.Tensor, row_point: torch.Tensor, n_frames: int, n_rows: int, n_points: int,
+                   capacity: Optional[int] = None) -> dict:
+    """adj_off / adj / row_frame: tri_adjacency's (n_adj: the entries adj holds); registered uint8 [F]; row_point int32 [n_rows]
+    -> n_corr int32 [F], corr_off int32 [F + 1], dropped int32 [F], corr_row / corr_point int32 [capacity] ordered by (row, point).
+    capacity: None sizes the lists for the worst case, min(MAP_MAX_LINKS * n_rows, n_adj)."""
+    L = _lib.load()
+    F, n, A, Pt = int(n_frames), int(n_rows), int(n_adj), int(n_points)
+    _tri_chk(((adj_off, "adj_off", torch.int32), (adj, "adj", torch.int32), (row_frame, "row_frame", torch.int32), (frame_off, "frame_off", torch.int32),
+              (registered, "registered", torch.uint8), (row_point, "row_point", torch.int32)))
+    assert adj_off.numel() >= n + 1 and adj.numel() >= A and row_frame.numel() >= n and frame_off.numel() >= F + 1
+    assert registered.numel() >= F and row_point.numel() >= n
+    cap = min(MAP_MAX_LINKS * n, A) if capacity is None else int(capacity)
+    dev = adj.device
+    i32 = lambda m: torch.empty(max(m, 1), device=dev, dtype=torch.int32)
+    out = {"n_corr": i32(F), "corr_off": i32(F + 1), "dropped": i32(F), "corr_row": i32(cap), "corr_point": i32(cap), "capacity": cap}
+    _lib.check(L.pram_map_correspond(_p(adj_off), _p(adj), _p(row_frame), A, _p(frame_off), _p(registered), _p(row_point), F, n, Pt, cap,
+                                     _p(out["n_corr"]), _p(out["corr_off"]), _p(out["dropped"]), _p(out["corr_row"]), _p(out["corr_point"]), _st()),
+               "pram_map_correspond")
+    return out
+
+
+def map_choose(n_corr: torch.Tensor, registered: torch.Tensor, tries: torch.Tensor, n_frames: int, min_corr: int = 30, max_reg_trials: int = 3,
+               round_frames: int = 0) -> dict:
+    """-> chosen int32 [F] (-1 padded), chosen_count int32 [F] and n_chosen int32 [1], on the device: the unregistered frames with
+    n_corr >= min_corr and tries < max_reg_trials by (n_corr descending, frame ascending), round_frames of them at most (0: all)."""
+    L = _lib.load()
+    F = int(n_frames)
+    _tri_chk(((n_corr, "n_corr", torch.int32), (registered, "registered", torch.uint8), (tries, "tries", torch.int32)))
+    assert n_corr.numel() >= F and registered.numel() >= F and tries.numel() >= F
+    i32 = lambda m: torch.empty(max(m, 1), device=n_corr.device, dtype=torch.int32)
+    out = {"chosen": i32(F), "chosen_count": i32(F), "n_chosen": i32(1)}
+    _lib.check(L.pram_map_choose(_p(n_corr), _p(registered), _p(tries), F, int(min_corr), int(max_reg_trials), int(round_frames), _p(out["chosen"]),
+                                 _p(out["chosen_count"]), _p(out["n_chosen"]), _st()), "pram_map_choose")
+    return out
+
+
+def map_pack(chosen: torch.Tensor, n_chosen: int, corr: dict, keypoints: torch.Tensor, xyz: torch.Tensor, n_frames: int, n_rows: int,
+             n_points: int, t0: int) -> dict:
+    """chosen int32 [S]; corr: map_correspond's dict -> matched_keypoints float32 [S, t0, 2], matched_xyzs float64 [S, t0, 3], counts
+    int32 [S] and cut int32 [S] (the rows beyond t0), as pose.estimate_poses takes them."""
+    L = _lib.load()
+    S, F, n, Pt, t0 = int(n_chosen), int(n_frames), int(n_rows), int(n_points), int(t0)
+    _tri_chk(((chosen, "chosen", torch.int32), (corr["corr_off"], "corr_off", torch.int32), (corr["corr_row"], "corr_row", torch.int32),
+              (corr["corr_point"], "corr_point", torch.int32), (keypoints, "keypoints", torch.float32), (xyz, "xyz", torch.float64)))
+    cap = int(corr["capacity"])
+    assert chosen.numel() >= S and corr["corr_off"].numel() >= F + 1 and min(corr["corr_row"].numel(), corr["corr_point"].numel()) >= cap
+    assert keypoints.numel() >= 2 * n and xyz.numel() >= 3 * Pt
+    dev = chosen.device
+    out = {"matched_keypoints": torch.empty(max(S, 1), max(t0, 1), 2, device=dev, dtype=torch.float32),
+           "matched_xyzs": torch.empty(max(S, 1), max(t0, 1), 3, device=dev, dtype=torch.float64),
+           "counts": torch.empty(max(S, 1), device=dev, dtype=torch.int32), "cut": torch.empty(max(S, 1), device=dev, dtype=torch.int32)}
+    _lib.check(L.pram_map_pack(_p(chosen), S, _p(corr["corr_off"]), _p(corr["corr_row"]), _p(corr["corr_point"]), cap, _p(keypoints), _p(xyz), F, n,
+                               Pt, t0, _p(out["matched_keypoints"]), _p(out["matched_xyzs"]), _p(out["counts"]), _p(out["cut"]), _st()),
+               "pram_map_pack")
+    return out
+
+
+def map_live_edges(edges: torch.Tensor, n_edges: int, row_frame: torch.Tensor, registered: torch.Tensor, n_frames: int, n_rows: int) -> torch.Tensor:
+    """edges int32 [n_edges, 2] rows -> int32 [n_edges, 2]: the edge where the frames of both ends are registered, (-1, -1) elsewhere."""
+    L = _lib.load()
+    m, F, n = int(n_edges), int(n_frames), int(n_rows)
+    _tri_chk(((edges, "edges", torch.int32), (row_frame, "row_frame", torch.int32), (registered, "registered", torch.uint8)))
+    assert edges.numel() >= 2 * m and row_frame.numel() >= n and registered.numel() >= F
+    out = torch.empty(max(m, 1), 2, device=edges.device, dtype=torch.int32)
+    _lib.check(L.pram_map_live_edges(_p(edges), m, _p(row_frame), _p(registered), F, n, _p(out), _st()), "pram_map_live_edges")
+    return out
