@@ -5,7 +5,7 @@
 // every kernel reads, so nothing is read by the host inside a solve and a finished solve turns the launches that are still
 // enqueued into early exits.  float64 throughout, no floating-point atomics; every sum has one fixed order:
 //   * per point over its observations: per lane in ascending order, then the butterfly of wave_sum_f64 (one wave per point);
-//   * per frame over its observations: the same per wave, then the fixed 4-wave fold of pose.hip's lm_pass (one workgroup);
+//   * per frame over its observations: the same per wave, then the fixed 4-wave fold of block_fold_f64 (one workgroup);
 //   * over frames (dot products, the cost): blocks of PRAM_BA_BLOCK consecutive frames added to 0.0 in ascending order, the block
 //     partials added to 0.0 in ascending order (the blocked order of kmeans.hip).
 // The final filter is COLMAP's point filter (FilterPoints3D: reprojection error and the largest triangulation angle) as
@@ -70,20 +70,6 @@ __device__ double blocked_sum(const double* v, int n, double* part, double* sh) 
     const double out = sh[0];
     __syncthreads();
     return out;
-}
-
-// per-frame sums: NV values per thread -> tot [NV] in LDS, by the wave butterfly and the fixed 4-wave fold
-template <int NV>
-__device__ __forceinline__ void frame_fold(double* acc, double (*wred)[NV], double* tot) {
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-#pragma unroll
-    for (int e = 0; e < NV; ++e) {
-        const double s = wave_sum_f64(acc[e]);
-        if (lane == 0) wred[wave][e] = s;
-    }
-    __syncthreads();
-    if (tid < NV) tot[tid] = ((wred[0][tid] + wred[1][tid]) + wred[2][tid]) + wred[3][tid];
-    __syncthreads();
 }
 
 // M z = r with the frame's block of S (damped already); a block that does not factor leaves z = r
@@ -264,7 +250,7 @@ __global__ __launch_bounds__(256) void ba_frames_kernel(Ba g) {
             acc[33 + a] += WV[a][0] * gp[0] + WV[a][1] * gp[1] + WV[a][2] * gp[2];
         }
     }
-    frame_fold<NV_FRAME>(acc, wred, tot);
+    block_fold_f64<NV_FRAME>(acc, wred, tot);
     if (tid != 0) return;
     const double lam = g.sd[SD_LAM];
     const int mask = g.fmask[f];
@@ -366,7 +352,7 @@ __global__ __launch_bounds__(256) void ba_mv_frames_kernel(Ba g) {
 #pragma unroll
         for (int a = 0; a < 6; ++a) acc[a] += j[a] * t0 + j[6 + a] * t1;
     }
-    frame_fold<6>(acc, wred, tot);
+    block_fold_f64<6>(acc, wred, tot);
     if (tid != 0) return;
     const double lam = g.sd[SD_LAM];
     const int mask = g.fmask[f];
@@ -476,7 +462,7 @@ __global__ __launch_bounds__(256) void ba_cost_kernel(Ba g, int cand) {
         const double s = (r0 * r0 + r1 * r1) / loss2;
         if (z > 1e-12 && fin(s)) acc[0] += log1p(s);
     }
-    frame_fold<1>(acc, wred, tot);
+    block_fold_f64<1>(acc, wred, tot);
     if (tid == 0) g.fcost[f] = tot[0];
 }
 
@@ -567,8 +553,7 @@ __global__ __launch_bounds__(64) void ba_filter_points_kernel(Ba g, const unsign
     }
     cnt = wave_sum_i32(cnt);
     esum = wave_sum_f64(esum);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) best = fmax(best, __shfl_xor(best, o, 64));
+    best = wave_max_f64(best);
     if (lane != 0) return;
     pt_keep[p] = cnt >= 2 && best >= min_angle;
     pt_err[p] = cnt > 0 ? esum / (double)cnt : 0.0;

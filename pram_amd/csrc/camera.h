@@ -1,7 +1,8 @@
-// What the float64 geometry kernels share (pose.hip, triangulate.hip): COLMAP's camera models unified to OPENCV, its distortion
-// function and Jacobian, the 3-vector helpers, the butterfly sums of a wave and the counter-based sampler's mixing function.
+// What the float64 geometry kernels share (pose.hip, twoview.hip, triangulate.hip, and through obs.h and ransac.h bundle.hip and
+// mapper.hip): COLMAP's camera models unified to OPENCV, its distortion function and Jacobian, the 3-vector helpers and the
+// counter-based sampler's mixing function.  The sums of a wave and of a workgroup are workgroup.h's, included from here.
 #pragma once
-#include "common.h"
+#include "workgroup.h"
 #include <math.h>
 
 struct Cam { double fx, fy, cx, cy, k1, k2, p1, p2; };
@@ -42,18 +43,6 @@ __device__ __forceinline__ double dot(V3 a, V3 b) { return a.x * b.x + a.y * b.y
 __device__ __forceinline__ V3 cross(V3 a, V3 b) { return {a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x}; }
 __device__ __forceinline__ double angle(V3 a, V3 b) { const V3 c = cross(a, b); return atan2(sqrt(dot(c, c)), dot(a, b)); }
 __device__ __forceinline__ bool fin(double x) { return isfinite(x); }
-
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
-__device__ __forceinline__ int wave_sum_i32(int v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
 
 __device__ __forceinline__ unsigned long long sm64(unsigned long long x) {
     x += 0x9E3779B97F4A7C15ull;

@@ -44,6 +44,9 @@ __device__ __forceinline__ void project(const Cam& c, double x, double y, double
 // the device state of one selection: all of it in the caller's workspace
 struct SelState { int* row_pt; int* kept; int* disc; int* chain; int* counts; };      // counts[0]: chain length, counts[1]: frames retained
 
+// Frame f's rows, cut by hand and not by glue.h's clamped_range: the callers iterate [r0, r1) or cap a count at r1 - r0 that is
+// compared with nkpts >= 1, so the two agree, but clamped_range's two further bounds measured 1.3 % on pram_compress_select, whose
+// thousands of one-workgroup launches are each a few instructions long (profiles/geometry_shared_code.md).
 __device__ __forceinline__ void frame_rows(const int* __restrict__ frame_off, int f, int n_rows, int& r0, int& r1) {
     r0 = frame_off[f];
     r1 = frame_off[f + 1];
@@ -169,10 +172,9 @@ __global__ __launch_bounds__(256) void compress_commit_kernel(const int* __restr
             n += keep;
         }
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) n += __shfl_xor(n, o, 64);
+    n = wave_sum_i32(n);
     if ((tid & 63) == 0) s4[tid >> 6] = n;
-    __syncthreads();
+    __syncthreads();      // not block_sum_i32: s4 is written once and thread 0 alone reads the sum, so one barrier does
     if (tid == 0 && (was || s4[0] + s4[1] + s4[2] + s4[3] > 0)) {
         if (!was) ret_order[c] = st.counts[1]++;
         const int len = st.counts[0];

@@ -1,9 +1,10 @@
-// Building blocks the localisation glue kernels share (candidates.hip, refine.hip, projref.hip, track.hip, extras.hip): the
-// columns of the plan table, the match list and its row copies, ordered compaction inside a workgroup, the search over the sorted
-// point ids, and the covisible list of the frame a localisation kept.  Two of them serve every file that searches or walks a CSR
-// table (kmeans.hip and triangulate.hip too): the one bisection, first_true, and clamped_range.
+// Building blocks the localisation glue kernels share (candidates.hip, refine.hip, projref.hip, track.hip, retrieval.hip,
+// extras.hip): the columns of the plan table, the match list and its row copies, the search over the sorted point ids, and the
+// covisible list of the frame a localisation kept.  Two of them serve every file that searches or walks a CSR table (kmeans.hip,
+// triangulate.hip, twoview.hip, mapper.hip, mapbuild.hip and compress.hip too): the one bisection, first_true, and clamped_range.
+// The collectives (ordered compaction, the workgroup's sums and maxima) are workgroup.h's, which every includer gets from here.
 #pragma once
-#include "common.h"
+#include "workgroup.h"
 
 // column-major plan table: field X of pair p at plan[X * pairs + p]
 enum { PL_QUERY = 0, PL_SID, PL_FRAME, PL_SEM, PL_LEN0, PL_LEN1, PL_TOK_OFF, PL_ROW0, PL_SEL_OFF, PL_ORDER };
@@ -53,48 +54,6 @@ __device__ __forceinline__ void match_emit_row(const MatchList& dst, size_t d, l
     dst.p3d[d] = p3d;
     dst.xyz[d * 3] = x; dst.xyz[d * 3 + 1] = y; dst.xyz[d * 3 + 2] = z;
     dst.sids[d] = sid;
-}
-
-// Ordered compaction inside a workgroup of WAVES waves, one chunk of 64 * WAVES items per call; every thread of the workgroup
-// calls it.  Returns the offset of this thread's items among the chunk's (thread order) and the chunk's total through `total`;
-// the caller adds the running base, a register every thread carries.  Two barriers: the first lets the previous call's readers
-// of wsum [WAVES] finish, the second publishes this call's sums.
-// Flag form: one item or none per thread.
-template <int WAVES>
-__device__ __forceinline__ int chunk_offset(bool f, int* wsum, int& total) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const unsigned long long bal = __ballot(f);
-    const int before = __popcll(bal & ((1ull << lane) - 1ull));
-    __syncthreads();
-    if (lane == 0) wsum[wave] = __popcll(bal);
-    __syncthreads();
-    int woff = 0, tot = 0;
-#pragma unroll
-    for (int w = 0; w < WAVES; ++w) { if (w < wave) woff += wsum[w]; tot += wsum[w]; }
-    total = tot;
-    return woff + before;
-}
-
-// Count form: n >= 0 items per thread.  A caller that compacts in place (reads a chunk, calls this, writes at or before the
-// positions read so far: phase 2 of projref_project_kernel) relies on a barrier standing between the chunk's reads and its
-// writes; both barriers here do.
-template <int WAVES>
-__device__ __forceinline__ int chunk_offset_n(int n, int* wsum, int& total) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int incl = n;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const int v = __shfl_up(incl, o, 64);
-        if (lane >= o) incl += v;
-    }
-    __syncthreads();
-    if (lane == 63) wsum[wave] = incl;
-    __syncthreads();
-    int woff = 0, tot = 0;
-#pragma unroll
-    for (int w = 0; w < WAVES; ++w) { if (w < wave) woff += wsum[w]; tot += wsum[w]; }
-    total = tot;
-    return woff + incl - n;
 }
 
 // The one bisection: the first index i in [lo, hi) at which the monotone predicate holds (false ... false true ... true), hi if

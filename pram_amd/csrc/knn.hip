@@ -5,7 +5,7 @@
 //     query's smallest d2 as a sorted list in registers.
 //   * pram_sor_select: the valid points' mean and sample deviation in the k-means order of sums (blocks of PRAM_SOR_BLOCK, a block
 //     added serially by one thread, the block sums in block order by one workgroup), then the mask and an ordered compaction of
-//     the inliers' indices on glue.h's chunk_offset.
+//     the inliers' indices on workgroup.h's chunk_offset.
 // Float64 throughout, every product and sum written out (the library is built with -ffp-contract=off); no floating-point atomics;
 // plain stores only; no workgroup waits for another; every loop is bounded by an argument.
 #include "glue.h"

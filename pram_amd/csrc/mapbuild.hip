@@ -30,9 +30,7 @@ __device__ __forceinline__ double dot128_half(const float4 x, const float4 y) {
     q = fma((double)x.y, (double)y.y, q);
     q = fma((double)x.z, (double)y.z, q);
     q = fma((double)x.w, (double)y.w, q);
-#pragma unroll
-    for (int o = 16; o > 0; o >>= 1) q += __shfl_xor(q, o, 64);
-    return q;
+    return half_wave_sum_f64(q);
 }
 
 // numpy's median of the n values that are not NaN among d[0 .. len) by rank counting, into v[0] (the k0-th smallest) and v[1]
@@ -120,12 +118,7 @@ __global__ __launch_bounds__(256) void mapbuild_desc_kernel(const float4* __rest
             double m = tid < n ? (s_v[tid & (MB_SHORT - 1)] + s_v[MB_SHORT + (tid & (MB_SHORT - 1))]) * 0.5 : __longlong_as_double(0x7ff0000000000000LL);
             int bi = tid < n ? tid : 0x7fffffff;
             if (tid < 64) {
-#pragma unroll
-                for (int o = 32; o > 0; o >>= 1) {
-                    const double om = __shfl_xor(m, o, 64);
-                    const int oi = __shfl_xor(bi, o, 64);
-                    if (om < m || (om == m && oi < bi)) { m = om; bi = oi; }
-                }
+                wave_argmin_f64(m, bi);
                 if (tid == 0) s_n = bi < n ? bi : 0;      // a track of NaN rows: in range, no more is promised
             }
             __syncthreads();
@@ -146,8 +139,7 @@ __global__ __launch_bounds__(256) void mapbuild_desc_kernel(const float4* __rest
             rows[j] = r;
             cnt += r >= 0;
         }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) cnt += __shfl_xor(cnt, o, 64);
+        cnt = wave_sum_i32(cnt);
         if (lane == 0 && cnt) atomicAdd(&s_n, cnt);
         __syncthreads();
         const int n = s_n;
@@ -208,41 +200,15 @@ __device__ __forceinline__ int vrf_lookup(const unsigned long long* hkey, const 
     return -1;
 }
 
-// every thread of the workgroup calls these; two barriers each, as chunk_offset
-__device__ __forceinline__ unsigned long long block_max_u64(unsigned long long v, unsigned long long* s4) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const unsigned long long other = __shfl_xor(v, o, 64);
-        v = other > v ? other : v;
-    }
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) s4[threadIdx.x >> 6] = v;
-    __syncthreads();
-    v = s4[0];
-    for (int w = 1; w < 4; ++w) v = s4[w] > v ? s4[w] : v;
-    return v;
-}
-
-__device__ __forceinline__ int block_sum(int v, int* s4) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) s4[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return s4[0] + s4[1] + s4[2] + s4[3];
-}
-
 // recmap.py:289: a frame's observation count = its rows with id > 0.  One workgroup per frame.
 __global__ __launch_bounds__(256) void mapbuild_frame_obs_kernel(const long long* __restrict__ ids, const int* __restrict__ frame_off,
                                                                  int n_rows, int* __restrict__ fcount) {
     __shared__ int s4[4];
     const int f = blockIdx.x;
-    int r0 = frame_off[f], r1 = frame_off[f + 1];
-    r0 = r0 < 0 ? 0 : r0;
-    r1 = r1 > n_rows ? n_rows : r1;
-    int c = 0;
+    int r0, r1, c = 0;
+    clamped_range(frame_off[f], frame_off[f + 1], n_rows, r0, r1);
     for (int r = r0 + (int)threadIdx.x; r < r1; r += 256) c += ids[r] > 0;
-    c = block_sum(c, s4);
+    c = block_sum_i32<4>(c, s4);
     if (threadIdx.x == 0) fcount[f] = c;
 }
 
@@ -298,9 +264,8 @@ __global__ __launch_bounds__(256) void mapbuild_vrf_kernel(const long long* __re
         }
         const int lo = lower_bound_i64(pt_ids, n_points, id);
         if (lo >= n_points || pt_ids[lo] != id) continue;
-        int e0 = pt_off[lo], e1 = pt_off[lo + 1];
-        e0 = e0 < 0 ? 0 : e0;
-        e1 = e1 > n_entries ? n_entries : e1;
+        int e0, e1;
+        clamped_range(pt_off[lo], pt_off[lo + 1], n_entries, e0, e1);
         for (int e = e0; e < e1; ++e) {
             const int f = pt_frames[e];
             if (f >= 0 && f < F && frame_ignored[f] == 0) atomicMin(enc + f, ((unsigned long long)(unsigned)q << 32) | (unsigned)(e - e0));
@@ -342,9 +307,8 @@ __global__ __launch_bounds__(256) void mapbuild_vrf_kernel(const long long* __re
     // ---- masks (recmap.py:311-322): one wave per candidate, a bit per list position whose id a row of the frame carries
     for (int c = wave; c < n_cand; c += 4) {
         const int f = cand[c];
-        int r0 = frame_off[f], r1 = frame_off[f + 1];
-        r0 = r0 < 0 ? 0 : r0;
-        r1 = r1 > n_rows ? n_rows : r1;
+        int r0, r1;
+        clamped_range(frame_off[f], frame_off[f + 1], n_rows, r0, r1);
         for (int r = r0 + lane; r < r1; r += 64) {
             const long long id = ids[r];
             if (id <= 0) continue;
@@ -369,7 +333,7 @@ __global__ __launch_bounds__(256) void mapbuild_vrf_kernel(const long long* __re
             const unsigned long long key = ((unsigned long long)(unsigned)gain << 32) | (unsigned)(0x7fffffff - c);
             best = key > best ? key : best;
         }
-        best = block_max_u64(best, s_u64);      // the largest gain, then the first candidate
+        best = block_max_u64<4>(best, s_u64);      // the largest gain, then the first candidate
         if (best == 0ull) break;
         const int c = 0x7fffffff - (int)(best & 0xffffffffu), gain = (int)(best >> 32);
         if (tid == 0) s_chosen[n_ch] = c;
@@ -379,7 +343,7 @@ __global__ __launch_bounds__(256) void mapbuild_vrf_kernel(const long long* __re
             unobs[w] = u;
             rem += __popc(u);
         }
-        rem = block_sum(rem, s_i4);
+        rem = block_sum_i32<4>(rem, s_i4);
         ++n_ch;
         if ((double)gain / (double)n < gain_floor) break;
         if (!(1.0 - (double)rem / (double)n < min_cover)) break;
@@ -398,9 +362,8 @@ __global__ __launch_bounds__(256) void mapbuild_vrf_kernel(const long long* __re
         const double r00 = 1.0 - 2.0 * qy * qy - 2.0 * qz * qz, r01 = 2.0 * qx * qy - 2.0 * qw * qz, r02 = 2.0 * qz * qx + 2.0 * qw * qy;
         const double r10 = 2.0 * qx * qy + 2.0 * qw * qz, r11 = 1.0 - 2.0 * qx * qx - 2.0 * qz * qz, r12 = 2.0 * qy * qz - 2.0 * qw * qx;
         const double r20 = 2.0 * qz * qx - 2.0 * qw * qy, r21 = 2.0 * qy * qz + 2.0 * qw * qx, r22 = 1.0 - 2.0 * qx * qx - 2.0 * qy * qy;
-        int r0 = frame_off[f], r1 = frame_off[f + 1];
-        r0 = r0 < 0 ? 0 : r0;
-        r1 = r1 > n_rows ? n_rows : r1;
+        int r0, r1;
+        clamped_range(frame_off[f], frame_off[f + 1], n_rows, r0, r1);
         int flag = 0;
         for (int r = r0 + tid; r < r1; r += 256) {
             const long long id = ids[r];

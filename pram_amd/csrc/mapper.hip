@@ -14,31 +14,6 @@ constexpr int LINKS = PRAM_MAP_MAX_LINKS;
 constexpr int NO_POINT = 0x7fffffff;                 // an empty slot of a row's sorted list
 constexpr unsigned long long NOT_COUNTED = ~0ull;    // the scratch word of a match that does not count: above every angle's bits
 
-// the sum of v over a workgroup of 4 waves, in every thread; two barriers, as chunk_offset
-__device__ __forceinline__ int block_sum_i32(int v, int* wsum) {
-    v = wave_sum_i32(v);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return wsum[0] + wsum[1] + wsum[2] + wsum[3];
-}
-
-// the largest key over a workgroup of 4 waves, in every thread
-__device__ __forceinline__ unsigned long long block_max_u64(unsigned long long v, unsigned long long* wbest) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const unsigned long long other = __shfl_xor(v, o, 64);
-        v = other > v ? other : v;
-    }
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) wbest[threadIdx.x >> 6] = v;
-    __syncthreads();
-    v = wbest[0];
-#pragma unroll
-    for (int w = 1; w < 4; ++w) v = wbest[w] > v ? wbest[w] : v;
-    return v;
-}
-
 // ---------------------------------------------------------------- stage 1: the seed scores, one workgroup per pair
 // Frame 0 is the world: its centre the origin, its rays as they are.  Frame 1 is (R, t) of the pair's qvec / tvec, laid out as a
 // row of the frame table so that the rays, the midpoint and the depths are obs.h's.  The angles go to scratch as bit patterns;
@@ -97,14 +72,14 @@ __global__ __launch_bounds__(256) void map_pair_angles_kernel(const double* __re
         scratch[m0 + e] = word;
         mine += word != NOT_COUNTED;
     }
-    const int total = block_sum_i32(mine, wsum);      // its barriers also publish the workgroup's scratch words
+    const int total = block_sum_i32<4>(mine, wsum);      // its barriers also publish the workgroup's scratch words
     const int k = (total - 1) / 2;
     unsigned long long med = 0;
     for (int bit = 63; bit >= 0; --bit) {
         const unsigned long long cand = med | (1ull << bit);
         int below = 0;
         for (int e = tid; e < n; e += 256) below += scratch[m0 + e] < cand;
-        if (block_sum_i32(below, wsum) <= k) med = cand;
+        if (block_sum_i32<4>(below, wsum) <= k) med = cand;
     }
     if (tid == 0) {
         n_tri[p] = total;
@@ -124,7 +99,7 @@ __global__ __launch_bounds__(256) void map_seed_kernel(const int* __restrict__ s
         const unsigned long long key = ((unsigned long long)(unsigned)n << 32) | (unsigned)(0x7fffffff - p);
         if (ok && key > best) best = key;
     }
-    best = block_max_u64(best, wbest);
+    best = block_max_u64<4>(best, wbest);
     if (threadIdx.x == 0) seed[0] = best ? 0x7fffffff - (int)(best & 0xffffffffu) : -1;
 }
 
@@ -196,7 +171,7 @@ __global__ __launch_bounds__(256) void map_correspond_kernel(MapAdj a, const int
         lost += rest;
     }
     if (!FILL) {
-        lost = block_sum_i32(lost, wsum);
+        lost = block_sum_i32<4>(lost, wsum);
         if (tid == 0) { n_corr[f] = base; dropped[f] = lost; }
     }
 }
@@ -233,7 +208,7 @@ __global__ __launch_bounds__(256) void map_choose_kernel(const int* __restrict__
             const unsigned long long key = ((unsigned long long)(unsigned)c << 32) | (unsigned)(0x7fffffff - f);
             if (registered[f] == 0 && c > 0 && c >= min_corr && tries[f] < max_reg_trials && key < prev && key > best) best = key;
         }
-        best = block_max_u64(best, wbest);
+        best = block_max_u64<4>(best, wbest);
         if (best == 0) break;      // uniform: nothing left, every later round finds nothing either
         prev = best;
         if (tid == 0) { chosen[found] = 0x7fffffff - (int)(best & 0xffffffffu); chosen_count[found] = (int)(best >> 32); }

@@ -1,5 +1,6 @@
-// The observation model the map kernels share (triangulate.hip, bundle.hip): keypoint (row) r seen in frame f of the frame table,
-// and the 3 x 3 Cholesky solve of a point's normal equations.
+// The observation model the map kernels share (triangulate.hip, bundle.hip, mapper.hip): keypoint (row) r seen in frame f of the
+// frame table, its ray, residual and midpoint, and the 3 x 3 Cholesky solve of a point's normal equations.  camera.h brings the
+// camera model and, through workgroup.h, the sums.
 #pragma once
 #include "camera.h"
 

@@ -15,7 +15,6 @@ constexpr int QUARTIC_POLISH = 3;
 constexpr int SCORE_CHUNK = 768;          // rows per LDS chunk: 5 doubles each = 30 KB (always chunked, whatever t0)
 constexpr int SCORE_TPW = 4;              // trials a wave takes in turn on every chunk
 constexpr int SCORE_TRIALS = 4 * SCORE_TPW;      // trials per workgroup: the rows staged in LDS serve 16 trials = 64 slots
-constexpr double LM_LAMBDA0 = 1e-3;
 
 // ---------------------------------------------------------------- prepare: pixels -> normalised camera plane
 __global__ __launch_bounds__(256) void pose_prepare_kernel(const float* __restrict__ kpts, const int* __restrict__ count,
@@ -261,9 +260,7 @@ __global__ __launch_bounds__(256) void pose_score_kernel(const double* __restric
         const int ns = n_sol[slot];
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
-            int c = cnt[t][k];
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o, 64);
+            const int c = wave_sum_i32(cnt[t][k]);
             const double s = wave_sum_f64(res[t][k]);
             if (lane == 0) {
                 h_inl[slot * 4 + k] = k < ns ? c : -1;      // -1 = no hypothesis in this slot
@@ -287,29 +284,22 @@ __device__ __forceinline__ bool row_inlier(const Pose& q, const double* __restri
 // marks the inliers of q (one byte per row, thread tid owns rows tid, tid + 256, ...) and returns their number to every thread
 __device__ int mark_inliers(const Pose& q, const double* __restrict__ pb, const double* __restrict__ xb, int n, double thr2,
                             unsigned char* __restrict__ mask, int* sred) {
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     int c = 0;
-    for (int i = tid; i < n; i += 256) {
+    for (int i = threadIdx.x; i < n; i += 256) {
         const bool in = row_inlier(q, pb + (size_t)i * 2, xb + (size_t)i * 3, thr2);
         mask[i] = in;
         c += in;
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o, 64);
-    __syncthreads();
-    if (lane == 0) sred[wave] = c;
-    __syncthreads();
-    return sred[0] + sred[1] + sred[2] + sred[3];
+    return block_sum_i32<4>(c, sred);
 }
 
 // cost, J^T W J, J^T W r over the masked rows at pose q -> tot[LM_VALS] in LDS (every thread may read it after the call)
 __device__ void lm_pass(const Pose& q, const Cam& cam, const float* __restrict__ kb, const double* __restrict__ xb, int n,
                         const unsigned char* __restrict__ mask, double (*wred)[LM_VALS], double* tot) {
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     double acc[LM_VALS];
 #pragma unroll
     for (int e = 0; e < LM_VALS; ++e) acc[e] = 0.0;
-    for (int i = tid; i < n; i += 256) {
+    for (int i = threadIdx.x; i < n; i += 256) {
         if (!mask[i]) continue;
         const double* X = xb + (size_t)i * 3;
         const double Y0 = q.R[0] * X[0] + q.R[1] * X[1] + q.R[2] * X[2];
@@ -341,57 +331,13 @@ __device__ void lm_pass(const Pose& q, const Cam& cam, const float* __restrict__
 #pragma unroll
         for (int a = 0; a < 6; ++a) acc[22 + a] += w * (J[0][a] * r0 + J[1][a] * r1);
     }
-    __syncthreads();      // tot / wred of the previous pass have been read
-#pragma unroll
-    for (int e = 0; e < LM_VALS; ++e) {
-        const double s = wave_sum_f64(acc[e]);
-        if (lane == 0) wred[wave][e] = s;
-    }
-    __syncthreads();
-    if (tid < LM_VALS) tot[tid] = ((wred[0][tid] + wred[1][tid]) + wred[2][tid]) + wred[3][tid];
-    __syncthreads();
+    block_fold_f64<LM_VALS>(acc, wred, tot);
 }
 
 struct LmShared {
-    double wred[4][LM_VALS];
-    double tot[LM_VALS];
-    double cur[LM_VALS];      // cost, H, g at the accepted pose
-    Pose cand;
-    int solved;
+    LmState<Pose, LM_VALS> lm;
     int sred[4];
 };
-
-// `iters` Levenberg-Marquardt iterations from q on the masked rows; every thread ends with the same pose
-__device__ void lm_refine(Pose& q, const Cam& cam, const float* __restrict__ kb, const double* __restrict__ xb, int n,
-                          const unsigned char* __restrict__ mask, int iters, LmShared& sh) {
-    const int tid = threadIdx.x;
-    lm_pass(q, cam, kb, xb, n, mask, sh.wred, sh.tot);
-    if (tid < LM_VALS) sh.cur[tid] = sh.tot[tid];
-    double lam = LM_LAMBDA0;
-    for (int it = 0; it < iters; ++it) {
-        __syncthreads();      // cur is complete, solved / cand of the previous iteration have been read
-        if (tid == 0) {
-            double d[6];
-            const bool okd = chol_solve6(sh.cur + 1, sh.cur + 22, lam, d);
-            if (okd) pose_update(q, d, sh.cand);
-            sh.solved = okd;
-        }
-        __syncthreads();
-        if (!sh.solved) { lam *= 10.0; continue; }      // uniform over the workgroup
-        const Pose c = sh.cand;
-        lm_pass(c, cam, kb, xb, n, mask, sh.wred, sh.tot);
-        const bool accept = sh.tot[0] < sh.cur[0];      // NaN compares false: rejected
-        __syncthreads();
-        if (accept) {
-            q = c;
-            if (tid < LM_VALS) sh.cur[tid] = sh.tot[tid];
-            lam = fmax(lam * 0.1, 1e-15);
-        } else {
-            lam *= 10.0;
-        }
-    }
-    __syncthreads();
-}
 
 __global__ __launch_bounds__(256) void pose_refine_kernel(const float* __restrict__ kpts, const double* __restrict__ pts,
                                                           const double* __restrict__ xyz, const int* __restrict__ count,
@@ -430,15 +376,20 @@ __global__ __launch_bounds__(256) void pose_refine_kernel(const float* __restric
         h.t[a] = hp[a * 4 + 3];
     }
     Pose q = h;
+    // `iters` Levenberg-Marquardt iterations from q on the masked rows; every thread ends with the same pose
+    const auto pass = [&](const Pose& m) { lm_pass(m, cam, kb, xb, n, mask, sh.lm.wred, sh.lm.tot); };
+    const auto step = [](const double* cur, double lam, const Pose& from, Pose& cand) {
+        double d[6];
+        const bool okd = chol_solve6(cur + 1, cur + 22, lam, d);
+        if (okd) pose_update(from, d, cand);
+        return okd;
+    };
     mark_inliers(q, pb, xb, n, thr2, mask, sh.sred);
-    lm_refine(q, cam, kb, xb, n, mask, iters, sh);
+    lm_refine(q, iters, sh.lm, pass, step);
     mark_inliers(q, pb, xb, n, thr2, mask, sh.sred);
-    lm_refine(q, cam, kb, xb, n, mask, iters, sh);
+    lm_refine(q, iters, sh.lm, pass, step);
     int n2 = mark_inliers(q, pb, xb, n, thr2, mask, sh.sred);
-    bool okq = true;
-    for (int a = 0; a < 9; ++a) okq = okq && fin(q.R[a]);
-    for (int a = 0; a < 3; ++a) okq = okq && fin(q.t[a]);
-    if (n2 < n0 || !okq) {      // the refined pose lost support: the hypothesis stands
+    if (n2 < n0 || !pose_finite(q)) {      // the refined pose lost support: the hypothesis stands
         q = h;
         n2 = mark_inliers(q, pb, xb, n, thr2, mask, sh.sred);
     }

@@ -1,5 +1,6 @@
 // What the RANSAC stages share (pose.hip, twoview.hip): the ranking rule and the kernel that picks a pair's best slot by it, the
-// 6 x 6 damped Cholesky of the Levenberg-Marquardt step and the rotation-to-quaternion conversion.  bundle.hip takes the
+// 6 x 6 damped Cholesky of the Levenberg-Marquardt step, the pose (Pose) with its rotation update and finiteness test, the
+// Levenberg-Marquardt driver of a workgroup (LmState, lm_refine) and the rotation-to-quaternion conversion.  bundle.hip takes the
 // Cholesky, the conversion and the pose tangent (Pose, pose_update) from here.
 #pragma once
 #include "camera.h"
@@ -76,10 +77,18 @@ static __device__ bool chol_solve6(const double* __restrict__ Hu, const double* 
     return okx;
 }
 
-// The pose tangent of the Levenberg-Marquardt steps (pose.hip, bundle.hip): R <- exp([w]x) R, t <- t + d
+// A rigid motion x -> R x + t, R row-major: an absolute pose (pose.hip, bundle.hip) or a relative one (twoview.hip, |t| = 1)
 struct Pose { double R[9], t[3]; };
 
-static __device__ void pose_update(const Pose& q, const double* __restrict__ d, Pose& o) {
+__device__ __forceinline__ bool pose_finite(const Pose& q) {
+    bool okq = true;
+    for (int a = 0; a < 9; ++a) okq = okq && fin(q.R[a]);
+    for (int a = 0; a < 3; ++a) okq = okq && fin(q.t[a]);
+    return okq;
+}
+
+// out = exp([d]x) R by Rodrigues' formula on d[0 .. 3), first order below |d| = 1e-12
+static __device__ void rot_exp_left(const double* __restrict__ d, const double* __restrict__ R, double* __restrict__ out) {
     const double th = sqrt(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
     double E[9];
     if (th < 1e-12) {
@@ -95,8 +104,55 @@ static __device__ void pose_update(const Pose& q, const double* __restrict__ d, 
             }
     }
     for (int a = 0; a < 3; ++a)
-        for (int c = 0; c < 3; ++c) o.R[a * 3 + c] = E[a * 3] * q.R[c] + E[a * 3 + 1] * q.R[3 + c] + E[a * 3 + 2] * q.R[6 + c];
+        for (int c = 0; c < 3; ++c) out[a * 3 + c] = E[a * 3] * R[c] + E[a * 3 + 1] * R[3 + c] + E[a * 3 + 2] * R[6 + c];
+}
+
+// the pose tangent of the Levenberg-Marquardt steps (pose.hip, bundle.hip): R <- exp([w]x) R, t <- t + d
+static __device__ void pose_update(const Pose& q, const double* __restrict__ d, Pose& o) {
+    rot_exp_left(d, q.R, o.R);
     o.t[0] = q.t[0] + d[3]; o.t[1] = q.t[1] + d[4]; o.t[2] = q.t[2] + d[5];
+}
+
+// The Levenberg-Marquardt driver of one workgroup of 256 threads over NV sums (cost first, then H and g as the model lays them
+// out).  The state lives in LDS; wred and tot are block_fold_f64's.
+constexpr double LM_LAMBDA0 = 1e-3;
+
+template <class Model, int NV>
+struct LmState {
+    double wred[4][NV];
+    double tot[NV];
+    double cur[NV];      // cost, H, g at the accepted model
+    Model cand;
+    int solved;
+};
+
+// `iters` iterations from q; every thread calls it with the same q and ends with the same model.  pass(m) is called by every
+// thread and leaves cost, H, g at m in sh.tot, readable by every thread (it ends in block_fold_f64); step(cur, lam, q, cand) runs
+// on thread 0 alone, solves the damped system at the accepted sums `cur` and writes the candidate, false when there is none.
+template <class Model, int NV, class Pass, class Step>
+__device__ __forceinline__ void lm_refine(Model& q, int iters, LmState<Model, NV>& sh, Pass pass, Step step) {
+    const int tid = threadIdx.x;
+    pass(q);
+    if (tid < NV) sh.cur[tid] = sh.tot[tid];
+    double lam = LM_LAMBDA0;
+    for (int it = 0; it < iters; ++it) {
+        __syncthreads();      // cur is complete, solved / cand of the previous iteration have been read
+        if (tid == 0) sh.solved = step(sh.cur, lam, q, sh.cand);
+        __syncthreads();
+        if (!sh.solved) { lam *= 10.0; continue; }      // uniform over the workgroup
+        const Model c = sh.cand;
+        pass(c);
+        const bool accept = sh.tot[0] < sh.cur[0];      // NaN compares false: rejected
+        __syncthreads();
+        if (accept) {
+            q = c;
+            if (tid < NV) sh.cur[tid] = sh.tot[tid];
+            lam = fmax(lam * 0.1, 1e-15);
+        } else {
+            lam *= 10.0;
+        }
+    }
+    __syncthreads();
 }
 
 static __device__ void rot_to_qvec(const double* __restrict__ R, double* __restrict__ qv) {

@@ -93,7 +93,7 @@ __global__ __launch_bounds__(256) void covis_topk_kernel(const int* __restrict__
                                                          int* __restrict__ best_frames, int* __restrict__ best_counts,
                                                          int* __restrict__ n_found) {
     __shared__ unsigned long long wbest[4];
-    const int s = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int s = blockIdx.x, tid = threadIdx.x;
     int f = frames[s];
     if (f < 0 || f >= n_frames) f = -1;      // a frame the store does not hold shares nothing with anyone
     int v0 = 0, v1 = 0;
@@ -125,16 +125,7 @@ __global__ __launch_bounds__(256) void covis_topk_kernel(const int* __restrict__
             const unsigned long long key = ((unsigned long long)(unsigned)c << 32) | (unsigned)(0x7fffffff - g);
             if (c > 0 && key < prev && key > best) best = key;
         }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            const unsigned long long other = __shfl_xor(best, o, 64);
-            best = other > best ? other : best;
-        }
-        if (lane == 0) wbest[wave] = best;
-        __syncthreads();
-        best = wbest[0];
-        for (int w = 1; w < 4; ++w) best = wbest[w] > best ? wbest[w] : best;
-        __syncthreads();
+        best = block_max_u64<4>(best, wbest);
         if (best != 0) { prev = best; ++found; }
         else prev = 0;      // nothing left: every later round finds nothing either
         if (tid == 0) {

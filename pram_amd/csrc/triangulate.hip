@@ -1,7 +1,7 @@
 // A map's points from pairwise matches and known poses (what localization/triangulation.py of the reference hands to COLMAP):
 // normalised keypoints, the epipolar test of every match, connected components over the kept matches, the CSR table of tracks and
 // one robust multi-view solve per track.  float64 throughout; every sum runs per lane in ascending entry order and is combined by
-// the butterfly of wave_sum_f64, so a result does not depend on the launch or the run.  DESIGN.md 4.21 has the formulas and the
+// the butterfly of workgroup.h's wave_sum_f64, so a result does not depend on the launch or the run.  DESIGN.md 4.21 has the formulas and the
 // deviations from COLMAP's incremental triangulator.
 #include "obs.h"
 #include "glue.h"

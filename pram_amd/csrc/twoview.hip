@@ -20,7 +20,6 @@ constexpr int SCORE_CHUNK = 768;          // rows per LDS chunk: 4 doubles each 
 constexpr int SCORE_TPW = 2;              // trials a wave takes in turn on every chunk
 constexpr int SCORE_TRIALS = 4 * SCORE_TPW;      // trials per workgroup
 constexpr int SCORE_HALF = MAX_SOL / 2;   // solution slots scored together from registers
-constexpr double LM_LAMBDA0 = 1e-3;
 constexpr int LM_VALS = 21;               // cost, 15 of J^T W J (upper triangle, row-major), 5 of J^T W r
 
 // ---------------------------------------------------------------- a pair's rows: (u0, v0, u1, v1) of a match, NaN outside a frame
@@ -463,7 +462,15 @@ __global__ __launch_bounds__(256) void twoview_score_kernel(const double* __rest
 }
 
 // ---------------------------------------------------------------- finish: decomposition, refinement, the outputs of a pair
-struct Rel { double R[9], t[3]; };      // frame 1 from frame 0, |t| = 1
+using Rel = Pose;      // frame 1 from frame 0, |t| = 1
+
+struct FinishShared {
+    LmState<Rel, LM_VALS> lm;
+    Rel more[3];      // with lm.cand the four of the decomposition, before the refinement takes lm.cand for its candidate
+    int sred[4];
+    int wsum[4];
+    __device__ Rel& cand(int k) { return k == 0 ? lm.cand : more[k - 1]; }
+};
 
 __device__ __forceinline__ void essential_of(const Rel& q, double* E) {      // [t]x R / sqrt(2): Frobenius norm 1
     const double s = sqrt(2.0);
@@ -477,7 +484,7 @@ __device__ __forceinline__ void essential_of(const Rel& q, double* E) {      // 
 
 // The four (R, t) of a Frobenius-normalised E: t the largest cross product of two columns, normalised; R = cof(E') -+ [t]x E' with
 // E' = sqrt(2) E (Horn 1990), then Gram-Schmidt with the third row the cross product of the first two: det R = +1.
-__device__ void decompose(const double* __restrict__ E, Rel* out) {
+__device__ void decompose(const double* __restrict__ E, FinishShared& sh) {
     const V3 c0 = {E[0], E[3], E[6]}, c1 = {E[1], E[4], E[7]}, c2 = {E[2], E[5], E[8]};
     V3 b = cross(c0, c1);
     double bn = dot(b, b);
@@ -509,7 +516,7 @@ __device__ void decompose(const double* __restrict__ E, Rel* out) {
         a1 = {a1.x / n1, a1.y / n1, a1.z / n1};
         const V3 a2 = cross(a0, a1);
         for (int w = 0; w < 2; ++w) {
-            Rel& q = out[v * 2 + w];
+            Rel& q = sh.cand(v * 2 + w);
             q.R[0] = a0.x; q.R[1] = a0.y; q.R[2] = a0.z; q.R[3] = a1.x; q.R[4] = a1.y; q.R[5] = a1.z; q.R[6] = a2.x; q.R[7] = a2.y; q.R[8] = a2.z;
             const double ts = w == 0 ? 1.0 : -1.0;
             q.t[0] = ts * t.x; q.t[1] = ts * t.y; q.t[2] = ts * t.z;
@@ -528,16 +535,6 @@ __device__ __forceinline__ bool in_front(const Rel& q, double u0, double v0, dou
     return lam0 > 0.0 && lam1 > 0.0;
 }
 
-// the sum of a per-thread count over the workgroup, to every thread
-__device__ int block_sum(int c, int* sred) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    c = wave_sum_i32(c);
-    __syncthreads();
-    if (lane == 0) sred[wave] = c;
-    __syncthreads();
-    return sred[0] + sred[1] + sred[2] + sred[3];
-}
-
 // marks the Sampson inliers of E (one byte per match, thread tid owns matches tid, tid + 256, ...) and returns their number
 __device__ int mark_inliers(const double* __restrict__ E, const PairRows& g, double thr2, unsigned char* __restrict__ mask, int* sred) {
     int c = 0;
@@ -548,7 +545,7 @@ __device__ int mark_inliers(const double* __restrict__ E, const PairRows& g, dou
         mask[i] = in;
         c += in;
     }
-    return block_sum(c, sred);
+    return block_sum_i32<4>(c, sred);
 }
 
 __device__ int count_front(const Rel& q, const PairRows& g, const unsigned char* __restrict__ mask, int* sred) {
@@ -559,7 +556,7 @@ __device__ int count_front(const Rel& q, const PairRows& g, const unsigned char*
         load_row(g, i, u0, v0, u1, v1);
         c += in_front(q, u0, v0, u1, v1);
     }
-    return block_sum(c, sred);
+    return block_sum_i32<4>(c, sred);
 }
 
 // two unit vectors that span the tangent plane of the sphere at t: along t x (the axis where |t| is smallest), and t x that
@@ -585,7 +582,6 @@ __device__ __forceinline__ void skew_times(V3 v, const double* __restrict__ R, d
 
 // cost, J^T W J, J^T W r of sum log(1 + (d / scale)^2), d the signed Sampson distance, over the masked matches at q -> tot[LM_VALS]
 __device__ void lm_pass(const Rel& q, const PairRows& g, const unsigned char* __restrict__ mask, double scale, double (*wred)[LM_VALS], double* tot) {
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     double E[9], dE[5][9];
     const V3 tv = {q.t[0], q.t[1], q.t[2]};
     skew_times(tv, q.R, E);
@@ -603,7 +599,7 @@ __device__ void lm_pass(const Rel& q, const PairRows& g, const unsigned char* __
     double acc[LM_VALS];
 #pragma unroll
     for (int e = 0; e < LM_VALS; ++e) acc[e] = 0.0;
-    for (int i = tid; i < g.n; i += 256) {
+    for (int i = threadIdx.x; i < g.n; i += 256) {
         if (!mask[i]) continue;
         double u0, v0, u1, v1;
         load_row(g, i, u0, v0, u1, v1);
@@ -637,94 +633,17 @@ __device__ void lm_pass(const Rel& q, const PairRows& g, const unsigned char* __
 #pragma unroll
         for (int a = 0; a < 5; ++a) acc[16 + a] += w * (J[a] * r);
     }
-    __syncthreads();      // tot / wred of the previous pass have been read
-#pragma unroll
-    for (int e = 0; e < LM_VALS; ++e) {
-        const double s = wave_sum_f64(acc[e]);
-        if (lane == 0) wred[wave][e] = s;
-    }
-    __syncthreads();
-    if (tid < LM_VALS) tot[tid] = ((wred[0][tid] + wred[1][tid]) + wred[2][tid]) + wred[3][tid];
-    __syncthreads();
+    block_fold_f64<LM_VALS>(acc, wred, tot);
 }
 
 // R <- exp([w]x) R, t <- (t + d3 b1 + d4 b2) normalised
 __device__ void rel_update(const Rel& q, const double* __restrict__ d, Rel& o) {
-    const double th = sqrt(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
-    double X[9];
-    if (th < 1e-12) {
-        X[0] = 1.0; X[1] = -d[2]; X[2] = d[1]; X[3] = d[2]; X[4] = 1.0; X[5] = -d[0]; X[6] = -d[1]; X[7] = d[0]; X[8] = 1.0;
-    } else {
-        const double kx = d[0] / th, ky = d[1] / th, kz = d[2] / th;
-        const double K[9] = {0.0, -kz, ky, kz, 0.0, -kx, -ky, kx, 0.0};
-        const double sn = sin(th), cs = 1.0 - cos(th);
-        for (int a = 0; a < 3; ++a)
-            for (int c = 0; c < 3; ++c) {
-                const double kk = K[a * 3] * K[c] + K[a * 3 + 1] * K[3 + c] + K[a * 3 + 2] * K[6 + c];
-                X[a * 3 + c] = (a == c ? 1.0 : 0.0) + sn * K[a * 3 + c] + cs * kk;
-            }
-    }
-    for (int a = 0; a < 3; ++a)
-        for (int c = 0; c < 3; ++c) o.R[a * 3 + c] = X[a * 3] * q.R[c] + X[a * 3 + 1] * q.R[3 + c] + X[a * 3 + 2] * q.R[6 + c];
+    rot_exp_left(d, q.R, o.R);
     V3 b1, b2;
     tangent_basis(q.t, b1, b2);
     const double t0 = (q.t[0] + d[3] * b1.x) + d[4] * b2.x, t1 = (q.t[1] + d[3] * b1.y) + d[4] * b2.y, t2 = (q.t[2] + d[3] * b1.z) + d[4] * b2.z;
     const double n = sqrt(t0 * t0 + t1 * t1 + t2 * t2);
     o.t[0] = t0 / n; o.t[1] = t1 / n; o.t[2] = t2 / n;
-}
-
-struct FinishShared {
-    double wred[4][LM_VALS];
-    double tot[LM_VALS];
-    double cur[LM_VALS];      // cost, H, g at the accepted model
-    Rel cand[4];
-    int solved;
-    int sred[4];
-    int wsum[4];
-};
-
-// `iters` Levenberg-Marquardt iterations from q on the masked matches; every thread ends with the same model.  The 5 x 5 normal
-// equations go through chol_solve6 with the sixth unknown pinned (H66 = 1, g6 = 0).
-__device__ void lm_refine(Rel& q, const PairRows& g, const unsigned char* __restrict__ mask, double scale, int iters, FinishShared& sh) {
-    const int tid = threadIdx.x;
-    lm_pass(q, g, mask, scale, sh.wred, sh.tot);
-    if (tid < LM_VALS) sh.cur[tid] = sh.tot[tid];
-    double lam = LM_LAMBDA0;
-    for (int it = 0; it < iters; ++it) {
-        __syncthreads();      // cur is complete, solved / cand of the previous iteration have been read
-        if (tid == 0) {
-            double H6[21], g6[6], d[6];
-            int e6 = 0, e5 = 1;
-            for (int a = 0; a < 6; ++a)
-                for (int c = a; c < 6; ++c) H6[e6++] = (a < 5 && c < 5) ? sh.cur[e5++] : (a == 5 ? 1.0 : 0.0);
-            for (int a = 0; a < 5; ++a) g6[a] = sh.cur[16 + a];
-            g6[5] = 0.0;
-            const bool okd = chol_solve6(H6, g6, lam, d);
-            if (okd) rel_update(q, d, sh.cand[0]);
-            sh.solved = okd;
-        }
-        __syncthreads();
-        if (!sh.solved) { lam *= 10.0; continue; }      // uniform over the workgroup
-        const Rel c = sh.cand[0];
-        lm_pass(c, g, mask, scale, sh.wred, sh.tot);
-        const bool accept = sh.tot[0] < sh.cur[0];      // NaN compares false: rejected
-        __syncthreads();
-        if (accept) {
-            q = c;
-            if (tid < LM_VALS) sh.cur[tid] = sh.tot[tid];
-            lam = fmax(lam * 0.1, 1e-15);
-        } else {
-            lam *= 10.0;
-        }
-    }
-    __syncthreads();
-}
-
-__device__ __forceinline__ bool rel_finite(const Rel& q) {
-    bool okq = true;
-    for (int a = 0; a < 9; ++a) okq = okq && fin(q.R[a]);
-    for (int a = 0; a < 3; ++a) okq = okq && fin(q.t[a]);
-    return okq;
 }
 
 __global__ __launch_bounds__(256) void twoview_finish_kernel(const double* __restrict__ norm, const int* __restrict__ frame_off,
@@ -759,27 +678,41 @@ __global__ __launch_bounds__(256) void twoview_finish_kernel(const double* __res
         for (int a = 0; a < 9; ++a) Eh[a] = Es[((size_t)p * trials * MAX_SOL + bi) * 9 + a];
         mark_inliers(Eh, g, thr2, mask, sh.sred);
         // the (R, t) among the four with most inliers in front of both cameras, the lowest index on a tie
-        if (tid == 0) decompose(Eh, sh.cand);
+        if (tid == 0) decompose(Eh, sh);
         __syncthreads();
         int bf = -1, bk = 0;
         for (int k = 0; k < 4; ++k) {
-            const Rel c = sh.cand[k];
+            const Rel c = sh.cand(k);
             const int f = count_front(c, g, mask, sh.sred);
             if (f > bf) { bf = f; bk = k; }
         }
-        const Rel h = sh.cand[bk];
-        __syncthreads();      // cand[0] is the refinement's candidate from here on
-        good = rel_finite(h);
+        const Rel h = sh.cand(bk);
+        __syncthreads();      // lm.cand is the refinement's candidate from here on
+        good = pose_finite(h);
         if (good) {
+            // `iters` Levenberg-Marquardt iterations from q on the masked matches; every thread ends with the same model.  The
+            // 5 x 5 normal equations go through chol_solve6 with the sixth unknown pinned (H66 = 1, g6 = 0).
+            const auto pass = [&](const Rel& m) { lm_pass(m, g, mask, scale, sh.lm.wred, sh.lm.tot); };
+            const auto step = [](const double* cur, double lam, const Rel& from, Rel& cand) {
+                double H6[21], g6[6], d[6];
+                int e6 = 0, e5 = 1;
+                for (int a = 0; a < 6; ++a)
+                    for (int c = a; c < 6; ++c) H6[e6++] = (a < 5 && c < 5) ? cur[e5++] : (a == 5 ? 1.0 : 0.0);
+                for (int a = 0; a < 5; ++a) g6[a] = cur[16 + a];
+                g6[5] = 0.0;
+                const bool okd = chol_solve6(H6, g6, lam, d);
+                if (okd) rel_update(from, d, cand);
+                return okd;
+            };
             q = h;
-            lm_refine(q, g, mask, scale, iters, sh);
+            lm_refine(q, iters, sh.lm, pass, step);
             double Er[9];
             essential_of(q, Er);
             mark_inliers(Er, g, thr2, mask, sh.sred);
-            lm_refine(q, g, mask, scale, iters, sh);
+            lm_refine(q, iters, sh.lm, pass, step);
             essential_of(q, Er);
             support = mark_inliers(Er, g, thr2, mask, sh.sred);
-            if (support < n0 || !rel_finite(q)) {      // the refined model lost support: the hypothesis stands
+            if (support < n0 || !pose_finite(q)) {      // the refined model lost support: the hypothesis stands
                 q = h;
                 support = mark_inliers(Eh, g, thr2, mask, sh.sred);
 #pragma unroll
