@@ -1411,6 +1411,52 @@ int pram_ba_finish(const void* context, const double* qvec_in, const double* tve
                    double* qvec, double* tvec, double* xyz, unsigned char* obs_keep, double* obs_error, int* pt_keep,
                    double* pt_error, double* pt_angle, int* pt_kept, int* counts, void* stream);
 
+/* ---- bundle adjustment with camera groups (csrc/bundle.hip): the intrinsics refined with the poses and the points ------------
+ * The adjustment above with a second kind of unknown: the parameters of camera GROUPS.  A group is a set of frames that share one
+ * physical camera, hence one model and one parameter vector grp_params [n_groups][PRAM_BAC_GROUP_PARAMS]: the model's own
+ * parameters in COLMAP's order (3 for SIMPLE_PINHOLE, 4 for PINHOLE and SIMPLE_RADIAL, 5 for RADIAL, 8 for OPENCV), zero padded;
+ * a step is additive.  The reduced system has 6 n_frames + 8 n_groups unknowns; its preconditioner is block-Jacobi (a 6 x 6 block
+ * per frame, an 8 x 8 block per group, no coupling between them), its matvec exact.  DESIGN.md 4.27 has the passes, the fixed
+ * orders and the deviations from COLMAP.  The pram_ba_* entries are untouched by this; the state record, the stages, the reasons
+ * and the decision are theirs.
+ *
+ * The tables are pram_ba_begin's (there is no per-frame cam_params: a frame's parameters are its group's) and the groups':
+ * frm_grp [n_frames] the group of every frame, and its inverse as a CSR, grp_off [n_groups + 1] / grp_frame [n_frames], the frames
+ * of a group ascending.  grp_mask [n_groups]: eight bits per group, bit a freezes parameter a of the model's order; a parameter
+ * the model does not have and every parameter of a group without observations are frozen by the entry.  A frozen parameter's
+ * column is zero and its diagonal 1, so its step is exactly 0.  pram_bac_begin checks the group tables on the device as it checks
+ * the observation tables (every grp_frame in range, every frame in exactly one group, one model per group): a failure ends the run
+ * with PRAM_BA_REASON_TABLES before any kernel reads through them.
+ *
+ * Per observation the workspace holds PRAM_BAC_OBS_DOUBLES: sqrt(w) J_c [2][6], sqrt(w) J_k [2][8], sqrt(w) J_p [2][3],
+ * sqrt(w) r [2].  pram_bac_layout gives the offsets of the workspace's arrays [PRAM_BAC_ARRAYS + 1]: the first PRAM_BA_ARRAYS are
+ * pram_ba_layout's arrays, then the per-frame parameters (accepted, candidate), the groups' parameters (accepted, candidate), the
+ * groups' blocks [36], diag U_k, b_k, the groups' rows of cg_x / cg_r / cg_z / cg_p / cg_q, their dot products [2 n_groups] and
+ * block partials, the frames' partial sums [n_frames][60] and [n_frames][8], the groups' mask, candidate flag and model, and the
+ * block sums of the groups' folds [n_frames / PRAM_BA_BLOCK + n_groups + 1][60].
+ * A group's sum over its frames is the blocked order of PRAM_BA_BLOCK over grp_frame; a dot product adds the frames' total and
+ * the groups' total, frames first.  A candidate with a focal length that is not finite or not above 0 has cost NaN and is
+ * rejected.  pram_bac_finish writes pram_ba_finish's outputs, evaluated with the refined parameters, and grp_params
+ * [n_groups][PRAM_BAC_GROUP_PARAMS]: a group that never moved returns its input bit for bit.  `context`
+ * [PRAM_BAC_CONTEXT_BYTES] is HOST memory.  Limits: pram_ba_begin's, and 1 <= n_groups <= n_frames. */
+#define PRAM_BAC_OBS_DOUBLES 36
+#define PRAM_BAC_GROUP_PARAMS 8
+#define PRAM_BAC_ARRAYS 45
+#define PRAM_BAC_CONTEXT_BYTES 1024
+
+size_t pram_bac_workspace_bytes(int n_frames, int n_points, int n_obs, int n_groups, int max_iters);
+int pram_bac_layout(int n_frames, int n_points, int n_obs, int n_groups, int max_iters, size_t* offsets);
+int pram_bac_begin(const float* keypoints, const int* cam_model, const int* cam_model_host, const double* table, const double* xyz,
+                   const int* obs_row, const int* obs_frame, const int* obs_point, const int* frm_off, const int* pt_off,
+                   const int* pt_obs, const int* frozen, const int* frm_grp, const int* grp_off, const int* grp_frame,
+                   const double* grp_params, const int* grp_mask, int n_frames, int n_points, int n_obs, int n_rows, int n_groups,
+                   int max_iters, double loss_scale, double lam0, double cg_tol, double ftol, void* workspace, size_t workspace_bytes,
+                   void* context, void* stream);
+int pram_bac_iterate(const void* context, int n_iters, int cg_iters, int stages, void* stream);
+int pram_bac_finish(const void* context, const double* qvec_in, const double* tvec_in, double max_reproj_error, double min_tri_angle,
+                    double* qvec, double* tvec, double* xyz, unsigned char* obs_keep, double* obs_error, int* pt_keep,
+                    double* pt_error, double* pt_angle, int* pt_kept, int* counts, double* grp_params, void* stream);
+
 /* ---- incremental mapping (csrc/mapper.hip; pram_amd/localization/mapper.py drives these) ---------------------------------------
  * The glue that turns pram_twoview_*, pram_pose_*, pram_tri_* and pram_ba_* into a mapper that needs no poses: a seed pair, then
  * rounds of registration against the points so far, triangulation and adjustment.  NOT COLMAP's incremental mapper: every

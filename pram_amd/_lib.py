@@ -155,6 +155,11 @@ _SIGS = {
     "pram_ba_begin": (I, [P, P, P, P, P, P, P, P, P, P, P, P, P, I, I, I, I, I, C.c_double, C.c_double, C.c_double, C.c_double, P, SZ, P, P]),
     "pram_ba_iterate": (I, [P, I, I, I, P]),
     "pram_ba_finish": (I, [P, P, P, C.c_double, C.c_double, P, P, P, P, P, P, P, P, P, P, P]),
+    "pram_bac_workspace_bytes": (SZ, [I, I, I, I, I]),
+    "pram_bac_layout": (I, [I, I, I, I, I, P]),
+    "pram_bac_begin": (I, [P] * 17 + [I] * 6 + [C.c_double] * 4 + [P, SZ, P, P]),
+    "pram_bac_iterate": (I, [P, I, I, I, P]),
+    "pram_bac_finish": (I, [P, P, P, C.c_double, C.c_double, P, P, P, P, P, P, P, P, P, P, P, P]),
     "pram_map_pair_angles_workspace_bytes": (SZ, [I]),
     "pram_map_pair_angles": (I, [P, P, P, P, P, P, P, P, P, I, I, I, P, SZ, P, P, P]),
     "pram_map_seed": (I, [P, P, P, I, I, C.c_double, P, P]),

@@ -37,6 +37,36 @@ __device__ __forceinline__ void distort_jac(const Cam& c, double u, double v, do
     j22 = 1.0 + rad + 2.0 * v * v * dr + 2.0 * c.p2 * u + 6.0 * c.p1 * v;
 }
 
+// the number of parameters of a model (COLMAP's), and how many of the first are focal lengths
+__device__ __forceinline__ int cam_n_params(int model) {
+    switch (model) {
+        case PRAM_CAM_PINHOLE: case PRAM_CAM_SIMPLE_RADIAL: return 4;
+        case PRAM_CAM_RADIAL: return 5;
+        case PRAM_CAM_OPENCV: return 8;
+        default: return 3;
+    }
+}
+__device__ __forceinline__ int cam_n_focal(int model) { return model == PRAM_CAM_PINHOLE || model == PRAM_CAM_OPENCV ? 2 : 1; }
+
+// d residual / d (the model's own parameters, COLMAP's order): J [2][8], zero padded.  u, v: the normalised point; ud, vd: the
+// distorted point; r2 = u^2 + v^2 (obs_residual's).  A model with one focal length has the column (ud, vd) for f.
+__device__ __forceinline__ void cam_param_jac(int model, const Cam& c, double u, double v, double ud, double vd, double r2, double* J) {
+#pragma unroll
+    for (int e = 0; e < 16; ++e) J[e] = 0.0;
+    const double k1u = c.fx * u * r2, k1v = c.fy * v * r2, k2u = c.fx * u * r2 * r2, k2v = c.fy * v * r2 * r2;
+    switch (model) {
+        case PRAM_CAM_PINHOLE: J[0] = ud; J[9] = vd; J[2] = 1.0; J[11] = 1.0; break;
+        case PRAM_CAM_SIMPLE_RADIAL: J[0] = ud; J[8] = vd; J[1] = 1.0; J[10] = 1.0; J[3] = k1u; J[11] = k1v; break;
+        case PRAM_CAM_RADIAL: J[0] = ud; J[8] = vd; J[1] = 1.0; J[10] = 1.0; J[3] = k1u; J[11] = k1v; J[4] = k2u; J[12] = k2v; break;
+        case PRAM_CAM_OPENCV:
+            J[0] = ud; J[9] = vd; J[2] = 1.0; J[11] = 1.0; J[4] = k1u; J[12] = k1v; J[5] = k2u; J[13] = k2v;
+            J[6] = c.fx * (2.0 * u * v); J[14] = c.fy * (r2 + 2.0 * v * v);
+            J[7] = c.fx * (r2 + 2.0 * u * u); J[15] = c.fy * (2.0 * u * v);
+            break;
+        default: J[0] = ud; J[8] = vd; J[1] = 1.0; J[10] = 1.0; break;      // PRAM_CAM_SIMPLE_PINHOLE
+    }
+}
+
 struct V3 { double x, y, z; };
 __device__ __forceinline__ V3 sub(V3 a, V3 b) { return {a.x - b.x, a.y - b.y, a.z - b.z}; }
 __device__ __forceinline__ double dot(V3 a, V3 b) { return a.x * b.x + a.y * b.y + a.z * b.z; }

@@ -17,7 +17,11 @@ Where this differs from COLMAP / Ceres, on purpose:
   * not Ceres: fixed budgets (``max_iters`` LM iterations of at most ``cg_iters`` CG iterations), pose.hip's damping
     H + lam diag(H) and its lam x 0.1 / x 10 rule instead of a trust region with a gain ratio;
   * the robust cost enters as IRLS weights, with no Triggs correction of the Gauss-Newton matrix;
-  * intrinsics stay constant;
+  * intrinsics stay constant unless asked: ``refine_focal_length``, ``refine_principal_point`` and ``refine_extra_params``
+    (COLMAP's names and meanings; "extra" is the distortion) refine the parameters of camera groups, the frames that share one
+    physical camera (``camera_groups``), with the poses and the points.  Unlike COLMAP there are no priors on
+    the parameters and no bogus-parameter filter beyond the test that a focal length stays finite and positive; as in COLMAP the
+    principal point is off by default;
   * no Merge / Complete / Retriangulate between iterations: the tracks are the input's, the filter runs once, at the end.  Run
     triangulate_map again with the refined poses to get the tracks those poses support (INTEGRATION.md has the example);
   * the filter is COLMAP's FilterPoints3D as understood from its source: pycolmap is not installed and was never run beside
@@ -41,7 +45,7 @@ from pram_amd.localization.outliers import restrict_model
 # max_iters / cg_iters: profiles/bundle_timing.md has the iteration counts they were set from; lam0 is pose.hip's LM_LAMBDA0
 BA_DEFAULTS = dict(max_iters=40, cg_iters=60, cg_tol=1e-2, ftol=1e-6, loss_scale=1.0, lam0=1e-3,
                    max_reproj_error=tri.TRI_DEFAULTS["max_reproj_error"], min_tri_angle=tri.TRI_DEFAULTS["min_tri_angle"], gauge="colmap",
-                   frozen=None)
+                   frozen=None, refine_focal_length=False, refine_principal_point=False, refine_extra_params=False, camera_groups=None)
 BA_GROUP = 4      # LM iterations enqueued per look at the done word
 FROZEN_ALL = 63
 
@@ -59,7 +63,75 @@ def _ba_params(name: str, params: dict) -> dict:
         raise ValueError("needs 0 < cg_tol < 1, ftol >= 0, loss_scale > 0, lam0 > 0, max_reproj_error > 0, min_tri_angle >= 0")
     if p["gauge"] not in ("colmap", "none"):
         raise ValueError(f"gauge: 'colmap' or 'none', got {p['gauge']!r}")
+    for k in REFINE_FLAGS:
+        if not isinstance(p[k], (bool, np.bool_)):
+            raise ValueError(f"{k}: True or False")
     return p
+
+
+# ------------------------------------------------------------------ host side: the camera groups
+REFINE_FLAGS = ("refine_focal_length", "refine_principal_point", "refine_extra_params")
+# per model (COLMAP's parameter order): the indices of the focal lengths, of the principal point, of the extra parameters
+PARAM_KINDS = {"SIMPLE_PINHOLE": ((0,), (1, 2), ()), "PINHOLE": ((0, 1), (2, 3), ()), "SIMPLE_RADIAL": ((0,), (1, 2), (3,)),
+               "RADIAL": ((0,), (1, 2), (3, 4)), "OPENCV": ((0, 1), (2, 3), (4, 5, 6, 7))}
+GROUP_FROZEN_ALL = 255
+
+
+def _camera_key(cam) -> tuple:
+    name, w, h, prm = cam
+    return (str(name), int(w), int(h), np.asarray(prm, dtype=np.float64).tobytes())
+
+
+def camera_groups(cameras: Sequence, groups=None) -> np.ndarray:
+    """-> int32 [F], the group of every frame, numbered by first appearance.  ``groups`` None: frames whose camera tuples are equal
+    (the same model, width and height, bit-equal parameters) share a group.  An array: int [F], frames with equal values share one
+    camera; negative values, another shape or dtype, and a group whose frames differ in model, size or parameters raise."""
+    F = len(cameras)
+    keys = [_camera_key(c) for c in cameras]
+    if groups is None:
+        seen: dict = {}
+        return np.array([seen.setdefault(k, len(seen)) for k in keys], dtype=np.int32).reshape(F)
+    g = np.asarray(groups)
+    if g.shape != (F,) or not np.issubdtype(g.dtype, np.integer):
+        raise ValueError(f"camera_groups: an integer array [{F}]")
+    if (g < 0).any():
+        raise ValueError("camera_groups: values must not be negative")
+    seen, first, out = {}, {}, np.zeros(F, dtype=np.int32)
+    for f, v in enumerate(g.tolist()):
+        q = seen.setdefault(v, len(seen))
+        if first.setdefault(q, keys[f]) != keys[f]:
+            raise ValueError(f"camera_groups: frame {f} differs from its group's camera in model, size or parameters")
+        out[f] = q
+    return out
+
+
+def group_tables(cameras: Sequence, grp: np.ndarray, p: dict, masks=None) -> dict:
+    """The groups' tables of pram_bac_begin on the host: ``frm_grp`` int32 [F], the CSR ``grp_off`` int32 [G + 1] / ``grp_frame``
+    int32 [F] (ascending within a group), ``grp_params`` float64 [G, 8] (the model's own, zero padded), ``grp_mask`` int32 [G]
+    (bit a freezes parameter a: what the three flags leave frozen, or-ed with ``masks`` [G] when given), and per group
+    ``models`` (names) and ``first`` (its first frame)."""
+    grp = np.asarray(grp, dtype=np.int32)
+    G = int(grp.max()) + 1 if grp.shape[0] else 0
+    order = np.argsort(grp, kind="stable")
+    off = np.zeros(G + 1, dtype=np.int32)
+    off[1:] = np.cumsum(np.bincount(grp, minlength=G))
+    first = order[off[:-1]]
+    prm, mask, models = np.zeros((G, 8)), np.zeros(G, dtype=np.int32), []
+    for q, f in enumerate(first.tolist()):
+        name, _, _, x = cameras[f]
+        x = np.asarray(x, dtype=np.float64).reshape(-1)
+        prm[q, :x.shape[0]] = x
+        focal, pp, extra = PARAM_KINDS[str(name)]
+        free = (focal if p["refine_focal_length"] else ()) + (pp if p["refine_principal_point"] else ()) + (extra if p["refine_extra_params"] else ())
+        mask[q] = GROUP_FROZEN_ALL & ~sum(1 << a for a in free)
+        models.append(str(name))
+    if masks is not None:
+        mask = mask | (np.asarray(masks, dtype=np.int32).reshape(G) & GROUP_FROZEN_ALL)
+    return {"frm_grp": grp, "grp_off": off, "grp_frame": order.astype(np.int32), "grp_params": prm, "grp_mask": mask.astype(np.int32),
+            "models": models, "first": first}
+
+
+GROUP_KEYS = ("frm_grp", "grp_off", "grp_frame", "grp_params", "grp_mask")      # what goes to the device
 
 
 # ------------------------------------------------------------------ host side: the observation tables and the gauge
@@ -145,6 +217,21 @@ def _run(table: dict, tabs: dict, xyz: np.ndarray, mask: np.ndarray, qv: np.ndar
     """Everything on the device: the problem, the iterations in groups of BA_GROUP, the filter -> (problem, ops.ba_finish's dict)."""
     dev = table["keypoints"].device
     d = {k: tri._up(tabs[k], dev) for k in TABLE_KEYS}
+    if p.get("groups") is not None:      # a refine flag is set: the entries that carry the groups' parameters
+        gt = {k: tri._up(p["groups"][k], dev) for k in GROUP_KEYS}
+        prob = ops.bac_begin(table["keypoints"], table["cam_model"], table["cam_model_host"], table["frames"], tri._up(xyz, dev), d["obs_row"],
+                             d["obs_frame"], d["obs_point"], d["frm_off"], d["pt_off"], d["pt_obs"], tri._up(mask, dev), gt["frm_grp"], gt["grp_off"],
+                             gt["grp_frame"], gt["grp_params"], gt["grp_mask"], xyz.shape[0], tabs["obs_row"].shape[0], table["n_rows"],
+                             p["groups"]["grp_params"].shape[0], p["max_iters"], loss_scale=p["loss_scale"], lam0=p["lam0"], cg_tol=p["cg_tol"],
+                             ftol=p["ftol"])
+        state = prob["views"]["state_i32"]
+        for _ in range(0, p["max_iters"], BA_GROUP):
+            ops.bac_iterate(prob, BA_GROUP, p["cg_iters"])
+            if int(state[ops.BA_SI_DONE].item()):
+                break
+        out = ops.bac_finish(prob, tri._up(qv, dev), tri._up(tv, dev), max_reproj_error=p["max_reproj_error"],
+                             min_tri_angle=float(np.deg2rad(p["min_tri_angle"])))
+        return prob, out
     prob = ops.ba_begin(table["keypoints"], table["cam_model"], table["cam_params"], table["cam_model_host"], table["frames"], tri._up(xyz, dev),
                         d["obs_row"], d["obs_frame"], d["obs_point"], d["frm_off"], d["pt_off"], d["pt_obs"], tri._up(mask, dev), xyz.shape[0],
                         tabs["obs_row"].shape[0], table["n_rows"], p["max_iters"], loss_scale=p["loss_scale"], lam0=p["lam0"], cg_tol=p["cg_tol"],
@@ -207,10 +294,34 @@ def _solve(frames: Sequence[dict], cameras: Sequence, poses, model: dict, device
     table = tri.frame_table(frames, cameras, (qv, tv), device)
     tabs = observation_tables(model, frame_ids, table["frame_off_host"])
     mask = gauge_mask(p["gauge"], p["frozen"], tabs["frm_off"])
+    table["camera_groups"] = camera_groups(cameras, p["camera_groups"])
+    table["groups"] = group_tables(cameras, table["camera_groups"], p) if any(p[k] for k in REFINE_FLAGS) else None
     if tabs["obs_row"].shape[0] == 0:
         return table, tabs, qv, tv, xyz, None, None
-    prob, out = _run(table, tabs, xyz, mask, qv, tv, p)
+    prob, out = _run(table, tabs, xyz, mask, qv, tv, {**p, "groups": table["groups"]})
     return table, tabs, qv, tv, xyz, prob, out
+
+
+def _intrinsics(cameras: Sequence, table: dict, tabs: dict, refined) -> tuple:
+    """-> (the cameras of the result, report['intrinsics']): per group its model, frame and observation counts, the mask used and
+    the parameters before and after.  refined: float64 [G, 8] or None (nothing was refined: every frame gets its input tuple)."""
+    gt = table["groups"]
+    if gt is None:
+        return list(cameras), []
+    n_obs = np.diff(np.asarray(tabs["frm_off"], dtype=np.int64))
+    cams, rows = list(cameras), []
+    for q, name in enumerate(gt["models"]):
+        fr = gt["grp_frame"][gt["grp_off"][q]:gt["grp_off"][q + 1]]
+        n = ops.CAMERA_NUM_PARAMS[ops.CAMERA_MODELS[name]]
+        obs = int(n_obs[fr].sum())
+        used = GROUP_FROZEN_ALL if obs == 0 else int(gt["grp_mask"][q]) | (GROUP_FROZEN_ALL & ~((1 << n) - 1))
+        before = gt["grp_params"][q, :n].copy()
+        after = before.copy() if refined is None else np.asarray(refined[q, :n], dtype=np.float64).copy()
+        rows.append({"model": name, "frames": int(fr.shape[0]), "observations": obs, "mask": used, "params_before": before, "params_after": after})
+        if used != GROUP_FROZEN_ALL and not np.array_equal(before, after):
+            for f in fr.tolist():
+                cams[f] = (cameras[f][0], cameras[f][1], cameras[f][2], after.copy())
+    return cams, rows
 
 
 def bundle_adjust(frames: Sequence[dict], cameras: Sequence, poses, model: dict, device, **params) -> dict:
@@ -223,7 +334,14 @@ def bundle_adjust(frames: Sequence[dict], cameras: Sequence, poses, model: dict,
     ``lm_iterations``, ``lm_accepted``, ``accepted`` (bool per iteration), ``cg_iterations`` (per iteration), ``cg_breakdowns``,
     ``lam``, ``observations``, ``zero_weight_observations``, ``filtered_observations``, ``filtered_points``, ``unsolvable_points``
     and ``termination`` ('max_iters', 'ftol', or 'empty' for a model without observations).  params: BA_DEFAULTS (the module
-    docstring has the gauge).  With ``max_iters=0`` the poses and the points come back bit for bit and only the filter runs.
+    docstring has the gauge).  ``refine_focal_length`` / ``refine_principal_point`` / ``refine_extra_params`` (booleans, default
+    False) refine the intrinsics of the camera groups; ``camera_groups``: None (frames whose camera tuples are equal share a group,
+    :func:`camera_groups`) or an int array [F].  With all three False the adjustment is the one with constant intrinsics, bit for
+    bit.  The result also has ``cameras`` (one (model_name, width, height, params) tuple per frame, refined; a frame of a group that
+    was not refined gets its input tuple back), ``camera_groups`` (the array used) and ``report['intrinsics']`` (per group
+    ``model``, ``frames``, ``observations``, ``mask``, ``params_before``, ``params_after``; empty when nothing was asked).  A group
+    without observations is frozen.  Give ``result['cameras']`` to whatever reads the map afterwards (frame_table,
+    DatabaseStore.from_triangulation).  With ``max_iters=0`` the poses and the points come back bit for bit and only the filter runs.
     Everything is read back once, at the end.  The input is not modified."""
     p = _ba_params("bundle_adjust", params)
     table, tabs, qv, tv, xyz, prob, out = _solve(frames, cameras, poses, model, device, p)
@@ -233,13 +351,17 @@ def bundle_adjust(frames: Sequence[dict], cameras: Sequence, poses, model: dict,
                   "zero_weight_observations": 0, "filtered_observations": 0, "filtered_points": int(xyz.shape[0]), "unsolvable_points": 0,
                   "termination": "empty"}
         res = clean_model(model, tabs, table["frame_off_host"], xyz, np.zeros(xyz.shape[0], dtype=bool), np.zeros(xyz.shape[0]), np.zeros(0, dtype=bool))
-        res.update(qvecs=qv.copy(), tvecs=tv.copy(), removed_ids=np.asarray(model["point_ids"]), report=report)
+        cams, report["intrinsics"] = _intrinsics(cameras, table, tabs, None)
+        res.update(qvecs=qv.copy(), tvecs=tv.copy(), removed_ids=np.asarray(model["point_ids"]), report=report, cameras=cams,
+                   camera_groups=table["camera_groups"])
         return res
     # ---- the one read-back
     report = _report(prob, out, tabs["obs_row"].shape[0])
     host = {k: out[k].cpu().numpy() for k in ("qvec", "tvec", "xyz", "obs_keep", "pt_keep", "pt_error")}
     res = clean_model(model, tabs, table["frame_off_host"], host["xyz"], host["pt_keep"], host["pt_error"], host["obs_keep"])
-    res.update(qvecs=host["qvec"], tvecs=host["tvec"], removed_ids=np.asarray(model["point_ids"])[host["pt_keep"] == 0], report=report)
+    cams, report["intrinsics"] = _intrinsics(cameras, table, tabs, out["grp_params"].cpu().numpy() if "grp_params" in out else None)
+    res.update(qvecs=host["qvec"], tvecs=host["tvec"], removed_ids=np.asarray(model["point_ids"])[host["pt_keep"] == 0], report=report,
+               cameras=cams, camera_groups=table["camera_groups"])
     return res
 
 

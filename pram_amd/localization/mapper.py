@@ -336,7 +336,14 @@ def reconstruct(frames: Sequence[dict], cameras: Sequence, pairs, matches: Seque
       ``frames_tried``, ``frames_accepted``, ``correspondences``, ``cut`` (rows beyond max_corr), ``points``, ``observations``,
       ``ba_termination``, ``ba_initial_cost``, ``ba_final_cost``, ``ba_iterations``; round 0 is the seed's), ``unregistered``
       (frame -> one of REASONS, as the last look at the correspondences found it: after ``max_rounds`` a frame whose neighbours
-      are not registered yet has 'no_correspondences') and ``final_ba`` (bundle_adjust's report).
+      are not registered yet has 'no_correspondences') and ``final_ba`` (bundle_adjust's report);
+      ``cameras`` and ``camera_groups``: bundle_adjust's, one (model_name, width, height, params) tuple per frame.
+    Intrinsics.  ``bundle=dict(refine_focal_length=True, ...)`` (bundle.BA_DEFAULTS' three refine flags and ``camera_groups``)
+    reaches the final adjustment, which refines the camera groups' parameters and returns them as ``cameras``.  The per-round
+    solves ignore the flags and keep the intrinsics constant: they share the round's frame table, whose normalised keypoints come
+    from the input cameras.  So a caller with a rough focal length runs ``reconstruct`` again with the returned ``cameras``, so
+    that the two-view and P3P stages see them, and gives ``result['cameras']`` (not the input cameras) to
+    DatabaseStore.from_triangulation and triangulation.frame_table.
     World frame and scale: the camera frame of the seed's first frame, the seed baseline of length 1.  Without an eligible pair
     ``report['success']`` is False, the reason 'no_seed' and the model empty; nothing is raised.  params: MAP_DEFAULTS
     (``twoview``, ``triangulation``, ``bundle``: dicts of twoview.TWOVIEW_DEFAULTS', triangulation.TRI_DEFAULTS' and
@@ -355,7 +362,7 @@ def reconstruct(frames: Sequence[dict], cameras: Sequence, pairs, matches: Seque
     if seed < 0:
         res = _empty_model(frame_ids, table["frame_off_host"])
         res.update(res_tail, qvecs=qv, tvecs=tv, registered=np.zeros(F, dtype=bool), frame_round=np.full(F, -1, dtype=np.int32), seed_pair=-1,
-                   removed_ids=np.zeros(0, dtype=np.int64),
+                   removed_ids=np.zeros(0, dtype=np.int64), cameras=list(cameras), camera_groups=bundle.camera_groups(cameras, p["bundle"]["camera_groups"]),
                    report={"success": False, "reason": "no_seed", "seed_frames": None, "seed_relaxed": relaxed, "rounds": [],
                            "unregistered": {f: "no_correspondences" for f in range(F)}, "final_ba": None})
         return res

@@ -2747,6 +2747,94 @@ def ba_finish(problem: dict, qvec: torch.Tensor, tvec: torch.Tensor, max_reproj_
     return out
 
 
+# ---- bundle adjustment with camera groups (csrc/bundle.hip's pram_bac_*: DESIGN.md 4.27) ---------------------------------------
+BAC_OBS_DOUBLES, BAC_GROUP_PARAMS, BAC_CONTEXT_BYTES = 36, 8, 1024      # include/pram_hip.h
+CAMERA_NUM_PARAMS = {0: 3, 1: 4, 2: 4, 3: 5, 4: 8}      # by PRAM_CAM_* id, COLMAP's counts
+# the workspace's arrays: BA_ARRAYS with rows of BAC_OBS_DOUBLES, then the groups' (G: groups, G2: 2 G, C2: 2 ceil(G / BA_BLOCK), FB: F / BA_BLOCK + G + 1)
+BAC_ARRAYS = tuple((n, dt, c, BAC_OBS_DOUBLES if n == "jac" else k) for n, dt, c, k in BA_ARRAYS) + (
+    ("cam_params", torch.float64, "F", 8), ("cam_params_cand", torch.float64, "F", 8), ("grp_params", torch.float64, "G", 8),
+    ("grp_params_cand", torch.float64, "G", 8), ("g_block", torch.float64, "G", 36), ("g_diag_u", torch.float64, "G", 8), ("g_b", torch.float64, "G", 8),
+    ("g_cg_x", torch.float64, "G", 8), ("g_cg_r", torch.float64, "G", 8), ("g_cg_z", torch.float64, "G", 8), ("g_cg_p", torch.float64, "G", 8),
+    ("g_cg_q", torch.float64, "G", 8), ("group_dot", torch.float64, "G2", 1), ("g_partials", torch.float64, "C2", 1),
+    ("frame_group_sums", torch.float64, "F", 60), ("frame_mv_sums", torch.float64, "F", 8), ("grp_mask", torch.int32, "G", 1),
+    ("grp_bad", torch.int32, "G", 1), ("grp_model", torch.int32, "G", 1), ("fold_blocks", torch.float64, "FB", 60))
+
+
+def bac_begin(keypoints: torch.Tensor, cam_model: torch.Tensor, cam_model_host, table: torch.Tensor, xyz: torch.Tensor, obs_row: torch.Tensor,
+              obs_frame: torch.Tensor, obs_point: torch.Tensor, frm_off: torch.Tensor, pt_off: torch.Tensor, pt_obs: torch.Tensor,
+              frozen: torch.Tensor, frm_grp: torch.Tensor, grp_off: torch.Tensor, grp_frame: torch.Tensor, grp_params: torch.Tensor,
+              grp_mask: torch.Tensor, n_points: int, n_obs: int, n_rows: int, n_groups: int, max_iters: int, loss_scale: float = 1.0,
+              lam0: float = 1e-3, cg_tol: float = 1e-2, ftol: float = 1e-6) -> dict:
+    """The problem of pram_bac_begin: ba_begin's with camera groups in place of per-frame parameters (include/pram_hip.h has the
+    tables: frm_grp int32 [F], grp_off int32 [G + 1], grp_frame int32 [F], grp_params float64 [G, 8], grp_mask int32 [G]) -> ba_begin's
+    dict, ``views`` by BAC_ARRAYS' names, ``cam=True``.  The initial cost is enqueued; nothing is read back."""
+    import ctypes
+    L = _lib.load()
+    F, Pn, O, n, G, K = len(cam_model_host), int(n_points), int(n_obs), int(n_rows), int(n_groups), int(max_iters)
+    i32 = (("cam_model", cam_model), ("obs_row", obs_row), ("obs_frame", obs_frame), ("obs_point", obs_point), ("frm_off", frm_off),
+           ("pt_off", pt_off), ("pt_obs", pt_obs), ("frozen", frozen), ("frm_grp", frm_grp), ("grp_off", grp_off), ("grp_frame", grp_frame),
+           ("grp_mask", grp_mask))
+    _tri_chk(((keypoints, "keypoints", torch.float32), (grp_params, "grp_params", torch.float64), (table, "table", torch.float64),
+              (xyz, "xyz", torch.float64)) + tuple((t, nm, torch.int32) for nm, t in i32))
+    if F < 1 or Pn < 1 or O < 1 or n < 1 or G < 1 or G > F:
+        raise _lib.PramHipError("bac_begin: needs one frame, one point, one observation and one keypoint at least, and 1 <= groups <= frames")
+    assert keypoints.numel() >= 2 * n and cam_model.numel() >= F and table.numel() >= TRI_FRAME_COLS * F
+    assert xyz.numel() >= 3 * Pn and min(obs_row.numel(), obs_frame.numel(), obs_point.numel(), pt_obs.numel()) >= O
+    assert frm_off.numel() >= F + 1 and pt_off.numel() >= Pn + 1 and frozen.numel() >= F
+    assert frm_grp.numel() >= F and grp_frame.numel() >= F and grp_off.numel() >= G + 1 and grp_params.numel() >= BAC_GROUP_PARAMS * G and grp_mask.numel() >= G
+    need = int(L.pram_bac_workspace_bytes(F, Pn, O, G, K))
+    if need == 0:
+        raise _lib.PramHipError("pram_bac_begin: sizes beyond 2^24 frames, 2^28 points, 2^26 observations or 4096 iterations")
+    dev = keypoints.device
+    workspace = torch.empty(need, device=dev, dtype=torch.uint8)
+    offsets = (ctypes.c_size_t * (len(BAC_ARRAYS) + 1))()
+    _lib.check(L.pram_bac_layout(F, Pn, O, G, K, ctypes.addressof(offsets)), "pram_bac_layout")
+    count = {"F": F, "P": Pn, "O": O, "F2": 2 * F, "B2": 2 * ((F + BA_BLOCK - 1) // BA_BLOCK), "SD": BA_STATE_F64, "SI": BA_STATE_I32 + 2 * K,
+             "G": G, "G2": 2 * G, "C2": 2 * ((G + BA_BLOCK - 1) // BA_BLOCK), "FB": F // BA_BLOCK + G + 1}
+    views = {}
+    for (name, dt, cnt, cols), a in zip(BAC_ARRAYS, offsets):
+        nbytes = count[cnt] * cols * torch.empty(0, dtype=dt).element_size()
+        v = workspace[a:a + nbytes].view(dt)
+        views[name] = v.view(count[cnt], cols) if cols > 1 else v
+    host = _tri_models(cam_model_host, F)
+    context = ctypes.create_string_buffer(BAC_CONTEXT_BYTES)
+    _lib.check(L.pram_bac_begin(_p(keypoints), _p(cam_model), ctypes.addressof(host), _p(table), _p(xyz), _p(obs_row), _p(obs_frame), _p(obs_point),
+                                _p(frm_off), _p(pt_off), _p(pt_obs), _p(frozen), _p(frm_grp), _p(grp_off), _p(grp_frame), _p(grp_params),
+                                _p(grp_mask), F, Pn, O, n, G, K, float(loss_scale), float(lam0), float(cg_tol), float(ftol), _p(workspace),
+                                workspace.numel(), ctypes.addressof(context), _st()), "pram_bac_begin")
+    return {"context": context, "workspace": workspace, "views": views, "n_frames": F, "n_points": Pn, "n_obs": O, "n_groups": G, "max_iters": K,
+            "cam": True, "keep": (keypoints, cam_model, table, xyz, obs_row, obs_frame, obs_point, frm_off, pt_off, pt_obs, frozen, frm_grp,
+                                  grp_off, grp_frame, grp_params, grp_mask)}
+
+
+def bac_iterate(problem: dict, n_iters: int, cg_iters: int, stages: int = BA_STAGE_ALL):
+    """ba_iterate on a problem of bac_begin."""
+    import ctypes
+    L = _lib.load()
+    _lib.check(L.pram_bac_iterate(ctypes.addressof(problem["context"]), int(n_iters), int(cg_iters), int(stages), _st()), "pram_bac_iterate")
+
+
+def bac_finish(problem: dict, qvec: torch.Tensor, tvec: torch.Tensor, max_reproj_error: float = 4.0, min_tri_angle: float = 0.026179938779914945) -> dict:
+    """ba_finish on a problem of bac_begin, evaluated with the refined parameters, and ``grp_params`` float64 [G, 8]: the refined
+    parameters (a group that never moved keeps its input bit for bit)."""
+    import ctypes
+    L = _lib.load()
+    F, Pn, O, G = problem["n_frames"], problem["n_points"], problem["n_obs"], problem["n_groups"]
+    _tri_chk(((qvec, "qvec", torch.float64), (tvec, "tvec", torch.float64)))
+    assert qvec.numel() >= 4 * F and tvec.numel() >= 3 * F
+    dev = qvec.device
+    new = lambda m, dt, *rest: torch.empty(m, *rest, device=dev, dtype=dt)
+    out = {"qvec": new(F, torch.float64, 4), "tvec": new(F, torch.float64, 3), "xyz": new(Pn, torch.float64, 3), "obs_keep": new(O, torch.uint8),
+           "obs_error": new(O, torch.float64), "pt_keep": new(Pn, torch.int32), "pt_error": new(Pn, torch.float64),
+           "pt_angle": new(Pn, torch.float64), "pt_kept": new(Pn, torch.int32), "counts": new(2, torch.int32),
+           "grp_params": new(G, torch.float64, BAC_GROUP_PARAMS)}
+    _lib.check(L.pram_bac_finish(ctypes.addressof(problem["context"]), _p(qvec), _p(tvec), float(max_reproj_error), float(min_tri_angle),
+                                 _p(out["qvec"]), _p(out["tvec"]), _p(out["xyz"]), _p(out["obs_keep"]), _p(out["obs_error"]), _p(out["pt_keep"]),
+                                 _p(out["pt_error"]), _p(out["pt_angle"]), _p(out["pt_kept"]), _p(out["counts"]), _p(out["grp_params"]), _st()),
+               "pram_bac_finish")
+    return out
+
+
 # ---- incremental mapping (csrc/mapper.hip; pram_amd/localization/mapper.py drives these) --------------------------------------
 MAP_MAX_LINKS = 8      # PRAM_MAP_MAX_LINKS
 

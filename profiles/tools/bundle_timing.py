@@ -3,6 +3,11 @@ production size, of one conjugate-gradient iteration against the bytes it must m
 profiles/bundle_timing.md.
 
     python profiles/tools/bundle_timing.py [--frames 2000] [--points 100000] [--reps 10] [--out FILE]
+    python profiles/tools/bundle_timing.py --intrinsics [...]      # writes profiles/bundle_intrinsics_timing.md instead
+
+--intrinsics times the adjustment with camera groups (refine_focal_length: one group, the street's one camera) beside the one
+with constant intrinsics on the same map, in the same process, interleaved repetition by repetition: one LM iteration without its
+CG iterations, one CG iteration, and the whole call of each.
 
 The map: --frames pinhole cameras (640 x 480, f = 500) half a metre apart along a street, looking sideways; --points points 4 to
 12 m away, each seen by about eight of the frames around it with 0.5 px noise; the poses drift (a random walk of 0.02 degrees and
@@ -38,15 +43,15 @@ def resources() -> list:
     for line in r.stderr.splitlines():
         m = re.search(r"Function Name: (\S+)", line)
         if m:
-            name = re.search(r"(ba_\w+?_kernel|ransac_pick_kernel)", m.group(1))
-            cur = {"name": name.group(1) if name else m.group(1)}
+            name = re.search(r"(bac?_\w+?_kernel|ransac_pick_kernel)", m.group(1))
+            cur = {"name": (name.group(1) + ("<Bac>" if "INS_3BacE" in m.group(1) else "")) if name else m.group(1)}
             rows.append(cur)
         for key, pat in (("vgpr", r" VGPRs: (\d+)"), ("scratch", r"ScratchSize \[bytes/lane\]: (\d+)"), ("lds", r"LDS Size \[bytes/block\]: (\d+)"),
                          ("occ", r"Occupancy \[waves/SIMD\]: (\d+)"), ("spill", r"VGPRs Spill: (\d+)")):
             m = re.search(pat, line)
             if m and cur is not None:
                 cur[key] = int(m.group(1))
-    return [r for r in rows if r["name"].startswith("ba_")]
+    return [r for r in rows if r["name"].startswith(("ba_", "bac_"))]
 
 
 def simulate(n_frames: int, n_points: int, seed: int = 0) -> dict:
@@ -154,6 +159,96 @@ def measure(sim: dict, reps: int) -> dict:
             "F": F, "workspace": prob["workspace"].numel()}
 
 
+def measure_intrinsics(sim: dict, reps: int) -> dict:
+    """Flags off and on, interleaved: per repetition the stages of one LM iteration without CG and one CG iteration of each."""
+    import torch
+    from pram_amd import ops
+    from pram_amd.localization import bundle as BA
+    from pram_amd.localization import triangulation as TG
+    dev = torch.device("cuda:0")
+    p = BA._ba_params("bundle_timing", {"refine_focal_length": True})
+    qv, tv, ids, xyz, frame_ids = BA._inputs(sim["frames"], sim["poses"], sim["model"])
+    table = TG.frame_table(sim["frames"], sim["cameras"], (qv, tv), dev)
+    tabs = BA.observation_tables(sim["model"], frame_ids, table["frame_off_host"])
+    mask = TG._up(BA.gauge_mask("colmap", None, tabs["frm_off"]), dev)
+    d = {k: TG._up(tabs[k], dev) for k in BA.TABLE_KEYS}
+    gt = BA.group_tables(sim["cameras"], BA.camera_groups(sim["cameras"]), p)
+    g = {k: TG._up(gt[k], dev) for k in BA.GROUP_KEYS}
+    O, Pn, F, G = tabs["obs_row"].shape[0], xyz.shape[0], len(sim["frames"]), gt["grp_params"].shape[0]
+    kw = dict(loss_scale=p["loss_scale"], lam0=p["lam0"], cg_tol=p["cg_tol"], ftol=p["ftol"])
+    x = TG._up(xyz, dev)
+
+    def begin(cam: bool):
+        if cam:
+            return ops.bac_begin(table["keypoints"], table["cam_model"], table["cam_model_host"], table["frames"], x, d["obs_row"], d["obs_frame"],
+                                 d["obs_point"], d["frm_off"], d["pt_off"], d["pt_obs"], mask, g["frm_grp"], g["grp_off"], g["grp_frame"], g["grp_params"],
+                                 g["grp_mask"], Pn, O, table["n_rows"], G, p["max_iters"], **kw)
+        return ops.ba_begin(table["keypoints"], table["cam_model"], table["cam_params"], table["cam_model_host"], table["frames"], x, d["obs_row"],
+                            d["obs_frame"], d["obs_point"], d["frm_off"], d["pt_off"], d["pt_obs"], mask, Pn, O, table["n_rows"], p["max_iters"], **kw)
+
+    lm_bits = ops.BA_STAGE_LINEARISE | ops.BA_STAGE_BLOCKS | ops.BA_STAGE_CG_INIT
+    times = {(cam, k): [] for cam in (False, True) for k in ("lm", "cg", "step")}
+    ev = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
+    for rep in range(reps + 2):      # two warm-ups
+        for cam in (False, True):
+            it = ops.bac_iterate if cam else ops.ba_iterate
+            prob = begin(cam)
+            ev[0].record()
+            it(prob, 1, 0, lm_bits)
+            ev[1].record()
+            it(prob, 1, 1, ops.BA_STAGE_CG)
+            ev[2].record()
+            it(prob, 1, 0, ops.BA_STAGE_STEP)
+            ev[3].record()
+            torch.cuda.synchronize()
+            if rep >= 2:
+                for i, k in enumerate(("lm", "cg", "step")):
+                    times[(cam, k)].append(ev[i].elapsed_time(ev[i + 1]))
+    whole = {False: [], True: []}
+    reports = {}
+    for rep in range(3):
+        for cam in (False, True):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            res = BA.bundle_adjust(sim["frames"], sim["cameras"], sim["poses"], sim["model"], dev, refine_focal_length=cam)
+            torch.cuda.synchronize()
+            whole[cam].append((time.perf_counter() - t0) * 1e3)
+            reports[cam] = res["report"]
+    return {"times": times, "whole": whole, "reports": reports, "O": O, "P": Pn, "F": F, "G": G}
+
+
+def write_intrinsics(a, sim: dict, commit: str):
+    m = measure_intrinsics(sim, a.reps)
+    t, O = m["times"], m["O"]
+    lines = ["# Bundle adjustment with camera groups: time per iteration, flags off and on", "",
+             f"Measured {time.strftime('%Y-%m-%d')} on an MI355X by profiles/tools/bundle_timing.py --intrinsics, on top of commit {commit}.  Milliseconds, median "
+             f"(smallest .. largest) of {a.reps} repetitions after two warm-ups, between HIP events; flags off (pram_ba_*) and on (pram_bac_*, "
+             "refine_focal_length, one group: the street's one camera) in the same process, interleaved repetition by repetition.  No bar is set.", "",
+             f"## {m['F']} frames, {m['G']} group, {m['P']} points, {m['O']} observations (the simulated street of profiles/bundle_timing.md)", "",
+             "| | flags off | flags on | on / off |", "|---|---|---|---|"]
+    for k, name in (("lm", "one LM iteration without CG: linearise, blocks, CG start"), ("step", "its step: back-substitution, candidate, cost, decision, apply"),
+                    ("cg", "one CG iteration")):
+        off, on = t[(False, k)], t[(True, k)]
+        lines.append(f"| {name} | {med(off)} | {med(on)} | {statistics.median(on) / statistics.median(off):.2f} |")
+    lines.append(f"| bundle_adjust, whole call | {med(m['whole'][False])} | {med(m['whole'][True])} | {statistics.median(m['whole'][True]) / statistics.median(m['whole'][False]):.2f} |")
+    lines += ["", f"Derived, not measured: a CG iteration reads every observation's row twice; the row grows from 20 to 36 doubles (the 18 and 34 of them that are "
+              f"Jacobians: {2 * O * 18 * 8 / 1e6:.0f} MB -> {2 * O * 34 * 8 / 1e6:.0f} MB a CG iteration here), and the matvec has one launch more (the groups' "
+              "fold), the update and the direction one each.  The expected cost is that 36 / 20 growth of the traffic plus the launches.", ""]
+    for cam in (False, True):
+        r = m["reports"][cam]
+        lines.append(f"Flags {'on' if cam else 'off'}: {r['lm_iterations']} LM iterations ({r['lm_accepted']} accepted, {r['termination']}), CG iterations per LM iteration "
+                     f"{r['cg_iterations'].tolist()}; cost {r['initial_cost']:.1f} -> {r['final_cost']:.1f}; {r['cg_breakdowns']} CG breakdowns."
+                     + (f"  Focal length {r['intrinsics'][0]['params_before'][0]:.3f} -> {r['intrinsics'][0]['params_after'][0]:.3f} (planted 500)." if cam else ""))
+        lines.append("")
+    lines += ["## What the compiler reports (gfx950, -O3)", "", "| kernel | VGPRs | VGPR spills | scratch bytes / lane | static LDS bytes | occupancy (waves / SIMD) |",
+              "|---|---|---|---|---|---|"]
+    for r in resources():
+        lines.append(f"| {r['name']} | {r.get('vgpr')} | {r.get('spill')} | {r.get('scratch')} | {r.get('lds')} | {r.get('occ')} |")
+    lines.append("")
+    Path(a.out).write_text("\n".join(lines))
+    print("\n".join(lines))
+
+
 def pose_error(res: dict, sim: dict) -> tuple:
     from tests import bundle_ref as BR
     from tests import triangulation_ref as TR
@@ -169,13 +264,17 @@ def main():
     ap.add_argument("--frames", type=int, default=2000)
     ap.add_argument("--points", type=int, default=100000)
     ap.add_argument("--reps", type=int, default=10)
-    ap.add_argument("--out", default=str(ROOT / "profiles" / "bundle_timing.md"))
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--intrinsics", action="store_true")
     a = ap.parse_args()
+    a.out = a.out or str(ROOT / "profiles" / ("bundle_intrinsics_timing.md" if a.intrinsics else "bundle_timing.md"))
     import torch
     if not torch.cuda.is_available():
         raise SystemExit("bundle_timing: no GPU (a time is measured on the device or not at all)")
     commit = subprocess.run(["git", "-C", str(ROOT), "rev-parse", "--short", "HEAD"], capture_output=True, text=True).stdout.strip() or "working tree"
     sim = simulate(a.frames, a.points)
+    if a.intrinsics:
+        return write_intrinsics(a, sim, commit)
     m = measure(sim, a.reps)
     rep = m["report"]
     (r0, c0), (r1, c1) = pose_error(m["res"], sim)
