@@ -1517,6 +1517,58 @@ int pram_map_pack(const int* chosen, int n_chosen, const int* corr_off, const in
 int pram_map_live_edges(const int* edges, int n_edges, const int* row_frame, const unsigned char* registered, int n_frames,
                         int n_rows, int* edges_out, void* stream);
 
+/* ---- image retrieval (csrc/imgret.hip; pram_amd/localization/image_retrieval.py drives these) ----------------
+ * A VLAD vector per image (Jegou et al.; intra-normalisation after Arandjelovic and Zisserman) from its 128-D local descriptors
+ * and a vocabulary of k centres, and the best database images of every query by the inner product of two such vectors.  Not a
+ * restatement of anything in the reference, which ships no retrieval network.  desc float32 [n_rows][PRAM_IMGRET_DIM], centres
+ * float32 [k][PRAM_IMGRET_DIM], 1 <= k <= PRAM_IMGRET_MAX_K (the centres are staged in LDS: 128 KB at 256).  The result of every
+ * entry is a function of its inputs alone: every sum has the order written here, there are no floating-point atomics.  Every
+ * entry refuses (PRAM_E_ARG) a null or misaligned pointer (descriptor and vector rows 16 bytes, float64 and the workspace 8, int32
+ * 4), a size out of range and a workspace that is too small; none waits for the stream and none allocates. */
+#define PRAM_IMGRET_DIM 128
+#define PRAM_IMGRET_MAX_K 256
+#define PRAM_IMGRET_MAX_TOPK 64        /* a list slot per lane of the wave that keeps a query's list */
+#define PRAM_IMGRET_MAX_SPLITS 1024
+
+/* labels [n_rows]: the nearest centre of every row, the lowest index on a tie; dist float64 [n_rows]: its squared distance,
+ * the sum over d ascending of the square of double(x_d) - double(c_d), added to 0.0 (float64 on purpose: the products of fp32
+ * inputs are exact, so a numpy restatement reproduces every bit).  Every row of desc is read. */
+int pram_imgret_assign(const float* desc, int n_rows, const float* centres, int k, int* labels, double* dist, void* stream);
+
+/* Image i is the rows first[i] .. first[i] + count[i] - 1 of desc (clamped into [0, n_rows): no other row is read), which serves
+ * the stores' flat layout (frame_off) and a padded batch [B][N][128] with counts (first = b N) alike.  sums float64
+ * [n_img][k][128]: per image, centre c and dimension d the sum of double(x_d) - double(c_d) over the image's rows with
+ * labels == c, in ascending row index, added to 0.0; n_assigned [n_img][k]: how many rows that is.  A label outside [0, k)
+ * belongs to no centre. */
+int pram_imgret_aggregate(const float* desc, const int* labels, int n_rows, const float* centres, int k, const int* first,
+                          const int* count, int n_img, double* sums, int* n_assigned, void* stream);
+
+/* The Lloyd step of the vocabulary, from the two entries above with the "images" being blocks of consecutive rows: fold adds
+ * the blocks' sums [n_blk][k][128] and n_assigned [n_blk][k] onto total float64 [k][128] and total_n [k] in ascending block
+ * order (the caller zeroes both before an iteration and may hand its blocks over in several calls, in order); update then sets
+ * c <- float(double(c) + total / total_n) for every centre with total_n > 0; a centre without a row keeps its value. */
+int pram_imgret_fold(const double* sums, const int* n_assigned, int n_blk, int k, double* total, int* total_n, void* stream);
+int pram_imgret_update(float* centres, const double* total, const int* total_n, int k, void* stream);
+
+/* out float32 [n_img][k * 128] from sums: the block of centre c is v / n_c with n_c = sqrt of the sum over d ascending of v^2 (a
+ * zero block stays zero); g = sqrt of the sum, ONE chain over c ascending then d ascending, of the squares of those entries; out =
+ * float(entry / g).  An image whose sums are all zero (no rows) is all zeros. */
+int pram_imgret_normalize(const double* sums, int n_img, int k, float* out, void* stream);
+
+/* The best k database vectors of every query: q float32 [nq][L], db float32 [nd][L], L a multiple of 128, 1 <= k <=
+ * PRAM_IMGRET_MAX_TOPK, nd >= 1.  exclude [nq] or null: a database index the query may not return (-1: none); db_valid uint8
+ * [nd] or null: 0 bars a database vector for everybody.  idx [nq][k], sim [nq][k]: similarity descending, then database index
+ * ascending, at the cut too; entries beyond the allowed vectors hold -1 and 0.  A NaN similarity is never returned; -0.0 ranks
+ * as +0.0.  The similarity is exact fp32 on v_mfma_f32_32x32x2_f32: per (query, database vector) ONE accumulator chain over the
+ * whole of L in ascending index, from 0.0f, so a value depends neither on the tile it falls in nor on splits.  The grid is (tiles
+ * of 32 queries) x splits, each split a range of 128-row database tiles that leaves a list [nq][splits][k] of packed 64-bit keys
+ * in the workspace (the ordered float bits, then 0x7fffffff - index); a second launch merges them.  The order is total, so idx
+ * and sim are the same bits for every 1 <= splits <= PRAM_IMGRET_MAX_SPLITS.  The queries x database matrix is never written.
+ * The workspace size is 0 for sizes the entry refuses. */
+size_t pram_imgret_topk_workspace_bytes(int nq, int k, int splits);
+int pram_imgret_topk(const float* q, int nq, const float* db, int nd, int L, const int* exclude, const unsigned char* db_valid,
+                     int k, int splits, void* workspace, size_t workspace_bytes, int* idx, float* sim, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

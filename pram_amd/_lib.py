@@ -174,6 +174,13 @@ _SIGS = {
     "pram_retr_filter": (I, [P, P, P, P, P, P, P, I, I, P, P, I, I, P, P, P, P, P, P, P, P]),
     "pram_retr_select": (I, [P, P, P, I, I, I, I, P, P]),
     "pram_covis_topk": (I, [P, I, P, P, P, I, I, P, P, P, I, I, I, I, I, P, P, P, P, P]),
+    "pram_imgret_assign": (I, [P, I, P, I, P, P, P]),
+    "pram_imgret_aggregate": (I, [P, P, I, P, I, P, P, I, P, P, P]),
+    "pram_imgret_fold": (I, [P, P, I, I, P, P, P]),
+    "pram_imgret_update": (I, [P, P, P, I, P]),
+    "pram_imgret_normalize": (I, [P, I, I, P, P]),
+    "pram_imgret_topk_workspace_bytes": (SZ, [I, I, I]),
+    "pram_imgret_topk": (I, [P, I, P, I, I, P, P, I, I, P, SZ, P, P, P]),
 }
 
 

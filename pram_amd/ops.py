@@ -2940,3 +2940,105 @@ def map_live_edges(edges: torch.Tensor, n_edges: int, row_frame: torch.Tensor, r
     out = torch.empty(max(m, 1), 2, device=edges.device, dtype=torch.int32)
     _lib.check(L.pram_map_live_edges(_p(edges), m, _p(row_frame), _p(registered), F, n, _p(out), _st()), "pram_map_live_edges")
     return out
+
+
+# ---- image retrieval (csrc/imgret.hip; pram_amd/localization/image_retrieval.py drives these) --------------------------------
+IMGRET_DIM, IMGRET_MAX_K, IMGRET_MAX_TOPK, IMGRET_MAX_SPLITS = 128, 256, 64, 1024      # include/pram_hip.h
+IMGRET_QUERY_TILE, IMGRET_DB_TILE = 32, 128      # the tile of pram_imgret_topk's grid: what a choice of ``splits`` starts from
+
+
+def _imgret_rows(t: torch.Tensor, name: str) -> int:
+    _chk(t, name)
+    if t.dim() != 2 or t.shape[1] != IMGRET_DIM or not t.is_contiguous():
+        raise _lib.PramHipError(f"{name}: expected a contiguous float32 [n, {IMGRET_DIM}] tensor, got {tuple(t.shape)}")
+    return int(t.shape[0])
+
+
+def imgret_assign(desc: torch.Tensor, centres: torch.Tensor):
+    """desc float32 [n, 128], centres float32 [k, 128] -> (labels int32 [n]: the nearest centre, the lowest index on a tie, dist
+    float64 [n]: its squared distance, summed in float64 over ascending d)."""
+    L = _lib.load()
+    n, k = _imgret_rows(desc, "desc"), _imgret_rows(centres, "centres")
+    labels = torch.empty(max(n, 1), device=desc.device, dtype=torch.int32)
+    dist = torch.empty(max(n, 1), device=desc.device, dtype=torch.float64)
+    _lib.check(L.pram_imgret_assign(_p(desc), n, _p(centres), k, _p(labels), _p(dist), _st()), "pram_imgret_assign")
+    return labels[:n], dist[:n]
+
+
+def imgret_aggregate(desc: torch.Tensor, labels: torch.Tensor, centres: torch.Tensor, first: torch.Tensor, count: torch.Tensor):
+    """The residual sums of the images first[i] .. first[i] + count[i] - 1 (int32 [n_img] row ranges into desc) -> (sums float64
+    [n_img, k, 128]: per centre the sum of x - c over the image's rows with that label in ascending row index, n_assigned int32
+    [n_img, k])."""
+    L = _lib.load()
+    n, k = _imgret_rows(desc, "desc"), _imgret_rows(centres, "centres")
+    _tri_chk(((labels, "labels", torch.int32), (first, "first", torch.int32), (count, "count", torch.int32)))
+    assert labels.numel() >= n and first.dim() == 1 and count.numel() == first.numel()
+    m = first.numel()
+    sums = torch.empty(max(m, 1), max(k, 1), IMGRET_DIM, device=desc.device, dtype=torch.float64)
+    n_assigned = torch.empty(max(m, 1), max(k, 1), device=desc.device, dtype=torch.int32)
+    _lib.check(L.pram_imgret_aggregate(_p(desc), _p(labels), n, _p(centres), k, _p(first), _p(count), m, _p(sums), _p(n_assigned), _st()),
+               "pram_imgret_aggregate")
+    return sums[:m], n_assigned[:m]
+
+
+def imgret_fold(sums: torch.Tensor, n_assigned: torch.Tensor, total: torch.Tensor, total_n: torch.Tensor) -> None:
+    """Adds the blocks' sums float64 [n_blk, k, 128] and n_assigned int32 [n_blk, k] onto total float64 [k, 128] and total_n int32
+    [k], in ascending block order."""
+    L = _lib.load()
+    _tri_chk(((sums, "sums", torch.float64), (n_assigned, "n_assigned", torch.int32), (total, "total", torch.float64), (total_n, "total_n", torch.int32)))
+    k = int(total_n.numel())
+    assert sums.dim() == 3 and sums.shape[1] == k and sums.shape[2] == IMGRET_DIM and n_assigned.numel() == sums.shape[0] * k and total.numel() == k * IMGRET_DIM
+    _lib.check(L.pram_imgret_fold(_p(sums), _p(n_assigned), int(sums.shape[0]), k, _p(total), _p(total_n), _st()), "pram_imgret_fold")
+
+
+def imgret_update(centres: torch.Tensor, total: torch.Tensor, total_n: torch.Tensor) -> None:
+    """centres float32 [k, 128] in place: c <- float(double(c) + total / total_n) where total_n > 0."""
+    L = _lib.load()
+    k = _imgret_rows(centres, "centres")
+    _tri_chk(((total, "total", torch.float64), (total_n, "total_n", torch.int32)))
+    assert total.numel() == k * IMGRET_DIM and total_n.numel() == k
+    _lib.check(L.pram_imgret_update(_p(centres), _p(total), _p(total_n), k, _st()), "pram_imgret_update")
+
+
+def imgret_normalize(sums: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """sums float64 [n_img, k, 128] -> the VLAD vectors float32 [n_img, k * 128] (into ``out`` when given): every centre's block
+    divided by its norm, then the whole by its norm; an image without rows is all zeros."""
+    L = _lib.load()
+    _chk(sums, "sums", torch.float64)
+    if sums.dim() != 3 or sums.shape[2] != IMGRET_DIM or not sums.is_contiguous():
+        raise _lib.PramHipError(f"sums: expected a contiguous float64 [n_img, k, {IMGRET_DIM}] tensor, got {tuple(sums.shape)}")
+    m, k = int(sums.shape[0]), int(sums.shape[1])
+    if out is None:
+        out = torch.empty(max(m, 1), max(k, 1) * IMGRET_DIM, device=sums.device, dtype=torch.float32)
+    _chk(out, "out")
+    assert out.is_contiguous() and out.numel() >= m * k * IMGRET_DIM
+    _lib.check(L.pram_imgret_normalize(_p(sums), m, k, _p(out), _st()), "pram_imgret_normalize")
+    return out[:m]
+
+
+def imgret_topk(q: torch.Tensor, db: torch.Tensor, k: int, exclude: Optional[torch.Tensor] = None, db_valid: Optional[torch.Tensor] = None,
+                splits: int = 1, workspace: Optional[torch.Tensor] = None):
+    """q float32 [nq, L], db float32 [nd, L] (L a multiple of 128) -> (idx int32 [nq, k], sim float32 [nq, k]): per query the k
+    database rows of largest inner product (exact fp32, one chain over L), similarity descending, then index ascending; -1 / 0 where
+    fewer are allowed.  exclude int32 [nq]: an index the query may not return (-1 none); db_valid uint8 [nd]: 0 bars a row.  The
+    result is the same bits for every ``splits``."""
+    L_ = _lib.load()
+    _chk(q, "q"), _chk(db, "db")
+    if q.dim() != 2 or db.dim() != 2 or q.shape[1] != db.shape[1] or not q.is_contiguous() or not db.is_contiguous():
+        raise _lib.PramHipError(f"imgret_topk: expected contiguous float32 [nq, L] and [nd, L], got {tuple(q.shape)} and {tuple(db.shape)}")
+    nq, nd, Ln, k, splits = int(q.shape[0]), int(db.shape[0]), int(q.shape[1]), int(k), int(splits)
+    if exclude is not None:
+        _chk(exclude, "exclude", torch.int32)
+        assert exclude.is_contiguous() and exclude.numel() >= nq
+    if db_valid is not None:
+        _chk(db_valid, "db_valid", torch.uint8)
+        assert db_valid.is_contiguous() and db_valid.numel() >= nd
+    need = int(L_.pram_imgret_topk_workspace_bytes(nq, k, splits))
+    if workspace is None:
+        workspace = _workspace(need, q.device, "imgret_topk")
+    _chk(workspace, "workspace", torch.uint8)
+    idx = torch.empty(max(nq, 1), max(k, 1), device=q.device, dtype=torch.int32)
+    sim = torch.empty(max(nq, 1), max(k, 1), device=q.device, dtype=torch.float32)
+    _lib.check(L_.pram_imgret_topk(_p(q), nq, _p(db), nd, Ln, _p(exclude), _p(db_valid), k, splits, _p(workspace), workspace.numel(), _p(idx),
+                                   _p(sim), _st()), "pram_imgret_topk")
+    return idx[:nq], sim[:nq]
