@@ -18,17 +18,15 @@ ENTRIES = ("pram_ba_workspace_bytes", "pram_ba_layout", "pram_ba_begin", "pram_b
 
 
 def test_symbols_declared_and_exported(hip_lib):
+    """The entries' declarations, types and exports and header == ops for the constants: tests/test_abi_contract_cpu.py."""
     from pram_amd import _lib, ops
     from pram_amd.localization import bundle as BA
     header = (ROOT / "include" / "pram_hip.h").read_text()
-    for n in ENTRIES:
-        decl = re.search(r"\b" + n + r"\s*\(([^)]*)\)", header)
-        assert decl and n in _lib.exported_symbols() and hasattr(hip_lib, n), n
-        assert len(decl.group(1).split(",")) == len(_lib._SIGS[n][1]), n
+    assert set(ENTRIES) <= set(_lib.exported_symbols())
     for name, value in (("OBS_DOUBLES", BR.OBS_DOUBLES), ("BLOCK", BR.BLOCK), ("CONTEXT_BYTES", 512), ("STATE_F64", 16), ("STATE_I32", 16),
                         ("SD_COST", 0), ("SD_LAM", 2), ("SD_COST0", 9), ("SI_DONE", 0), ("SI_REASON", 1), ("SI_LM_ITER", 2), ("SI_ACCEPTED", 3),
                         ("SI_CG_FAIL", 9), ("STAGE_ALL", 31)):
-        assert int(re.search(r"#define PRAM_BA_" + name + r" (\d+)", header).group(1)) == value == getattr(ops, "BA_" + name), name
+        assert value == getattr(ops, "BA_" + name), name
     assert int(re.search(r"#define PRAM_BA_ARRAYS (\d+)", header).group(1)) == len(ops.BA_ARRAYS)
     tri_src, obs_h = (ROOT / "pram_amd" / "csrc" / "triangulate.hip").read_text(), (ROOT / "pram_amd" / "csrc" / "obs.h").read_text()
     pose_src, ransac_h = (ROOT / "pram_amd" / "csrc" / "pose.hip").read_text(), (ROOT / "pram_amd" / "csrc" / "ransac.h").read_text()

@@ -28,18 +28,16 @@ ENTRIES = ("pram_bac_workspace_bytes", "pram_bac_layout", "pram_bac_begin", "pra
 
 
 def test_symbols_declared_and_exported(hip_lib):
+    # the entries' declarations, types and exports and header == ops for the constants: tests/test_abi_contract_cpu.py
     from pram_amd import _lib, ops
     header = (ROOT / "include" / "pram_hip.h").read_text()
-    for n in ENTRIES:
-        decl = re.search(r"\b" + n + r"\s*\(([^)]*)\)", header)
-        assert decl and n in _lib.exported_symbols() and hasattr(hip_lib, n), n
-        assert len(decl.group(1).split(",")) == len(_lib._SIGS[n][1]), n
+    assert set(ENTRIES) <= set(_lib.exported_symbols())
     for name, value in (("OBS_DOUBLES", IR.OBS_DOUBLES), ("GROUP_PARAMS", IR.NK), ("CONTEXT_BYTES", 1024)):
-        assert int(re.search(r"#define PRAM_BAC_" + name + r" (\d+)", header).group(1)) == value == getattr(ops, "BAC_" + name), name
+        assert value == getattr(ops, "BAC_" + name), name
     assert int(re.search(r"#define PRAM_BAC_ARRAYS (\d+)", header).group(1)) == len(ops.BAC_ARRAYS)
     assert [a[0] for a in ops.BAC_ARRAYS[:len(ops.BA_ARRAYS)]] == [a[0] for a in ops.BA_ARRAYS] and ops.CAMERA_NUM_PARAMS == IR.N_PARAMS
     # the existing entries keep their constants
-    assert int(re.search(r"#define PRAM_BA_OBS_DOUBLES (\d+)", header).group(1)) == 20 and int(re.search(r"#define PRAM_BA_ARRAYS (\d+)", header).group(1)) == 25
+    assert ops.BA_OBS_DOUBLES == 20 and int(re.search(r"#define PRAM_BA_ARRAYS (\d+)", header).group(1)) == 25
     src = (ROOT / "pram_amd" / "csrc" / "bundle.hip").read_text()
     assert not re.search(r"atomicAdd\(\s*(&\s*)?g\.(sd|J|x|r|z|p|q|k|kc|gx|gr|gz|gpv|gq|fpart|mvpart)\b", src)      # no floating-point atomics
 

@@ -1,7 +1,6 @@
 """CPU: the numpy restatement of the reference's map compression (tests/compress_ref.py) against the fixture pinned by running
 the reference (tests/golden/compress_pinned.npz, tests/tools/gen_compress_pinned.py), what the scene is made for, and the host side
 of pram_amd.localization.compress that needs no GPU."""
-import re
 from pathlib import Path
 
 import numpy as np
@@ -14,14 +13,10 @@ ENTRIES = ("pram_compress_workspace_bytes", "pram_compress_select", "pram_compre
 
 
 def test_symbols_declared_and_exported(hip_lib):
+    # the entries' declarations, types and exports and header == ops for the constants: tests/test_abi_contract_cpu.py
     from pram_amd import _lib, ops
-    header = (ROOT / "include" / "pram_hip.h").read_text()
-    for n in ENTRIES:
-        decl = re.search(r"\b" + n + r"\s*\(([^)]*)\)", header)
-        assert decl and n in _lib.exported_symbols() and hasattr(hip_lib, n), n
-        assert len(decl.group(1).split(",")) == len(_lib._SIGS[n][1]), n
-    for name, value in (("ROW_TILE", CR.ROW_TILE), ("KPT_TILE", CR.KPT_TILE)):
-        assert int(re.search(r"#define PRAM_COMPRESS_" + name + r" (\d+)", header).group(1)) == value == getattr(ops, "COMPRESS_" + name)
+    assert set(ENTRIES) <= set(_lib.exported_symbols())
+    assert CR.ROW_TILE == ops.COMPRESS_ROW_TILE and CR.KPT_TILE == ops.COMPRESS_KPT_TILE
     assert (ROOT / "pram_amd" / "csrc" / "compress.hip").exists()
     assert hip_lib.pram_compress_workspace_bytes(100, 5) == 24 * 100 + 4 * 6 + 16 and hip_lib.pram_compress_workspace_bytes(-1, 5) == 0
 

@@ -2,7 +2,6 @@
 symbol surface, the Python module's defaults and refusals, and the margins of every discrete assertion tests/test_gpu_imgret.py
 makes on a scene: an input whose margin is too thin is replaced here, not excused on the device."""
 import inspect
-import re
 from pathlib import Path
 
 import numpy as np
@@ -116,13 +115,9 @@ def test_vocabulary_restatement():
 # ---------------------------------------------------------------- the symbol surface, defaults, refusals
 def test_header_and_exports(hip_lib):
     from pram_amd import _lib, ops
-    hdr = (ROOT / "include" / "pram_hip.h").read_text()
-    declared = sorted(set(re.findall(r"\b(pram_imgret_[a-z0-9_]+)\s*\(", hdr)))
-    assert declared == sorted(ENTRIES) == sorted(n for n in _lib.exported_symbols() if n.startswith("pram_imgret_"))
-    assert all(hasattr(hip_lib, n) for n in ENTRIES) and all(n in _lib._SIGS for n in ENTRIES)
-    const = lambda name: int(re.search(rf"#define PRAM_IMGRET_{name} (\d+)", hdr).group(1))
-    assert const("DIM") == IR.DIM == ops.IMGRET_DIM and const("MAX_K") == IR.MAX_K == ops.IMGRET_MAX_K
-    assert const("MAX_TOPK") == IR.MAX_TOPK == ops.IMGRET_MAX_TOPK and const("MAX_SPLITS") == ops.IMGRET_MAX_SPLITS
+    # exported == declared, by type, and header == ops for the PRAM_IMGRET_* constants: tests/test_abi_contract_cpu.py
+    assert sorted(ENTRIES) == sorted(n for n in _lib.exported_symbols() if n.startswith("pram_imgret_"))
+    assert IR.DIM == ops.IMGRET_DIM and IR.MAX_K == ops.IMGRET_MAX_K and IR.MAX_TOPK == ops.IMGRET_MAX_TOPK
     # the workspace function needs no device
     assert hip_lib.pram_imgret_topk_workspace_bytes(10, 20, 3) == 10 * 3 * 20 * 8
     assert hip_lib.pram_imgret_topk_workspace_bytes(10, 65, 1) == 0 and hip_lib.pram_imgret_topk_workspace_bytes(10, 0, 1) == 0

@@ -6,7 +6,6 @@ The label rule.  The restatement's distances are ((x0 - c0)^2 + (x1 - c1)^2) + (
 within about 10 ulp of R^2, R the largest centred norm.  A label may therefore differ from the fixture only where the restatement's
 margin between the best and the second-best distance is at most 2^-40 R^2 (a factor of 512 above that rounding), and for at most
 0.1 % of the points.  On the fixture's scenes the smallest margin is 9e-7 R^2: nothing is excused."""
-import re
 from pathlib import Path
 
 import numpy as np
@@ -33,14 +32,9 @@ def restated():
 
 
 def test_symbols_declared_and_exported(hip_lib):
+    # the entries' declarations, types and exports and header == ops for the PRAM_KMEANS_* constants: tests/test_abi_contract_cpu.py
     from pram_amd import _lib, ops
-    header = (ROOT / "include" / "pram_hip.h").read_text()
-    for n in ENTRIES:
-        decl = re.search(r"\b" + n + r"\s*\(([^)]*)\)", header)
-        assert decl and n in _lib.exported_symbols() and hasattr(hip_lib, n), n
-        assert len(decl.group(1).split(",")) == len(_lib._SIGS[n][1]), n
-    for name in ("BLOCK", "MAX_K", "MAX_TRIALS", "STATE_WORDS"):
-        assert int(re.search(r"#define PRAM_KMEANS_" + name + r" (\d+)", header).group(1)) == getattr(ops, "KMEANS_" + name), name
+    assert set(ENTRIES) <= set(_lib.exported_symbols())
     assert KR.BLOCK == ops.KMEANS_BLOCK and ops.KMEANS_MAX_K >= 4096 and ops.KMEANS_MAX_TRIALS >= 2 + int(np.log(ops.KMEANS_MAX_K))
     assert (ROOT / "pram_amd" / "csrc" / "kmeans.hip").exists()
     L = hip_lib

@@ -1,7 +1,6 @@
 """CPU: the numpy restatement of the reference's map-building stages (tests/mapbuild_ref.py) against the fixture pinned by running
 the reference (tests/golden/mapbuild_pinned.npz, tests/tools/gen_mapbuild_pinned.py), the branches the scene's landmarks take, and
 the host side of pram_amd.localization.mapbuild that needs no GPU."""
-import re
 from pathlib import Path
 
 import numpy as np
@@ -18,14 +17,10 @@ GAP = 4e-5
 
 
 def test_symbols_declared_and_exported(hip_lib):
+    # the entries' declarations, types and exports and header == ops for the constants: tests/test_abi_contract_cpu.py
     from pram_amd import _lib, ops
-    header = (ROOT / "include" / "pram_hip.h").read_text()
-    for n in ENTRIES:
-        decl = re.search(r"\b" + n + r"\s*\(([^)]*)\)", header)
-        assert decl and n in _lib.exported_symbols() and hasattr(hip_lib, n), n
-        assert len(decl.group(1).split(",")) == len(_lib._SIGS[n][1]), n
-    for name, value in (("SHORT_TRACK", MR.SHORT), ("ROW_LDS", MR.ROW_LDS)):
-        assert int(re.search(r"#define PRAM_MAPBUILD_" + name + r" (\d+)", header).group(1)) == value == getattr(ops, "MAPBUILD_" + name)
+    assert set(ENTRIES) <= set(_lib.exported_symbols())
+    assert MR.SHORT == ops.MAPBUILD_SHORT_TRACK and MR.ROW_LDS == ops.MAPBUILD_ROW_LDS
     assert (ROOT / "pram_amd" / "csrc" / "mapbuild.hip").exists()
 
 

@@ -33,12 +33,9 @@ def clean():
 def test_symbols_declared_and_exported(hip_lib):
     from pram_amd import _lib, ops
     header = (ROOT / "include" / "pram_hip.h").read_text()
-    for n in ENTRIES:
-        decl = re.search(r"\b" + n + r"\s*\(([^)]*)\)", header)
-        assert decl and n in _lib.exported_symbols() and hasattr(hip_lib, n), n
-        assert len(decl.group(1).split(",")) == len(_lib._SIGS[n][1]), n
-    for name, value in (("GN_STEPS", TR.GN_STEPS), ("FRAME_COLS", TR.FRAME_COLS), ("CC_STATE_WORDS", 4)):
-        assert int(re.search(r"#define PRAM_TRI_" + name + r" (\d+)", header).group(1)) == value == getattr(ops, "TRI_" + name)
+    # the entries' declarations, types and exports and header == ops for the constants: tests/test_abi_contract_cpu.py
+    assert set(ENTRIES) <= set(_lib.exported_symbols())
+    assert TR.GN_STEPS == ops.TRI_GN_STEPS and TR.FRAME_COLS == ops.TRI_FRAME_COLS and ops.TRI_CC_STATE_WORDS == 4
     assert int(re.search(r"#define PRAM_POSE_UNDISTORT_STEPS (\d+)", header).group(1)) == PR.UNDISTORT_STEPS
     assert (ROOT / "pram_amd" / "csrc" / "triangulate.hip").exists()
     cam_h, pose = (ROOT / "pram_amd" / "csrc" / "camera.h").read_text(), (ROOT / "pram_amd" / "csrc" / "pose.hip").read_text()

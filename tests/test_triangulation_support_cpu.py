@@ -31,14 +31,9 @@ def gpu_cases() -> dict:
 
 
 def test_symbols_declared_and_exported(hip_lib):
-    import re
-    from pathlib import Path
+    # the entries' declarations, types and exports: tests/test_abi_contract_cpu.py
     from pram_amd import _lib, ops
-    header = (Path(__file__).resolve().parents[1] / "include" / "pram_hip.h").read_text()
-    for n in ("pram_tri_adjacency_workspace_bytes", "pram_tri_adjacency", "pram_tri_support"):
-        decl = re.search(r"\b" + n + r"\s*\(([^)]*)\)", header)
-        assert decl and n in _lib.exported_symbols() and hasattr(hip_lib, n), n
-        assert len(decl.group(1).split(",")) == len(_lib._SIGS[n][1]), n
+    assert {"pram_tri_adjacency_workspace_bytes", "pram_tri_adjacency", "pram_tri_support"} <= set(_lib.exported_symbols())
     assert callable(ops.tri_adjacency) and callable(ops.tri_support)
 
 
